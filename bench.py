@@ -3,7 +3,7 @@
 (sum-aggregate + KAN([F,F,F])) forward AND backward on the synthetic power-law graph of
 SURVEY.md 8(d) (1M nodes / 10M edges, fp32 I/O).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload headline|config3|fastkan|model]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload headline|config3|fastkan|model] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 One JSON line on stdout (rank 0).  Besides the contract's fields it carries
@@ -13,6 +13,9 @@ One JSON line on stdout (rank 0).  Besides the contract's fields it carries
                         its matrix-core flops -- the limiting ones are the KAN kernels, not the aggregation
   fp32_mode_ms_per_step the same step on the exact-fp32 MFMA kernels (KAGNN_PRECISION=fp32)
   cpu_baseline          the oracle (the reference's algorithm, "port") on the host cores, bounded sample
+ms_per_step is the wall time of one of the K timed steps.  --dump-outputs DIR writes what the last timed step computed (the
+layer workloads: y, x_grad and the parameter gradients; model: loss, the state after the Adam step and the gradients) as
+DIR/<name>.npy; every input is seeded, so two builds run with the same arguments can be compared output for output.
 The timed path is the product's default: ONE library call per convolution each way (kagnn_gin_kan_layer_fwd / _bwd); the
 dominant kernel is timed live inside it by the library's stage timer (kagnn_stage_timer_*: HIP events on the launch stream).
 N > 1 (one rank per GPU): a probe runs the combinations {feature-sharded (north_star's scheme), column/row transposed} x
@@ -362,6 +365,34 @@ def other_layer_figures(dev, graph, n, e, steps=10):
     return out
 
 
+# ---------------------------------------------------------------------------------------------- --dump-outputs
+DUMP_BUDGET_BYTES = 60_000_000          # the contract allows 64 MB in all: headroom for the .npy headers
+
+
+def dump_outputs(out_dir, arrays, n):
+    """`arrays` (name -> tensor) as out_dir/<name>.npy in float32, so that two builds can be compared output for output.
+    Over DUMP_BUDGET_BYTES, the arrays with one row per node keep the same fixed sample of rows (randperm of N under seed 0,
+    first k, ascending), with k as large as the budget allows; every other array is written whole."""
+    import numpy as np
+    arrays = {k: v.detach().float() for k, v in arrays.items()}
+    per_node = [k for k, v in arrays.items() if v.dim() >= 1 and v.shape[0] == n]
+    whole_bytes = sum(4 * v.numel() for k, v in arrays.items() if k not in per_node)
+    row_bytes = sum(4 * arrays[k][0].numel() for k in per_node)
+    keep = n
+    if whole_bytes + n * row_bytes > DUMP_BUDGET_BYTES:
+        keep = (DUMP_BUDGET_BYTES - whole_bytes) // row_bytes if row_bytes and whole_bytes < DUMP_BUDGET_BYTES else 0
+        if keep < 1:
+            raise SystemExit(f"bench.py --dump-outputs: the outputs do not fit {DUMP_BUDGET_BYTES} bytes even with one row per node array")
+        rows = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:keep].sort().values
+        for k in per_node:
+            arrays[k] = arrays[k][rows.to(arrays[k].device)]
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v.cpu().numpy())
+    sys.stderr.write(f"bench.py: {len(arrays)} arrays of the last timed step -> {out_dir}"
+                     + (f" ({keep} of {n} rows of {', '.join(per_node)})\n" if keep < n else "\n"))
+
+
 # ---------------------------------------------------------------------------------------------- main
 class _Reporter:
     """N > 1 only.  Rank 0 hands every candidate for THE line (interim after each finished combination, complete at the end) to a
@@ -445,7 +476,12 @@ def main():
     ap.add_argument("--no-extras", action="store_true", help="skip the secondary figures (copy bandwidth, full model step)")
     ap.add_argument("--no-traffic", action="store_true", help="skip the rocprofv3 --pmc passes behind roofline.traffic")
     ap.add_argument("--no-fp32", action="store_true", help="skip the exact-fp32 step timing")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (float32, at most "
+                         "64 MB: a fixed row sample of the per-node arrays when they are larger); single GPU only")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     os.environ["KAGNN_PRECISION"] = args.precision
     os.environ["KAGNN_ACT"] = args.act
     hidden, grid = WORKLOADS[args.workload]
@@ -459,6 +495,8 @@ def main():
         if world == 1 and args.gpus > 1:
             raise SystemExit("--gpus N > 1 must be launched with torch.distributed.run (one rank per GPU)")
         args.gpus = world
+    if args.dump_outputs and world > 1:
+        raise SystemExit("--dump-outputs is single-GPU only (the sharded paths leave column shards on every rank)")
     # (forked before the first HIP call of this process: the child only reads a pipe and writes one line)
     reporter = _Reporter() if (world > 1 and rank == 0 and os.environ.get("KAGNN_BENCH_REPORTER", "1") == "1") else None
     dog = _Watchdog(rank) if world > 1 else None
@@ -523,11 +561,14 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
+    last_out = [None]          # what the last timed step returned (--dump-outputs)
+
     def timed(step, steps):
         sync()
         t0 = time.perf_counter()
         for _ in range(steps):
-            step()
+            last_out[0] = None            # (released before the next step allocates: the step's peak memory is unchanged)
+            last_out[0] = step()
         sync()
         dt = time.perf_counter() - t0
         if dist is not None:
@@ -570,6 +611,7 @@ def main():
             loss = ops.softmax_cross_entropy(module(xin, graph), labels, None, pre_softmax=True)
             loss.backward()
             opt.step()
+            return loss
         return step
 
     alt = None
@@ -593,6 +635,7 @@ def main():
                 p.grad = None
             y = conv(x, graph)
             y.backward(gy)
+            return y
         parallelism = "single GPU"
     else:
         from kagnn_amd.sharded import ShardedGIFASTKANLayer, ShardedGIKANLayer, ShardedNodeModel, TransposedShardedGIKANLayer
@@ -749,6 +792,15 @@ def main():
         dt = timed(step, args.steps)
     peak_bytes = torch.cuda.max_memory_allocated()          # (the memory contract, SURVEY 7.3: the reference needs 45.1 GB RSS at 1M / 64)
     prof_live = ops.LibraryStageTimer.collect()
+    if args.dump_outputs:      # what a caller of the timed path receives from its last step (before the fp32 / half steps below)
+        if model_wl:
+            got = {"loss": last_out[0]}
+            got.update({f"state.{k}": v for k, v in net.state_dict().items() if v.is_floating_point()})
+            got.update({f"grad.{k}": p.grad for k, p in net.named_parameters() if p.grad is not None})
+        else:
+            got = {"y": last_out[0], "x_grad": x.grad}
+            got.update({f"grad.{k}": p.grad for k, p in conv.named_parameters() if p.grad is not None})
+        dump_outputs(args.dump_outputs, got, n)
     if dog is not None:
         dog.phase("per-rank gather", 60.0)
     ms = dt / args.steps * 1e3

@@ -10,7 +10,6 @@ if ROOT not in sys.path:
 sys.dont_write_bytecode = True
 
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-REFERENCE = "/root/reference/node_classification_clean"
 
 
 def _keep_big_blocks_in_the_heap():
@@ -61,20 +60,6 @@ def golden():
     def load(name):
         return np.load(os.path.join(GOLDEN, name + ".npz"))
     return load
-
-
-@pytest.fixture(scope="session")
-def reference_modules():
-    """The live reference layers (only in the build container); tests using it auto-skip elsewhere."""
-    if not os.path.isdir(REFERENCE):
-        pytest.skip("/root/reference not present")
-    sys.path.insert(0, REFERENCE)
-    try:
-        import ekan as ref_ekan
-        import fastkan as ref_fastkan
-    finally:
-        sys.path.remove(REFERENCE)
-    return ref_ekan, ref_fastkan
 
 
 def pytest_sessionfinish(session, exitstatus):

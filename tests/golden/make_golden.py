@@ -735,9 +735,38 @@ def g12():
     save("g12_fastkan_gcn", **out)
 
 
+def g14():
+    """The reference modules' surface for tests/test_host_cpu.py (state_dict layout, parameter order, KANLinear's init
+    draw) and test_oracle_golden.test_live_reference_matches_oracle (one KANLinear and one FastKAN forward)."""
+    out = {}
+
+    def put(prefix, module):
+        sd = module.state_dict()
+        out[f"{prefix}.keys"] = np.array(list(sd))
+        out[f"{prefix}.param_names"] = np.array([n for n, _ in module.named_parameters()])
+        for kname, v in sd.items():
+            out[f"{prefix}.{kname}"] = npy(v)
+
+    torch.manual_seed(0)                            # test_reference_state_dict_loads
+    put("kan", ref_ekan.KAN([6, 5, 4], grid_size=4, spline_order=2))
+    put("fastkan", ref_fastkan.FastKAN([6, 5, 4], num_grids=3))
+    torch.manual_seed(1)                            # test_init_distributions_match_reference
+    put("init", ref_ekan.KANLinear(64, 64))
+    torch.manual_seed(7)                            # test_live_reference_matches_oracle (its own seed sequence)
+    layer = ref_ekan.KANLinear(24, 18, grid_size=6, spline_order=2)
+    x = torch.randn(500, 24)
+    put("live.kan", layer)
+    out["live.x"] = npy(x)
+    out["live.kan.y"] = npy(layer(x))
+    fk = ref_fastkan.FastKAN([24, 12, 6], num_grids=5)
+    put("live.fastkan", fk)
+    out["live.fastkan.y"] = npy(fk(x))
+    save("g14_reference_surface", **out)
+
+
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g4b", "g567", "g5b", "g8", "g8b", "g9", "g10", "g11", "g12", "g13"]
+    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g4b", "g567", "g5b", "g8", "g8b", "g9", "g10", "g11", "g12", "g13", "g14"]
     fns = {"g1": g1, "g2": g2, "g3": g3, "g4": g4, "g4b": g4b, "g567": g5_g6_g7, "g5b": g5b, "g8": g8, "g8b": g8b, "g13": g13, "g9": g9,
-           "g10": g10, "g11": g11, "g12": g12}
+           "g10": g10, "g11": g11, "g12": g12, "g14": g14}
     for w in which:
         fns[w]()

@@ -1315,3 +1315,46 @@ def test_bench_single_gpu_line_carries_the_contract(workload):
         sec = d["secondary"]
         assert sec["model_step"]["ms_per_step"] > 0 and sec["graph_level_step"]["ms_per_step"] > 0 and len(sec["graph_level_step"]["repeats_ms_per_step"]) == 3
         assert set(sec["other_layers"]) == {"config3", "fastkan"} and d["fp32_mode_ms_per_step"] > d["ms_per_step"]
+
+
+def test_bench_dump_outputs_are_the_last_timed_steps_results(tmp_path):
+    """`bench.py --dump-outputs DIR`: the headline layer's y, x_grad and parameter gradients of the last timed step, against the
+    oracle on the inputs bench.py seeds (graph seed 0, x seed 0, gy seed 1, parameters under torch.manual_seed(0)); the model
+    workload dumps its loss, the state after the Adam step and every gradient."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    import bench
+    n, e, f = 20000, 200000, 64
+    quick = ["--nodes", str(n), "--edges", str(e), "--steps", "2", "--warmup", "1", "--no-traffic", "--no-cpu-baseline", "--no-extras", "--no-fp32"]
+    for workload in ("headline", "model"):
+        out = tmp_path / workload
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", workload, *quick, "--dump-outputs", str(out)],
+                           cwd=root, capture_output=True, text=True, timeout=600)
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert r.returncode == 0 and len(lines) == 1, (r.returncode, r.stdout[-1000:], r.stderr[-2000:])
+        assert json.loads(lines[0])["steps"] == 2
+        got = {p.stem: np.load(p) for p in out.glob("*.npy")}
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in got.values())
+        assert sum(a.nbytes for a in got.values()) <= bench.DUMP_BUDGET_BYTES
+        torch.manual_seed(0)
+        if workload == "model":
+            net = kagnn_amd.GKAN_Nodes("gin", 3, f, f, 40, skip=True, grid_size=5, spline_order=3, hidden_layers=2)
+            states = {f"state.{k}" for k, v in net.state_dict().items() if v.is_floating_point()}
+            grads = {f"grad.{k}" for k, _ in net.named_parameters()}
+            convs = {g_ for g_ in grads if g_.startswith("grad.convs.")}
+            assert got["loss"].shape == () and {k for k in got if k.startswith("state.")} == states
+            assert convs and convs <= set(got) and set(got) <= states | grads | {"loss"}
+            continue
+        conv = kagnn_amd.GIKANLayer(f, f, grid_size=5, spline_order=3, hidden_dim=f, nb_layers=2)
+        layers = [{k: v.double() for k, v in layer.state_dict().items()} for layer in conv.nn.layers]
+        x = torch.randn(n, f, generator=torch.Generator().manual_seed(0)) * 0.25
+        gy = torch.randn(n, f, generator=torch.Generator().manual_seed(1))
+        y, gx, g = orc.kan_gin_layer_fwd_bwd(x.double(), bench.powerlaw_graph(n, e, seed=0), layers, 3, gy.double())
+        assert set(got) == {"y", "x_grad"} | {f"grad.nn.layers.{li}.{k}" for li in range(2) for k in KAN_KEYS[:3]}
+        assert_close(T(got["y"]), y, what="bench dump y")
+        assert_close(T(got["x_grad"]), gx, what="bench dump x_grad")
+        for li in range(2):
+            for k in KAN_KEYS[:3]:
+                assert_close(T(got[f"grad.nn.layers.{li}.{k}"]), g[li][k], what=f"bench dump L{li}.{k}")

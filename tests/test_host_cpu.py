@@ -117,32 +117,39 @@ def test_constructor_signatures_match_reference():
                                         "spline_weight_init_scale"]
 
 
-def test_reference_state_dict_loads(reference_modules):
-    """a state_dict produced by the reference's own KAN loads into ours unchanged (and back)."""
-    ref_ekan, ref_fastkan = reference_modules
-    torch.manual_seed(0)
-    ref = ref_ekan.KAN([6, 5, 4], grid_size=4, spline_order=2)
+def _reference_state(z, prefix):
+    return {k: torch.from_numpy(z[f"{prefix}.{k}"]) for k in z[f"{prefix}.keys"]}
+
+
+def test_reference_state_dict_loads(golden):
+    """a state_dict produced by the reference's own KAN / FastKAN (tests/golden/g14_reference_surface.npz) loads into ours
+    unchanged, and ours gives back the same keys, shapes and values (so the reference loads it in turn)."""
+    z = golden("g14_reference_surface")
+    ref = _reference_state(z, "kan")
     ours = kagnn_amd.KAN([6, 5, 4], grid_size=4, spline_order=2)
-    ours.load_state_dict(ref.state_dict())
-    ref.load_state_dict(ours.state_dict())
-    rf = ref_fastkan.FastKAN([6, 5, 4], num_grids=3)
+    ours.load_state_dict(ref)
+    back = ours.state_dict()
+    assert list(back) == list(ref)
+    for k, v in ref.items():
+        assert torch.equal(back[k], v), k
+    rf = _reference_state(z, "fastkan")
     of = kagnn_amd.FastKAN([6, 5, 4], num_grids=3)
-    of.load_state_dict(rf.state_dict())
-    assert [n for n, _ in of.named_parameters()] == [n for n, _ in rf.named_parameters()]
+    of.load_state_dict(rf)
+    assert [n for n, _ in of.named_parameters()] == list(z["fastkan.param_names"])
 
 
-def test_init_distributions_match_reference(reference_modules):
-    """same init *distributions* (not RNG streams): compare moments of many draws."""
-    ref_ekan, _ = reference_modules
-    torch.manual_seed(1)
-    a = ref_ekan.KANLinear(64, 64)
+def test_init_distributions_match_reference(golden):
+    """same init *distributions* (not RNG streams): compare moments of many draws (the reference's KANLinear(64, 64) drawn
+    under seed 1, stored in g14_reference_surface)."""
+    z = golden("g14_reference_surface")
+    a = _reference_state(z, "init")
     torch.manual_seed(2)
     b = kagnn_amd.KANLinear(64, 64)
     for name in ("base_weight", "spline_weight", "spline_scaler"):
-        x, y = getattr(a, name).detach(), getattr(b, name).detach()
+        x, y = a[name], getattr(b, name).detach()
         assert abs(float(x.std()) - float(y.std())) < 0.1 * float(x.std()), name
         assert abs(float(x.mean()) - float(y.mean())) < 0.05 * float(x.std()) + 1e-4, name
-    assert torch.equal(a.grid, b.grid)
+    assert torch.equal(a["grid"], b.grid)
 
 
 def test_cpu_tensors_are_refused_not_emulated():
@@ -383,3 +390,27 @@ def test_kagin_model_struct_mirror_matches_the_header():
     outs = [ctypes.c_size_t(0) for _ in range(4)]
     assert lib.kagnn_kagin_model_sizes(ctypes.byref(m), *[ctypes.byref(o) for o in outs]) != 0
     assert b"kagnn_kagin_model" in lib.kagnn_last_error()
+
+
+def test_bench_dump_outputs_samples_the_same_rows_within_the_budget(tmp_path):
+    """bench.py --dump-outputs over the budget: every per-node array keeps the same seeded rows (the same ones on every run),
+    arrays without a row per node are written whole, everything as float32 within DUMP_BUDGET_BYTES."""
+    import numpy as np
+    import bench
+    n, f = 300_000, 64
+    g = torch.Generator().manual_seed(5)
+    arrays = {"y": torch.randn(n, f, generator=g), "x_grad": torch.randn(n, f, generator=g).bfloat16(),
+              "grad.w": torch.randn(64, 64, 8, generator=g), "loss": torch.tensor(1.5)}
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), arrays, n)
+    got = {p.stem: np.load(p) for p in (tmp_path / "a").glob("*.npy")}
+    assert set(got) == set(arrays) and all(a.dtype == np.float32 for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= bench.DUMP_BUDGET_BYTES
+    keep = got["y"].shape[0]
+    assert 0 < keep < n and got["x_grad"].shape == (keep, f)
+    rows = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:keep].sort().values
+    assert np.array_equal(got["y"], arrays["y"][rows].numpy())
+    assert np.array_equal(got["x_grad"], arrays["x_grad"][rows].float().numpy())
+    assert np.array_equal(got["grad.w"], arrays["grad.w"].numpy()) and got["loss"] == np.float32(1.5)
+    for name, a in got.items():
+        assert np.array_equal(a, np.load(tmp_path / "b" / f"{name}.npy")), name
