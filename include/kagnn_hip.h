@@ -49,7 +49,7 @@ extern "C" {
 #define KAGNN_DTYPE_F32 0
 #define KAGNN_DTYPE_BF16 1
 
-int kagnn_version(void);          /* 260 = this header (round 6: + the feature-sharded FastKAN entry points kagnn_fastkan_row_moments .. _shard_bwd_finish, + kagnn_kagin_model_*; 250 = 240 + KAGNN_PREC_HALF; 240 = 230 + kagnn_gin_kan_layer_bwd_bn_sums; 230 = 220 + the *_affine entry points of a folded BatchNorm1d; 220 = 210 + the stage timer) */
+int kagnn_version(void);          /* 261 = 260 + kagnn_fastkan_fwd_stats_in_kernel; 260 = round 6: + the feature-sharded FastKAN entry points kagnn_fastkan_row_moments .. _shard_bwd_finish, + kagnn_kagin_model_*; 250 = 240 + KAGNN_PREC_HALF; 240 = 230 + kagnn_gin_kan_layer_bwd_bn_sums; 230 = 220 + the *_affine entry points of a folded BatchNorm1d; 220 = 210 + the stage timer) */
 const char* kagnn_last_error(void);
 
 /* Stage timer -- a measurement aid, off by default (no reference counterpart: the reference times whole epochs with
@@ -525,6 +525,11 @@ int kagnn_fastkan_fwd(const float* x, int64_t ldx, int64_t num_rows, int32_t in_
                       const float* base_bias, float* y, int64_t ldy,
                       float* row_stats /* [N,2] = mean, rstd; required when ln_weight != NULL */,
                       int32_t precision, void* workspace, size_t workspace_bytes, void* stream);
+/* 1 when kagnn_fastkan_fwd with a layernorm computes the row statistics inside its forward kernel, 0 when it runs a separate
+ * statistics pass over x first (split precision: layers of more than one input chunk or more than 8 centres, or
+ * KAGNN_FASTKAN_STATS_IN_FWD=0; 0 also for arguments kagnn_fastkan_fwd refuses).                                          */
+int kagnn_fastkan_fwd_stats_in_kernel(int64_t num_rows, int32_t in_features, int32_t out_features, int32_t num_grids,
+                                      int32_t precision);
 int kagnn_fastkan_bwd_workspace_bytes(int64_t num_rows, int32_t in_features,
                                       int32_t out_features, int32_t num_grids,
                                       int32_t precision, size_t* bytes_host);

@@ -123,6 +123,7 @@ _SIGNATURES = {
     "kagnn_fastkan_fwd_workspace_bytes": (c_int32, [c_int64, c_int32, c_int32, c_int32, c_int32, POINTER(c_size_t)]),
     "kagnn_fastkan_fwd": (c_int32, [_P, c_int64, c_int64, c_int32, c_int32, c_int32, _P, c_float, _P, _P,
                                     c_float, _P, _P, _P, _P, c_int64, _P, c_int32, _P, c_size_t, _P]),
+    "kagnn_fastkan_fwd_stats_in_kernel": (c_int32, [c_int64, c_int32, c_int32, c_int32, c_int32]),
     "kagnn_fastkan_bwd_workspace_bytes": (c_int32, [c_int64, c_int32, c_int32, c_int32, c_int32, POINTER(c_size_t)]),
     "kagnn_fastkan_bwd": (c_int32, [_P, c_int64, _P, c_int64, c_int64, c_int32, c_int32, c_int32, _P,
                                     c_float, _P, _P, c_float, _P, _P, _P, _P, c_int64, _P, _P, _P, _P,

@@ -82,6 +82,7 @@ int kan_split_dx_stats(const float*, long, const float*, long, long, const float
 bool kan_split_dw_ok(int in, int out, int G, int K);
 
 int fastkan_fwd(const float*, long, long, int, int, int, const float*, float, const float*, const float*, float, const float*, const float*, const float*, float*, long, float*, void*, size_t, int, hipStream_t, bool stats_given = false);
+bool fastkan_fwd_stats_in_kernel(long, int, int, int, int);
 int fastkan_row_moments(const float*, long, long, int, float*, hipStream_t);
 int fastkan_merge_moments(const float*, int, long, int, float, float*, hipStream_t);
 size_t fastkan_fwd_ws_bytes(long N, int in, int out, int ng, int mode);
@@ -202,7 +203,7 @@ static bool use_split_dw(int in, int out, int G, int K, int mode) { return mode 
 #pragma GCC visibility push(default)
 extern "C" {
 
-int kagnn_version(void) { return 260; }
+int kagnn_version(void) { return 261; }
 const char* kagnn_last_error(void) { return g_err; }
 
 int kagnn_stage_timer_enable(const char* only) {
@@ -743,6 +744,12 @@ int kagnn_fastkan_fwd(const float* x, int64_t ldx, int64_t N, int32_t in, int32_
         return fail(KAGNN_ERR_UNSUPPORTED, "%s: leading dimension > 7680 floats; call with KAGNN_PREC_FP32", __func__);
     return fastkan_fwd(x, ldx, N, in, out, ng, centers, denominator, ln_w, ln_b, ln_eps, spline_w, base_w,
                        base_b, y, ldy, row_stats, ws, ws_bytes, mode, as_stream(stream));
+}
+
+int kagnn_fastkan_fwd_stats_in_kernel(int64_t N, int32_t in, int32_t out, int32_t ng, int32_t mode) {
+    ModeScope mode_scope_(mode);
+    if (check_fk(__func__, in, out, ng, mode)) return 0;
+    return fastkan_fwd_stats_in_kernel(N, in, out, ng, mode) ? 1 : 0;
 }
 
 int kagnn_fastkan_bwd_workspace_bytes(int64_t N, int32_t in, int32_t out, int32_t ng, int32_t mode, size_t* bytes) {

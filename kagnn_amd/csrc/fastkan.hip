@@ -727,6 +727,14 @@ __global__ void fastkan_dw_unpack_kernel(const float* __restrict__ gcat, int in,
 // ------------------------------------------------------------------ host launchers
 static size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 
+// the forward takes the LayerNorm row statistics from the rows it loads (no statistics pass before it): the exact-fp32 kernel
+// always; the split kernels for one-chunk layers (<= 8 centres, in <= 64 with <= 64 outputs / in <= 32 with <= 128, one output block)
+bool fastkan_fwd_stats_in_kernel(long N, int in, int out, int ng, int mode) {
+    if (!fk_split(in, out, ng, mode)) return true;
+    const int cf = cdiv(min(out, 128), 32) <= 2 ? 64 : 32;
+    return ng <= 8 && in <= cf && out <= 128 && N > 0 && fk_stats_in_fwd();
+}
+
 size_t fastkan_fwd_ws_bytes(long N, int in, int out, int ng, int mode) {
     if (fk_split(in, out, ng, mode)) return al256(kan_split_pack_fwd_bytes(in, out, ng)) + al256(kan_split_fwd_ws_bytes(N, in, out, ng));
     return al256(kan_f32_pack_fwd_bytes(in, out, ng)) + al256(kan_f32_pack_dx_bytes(in, out, ng));
@@ -742,8 +750,7 @@ int fastkan_fwd(const float* x, long ldx, long N, int in, int out, int ng, const
     if (fk_split(in, out, ng, mode)) {
         // one-chunk layers (<= 8 centres, in <= 64 with <= 64 outputs / in <= 32 with <= 128, one output block): the forward
         // kernel takes the row statistics from the rows it loads and stores them; anything else runs the statistics pass first
-        const int cf = cdiv(min(out, 128), 32) <= 2 ? 64 : 32;
-        const bool own_stats = lnw && !stats_given && ng <= 8 && in <= cf && out <= 128 && N > 0 && fk_stats_in_fwd();
+        const bool own_stats = lnw && !stats_given && fastkan_fwd_stats_in_kernel(N, in, out, ng, mode);
         if (lnw && !own_stats && !stats_given) { int rc = launch_stats(x, ldx, N, in, eps, stats, st); if (rc) return rc; }
         { int rc = kan_split_pack_fwd_noscale(bw, sw, nullptr, in, out, ng, ws, st); if (rc) return rc; }
         char* part = static_cast<char*>(ws) + al256(kan_split_pack_fwd_bytes(in, out, ng));

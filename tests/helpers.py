@@ -224,7 +224,13 @@ class bf16_gather_oracle:
     """context manager: inside it ``oracle.gin_conv`` rounds the two gathered matrices of every KAN-GIN convolution to bf16
     exactly where the build-defined KAGNN_ACT=bf16 mode does -- everything else stays fp64.  The HIP
     path must agree with THIS oracle at (nearly) the fp32 tolerance: that is the parity statement for the mode; its distance
-    from the unrounded oracle is a property of the mode, reported separately."""
+    from the unrounded oracle is a property of the mode, reported separately.  ``gathered_grad``: the backward's rounding on
+    its own, for checkers that restate the transposed aggregation themselves (the forward's rounded rows are then the
+    device's own aggregate)."""
+
+    @staticmethod
+    def gathered_grad(g):
+        return g.to(torch.bfloat16).to(g.dtype)
 
     def __enter__(self):
         self._orig = orc.gin_conv
@@ -304,3 +310,29 @@ class half_mode_oracle:
     def __exit__(self, *exc):
         orc.kan_linear_forward = self._orig
         return False
+
+
+# Parity of KAGNN_PREC_HALF (against the oracle fed the SAME once-rounded operands) is stated in two norms.  L2: the HIP path differs
+# from that oracle only where the device's fp32 evaluation of an operand (bases by the closed cubic form, SiLU through v_exp / v_rcp:
+# ~1e-7 from the oracle's fp64) lands on the other side of an fp16 rounding boundary -- ~2e-4 of the operands, each moving one term by
+# 2^-11 of itself: SPARSE errors, <= HALF_L2_TOL of the tensor's norm, at least 5x below the mode's own (dense) distance from the
+# unrounded oracle.  Max norm: one flipped term is up to ~1e-4 of max|y| at these widths (observed 0.5..1.0e-4), so the bound is
+# HALF_FLIP_TOL = 3e-4 -- a dropped operand, a wrong scale exponent or a missing product is >= 2^-11 dense, i.e. fails the L2 bound.
+HALF_L2_TOL, HALF_FLIP_TOL = 5e-5, 3e-4
+
+
+def l2_rel(a, b):
+    return float((a.detach().double().cpu() - b.double()).norm() / b.double().norm())
+
+
+def half_parity(got, rounded, plain, what, l2_tol=HALF_L2_TOL, flip_tol=HALF_FLIP_TOL):
+    """the two-norm parity statement of KAGNN_PREC_HALF above; returns (L2 vs rounding oracle, L2 vs unrounded oracle).
+    ``plain=None``: no unrounded oracle at hand -- the 5x separation is not checked."""
+    assert_close(got, rounded, flip_tol, what=what + " vs rounding oracle", elementwise=False)
+    lr = l2_rel(got, rounded)
+    check(lr <= l2_tol, what + ": L2 distance from the rounding oracle", lr)
+    if plain is None:
+        return lr, None
+    lp = l2_rel(got, plain)
+    check(5.0 * lr <= lp, what + ": the rounding oracle must explain the result at least 5x better than the unrounded one", (lr, lp))
+    return lr, lp

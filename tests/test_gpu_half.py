@@ -12,18 +12,12 @@ import torch
 import kagnn_amd
 from kagnn_amd import ops
 from oracle import kan_oracle as orc
-from helpers import (CONTRACT, assert_close, check, half_mode_oracle, oracle_kan_linear_fwd_bwd, oracle_node_model_fwd_bwd,
-                     prenorm_bias_noise)
+from helpers import (CONTRACT, HALF_FLIP_TOL as FLIP_TOL, HALF_L2_TOL as L2_TOL, assert_close, check, half_mode_oracle,
+                     half_parity as _parity, oracle_kan_linear_fwd_bwd, oracle_node_model_fwd_bwd, prenorm_bias_noise)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-# Parity of the mode (against the oracle fed the SAME once-rounded operands) is stated in two norms.  L2: the HIP path differs from that
-# oracle only where the device's fp32 evaluation of an operand (bases by the closed cubic form, SiLU through v_exp / v_rcp: ~1e-7
-# from the oracle's fp64) lands on the other side of an fp16 rounding boundary -- ~2e-4 of the operands, each moving one term by
-# 2^-11 of itself: SPARSE errors, <= L2_TOL of the tensor's norm, at least 5x below the mode's own (dense) distance from the
-# unrounded oracle.  Max norm: one flipped term is up to ~1e-4 of max|y| at these widths (observed 0.5..1.0e-4), so the bound is
-# FLIP_TOL = 3e-4 -- a dropped operand, a wrong scale exponent or a missing product is >= 2^-11 dense, i.e. fails the L2 bound.
-L2_TOL, FLIP_TOL = 5e-5, 3e-4
+# L2_TOL / FLIP_TOL: the mode's two-norm parity statement, tests/helpers.py (half_parity)
 MODE_FLOOR, MODE_CEIL = 3e-5, 3e-3      # a layer's distance from the UNROUNDED oracle, relative to the tensor's maximum: above the
                                         # three-product kernels' 1e-6 by construction (proves the single-product instantiation ran),
                                         # below ~6 x 2^-11 (operand roundings add up over two operands and the two branches)
@@ -32,19 +26,6 @@ REPORT = {}
 
 def _rel(a, b):
     return float((a.detach().double().cpu() - b.double()).abs().max() / b.double().abs().max())
-
-
-def _l2(a, b):
-    return float((a.detach().double().cpu() - b.double()).norm() / b.double().norm())
-
-
-def _parity(got, rounded, plain, what, l2_tol=L2_TOL, flip_tol=FLIP_TOL):
-    """the two-norm parity statement above; returns (L2 vs rounding oracle, L2 vs unrounded oracle)"""
-    assert_close(got, rounded, flip_tol, what=what + " vs rounding oracle", elementwise=False)
-    lr, lp = _l2(got, rounded), _l2(got, plain)
-    check(lr <= l2_tol, what + ": L2 distance from the rounding oracle", lr)
-    check(5.0 * lr <= lp, what + ": the rounding oracle must explain the result at least 5x better than the unrounded one", (lr, lp))
-    return lr, lp
 
 
 def _set_precision(module, mode):
