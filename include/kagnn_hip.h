@@ -49,7 +49,7 @@ extern "C" {
 #define KAGNN_DTYPE_F32 0
 #define KAGNN_DTYPE_BF16 1
 
-int kagnn_version(void);          /* 261 = 260 + kagnn_fastkan_fwd_stats_in_kernel; 260 = round 6: + the feature-sharded FastKAN entry points kagnn_fastkan_row_moments .. _shard_bwd_finish, + kagnn_kagin_model_*; 250 = 240 + KAGNN_PREC_HALF; 240 = 230 + kagnn_gin_kan_layer_bwd_bn_sums; 230 = 220 + the *_affine entry points of a folded BatchNorm1d; 220 = 210 + the stage timer) */
+int kagnn_version(void);          /* 262 = 261 - the fields edge_src, edge_dst, csr_flags of kagnn_kagin_model_t; 261 = 260 + kagnn_fastkan_fwd_stats_in_kernel; 260 = round 6: + the feature-sharded FastKAN entry points kagnn_fastkan_row_moments .. _shard_bwd_finish, + kagnn_kagin_model_*; 250 = 240 + KAGNN_PREC_HALF; 240 = 230 + kagnn_gin_kan_layer_bwd_bn_sums; 230 = 220 + the *_affine entry points of a folded BatchNorm1d; 220 = 210 + the stage timer) */
 const char* kagnn_last_error(void);
 
 /* Stage timer -- a measurement aid, off by default (no reference counterpart: the reference times whole epochs with
@@ -792,10 +792,6 @@ typedef struct kagnn_kagin_model {
     const int32_t* rowptr; const int32_t* col; const int32_t* perm;        /* CSR by destination (kagnn_csr_build_small) */
     const int32_t* rowptr_t; const int32_t* col_t; const int32_t* perm_t;  /* ... and its transpose */
     const int32_t* seg_ptr;                                                /* [num_graphs + 1] node offsets */
-    /* edge_src != NULL: the library builds the CSR + transpose of THIS batch itself (kagnn_csr_build_small: num_edges, num_nodes
-     * <= 65 536) into `saved`, on a stream of its own beside the encoders and the weight packs, and ignores the six arrays above;
-     * csr_flags (2 ints, device) receives the out-of-range-id flags of that build for the caller's validation                    */
-    const int64_t* edge_src; const int64_t* edge_dst; int32_t* csr_flags;
     const float* knots;
     const float* base_weight[KAGNN_MODEL_MAX_LAYERS]; const float* spline_weight[KAGNN_MODEL_MAX_LAYERS];
     const float* spline_scaler[KAGNN_MODEL_MAX_LAYERS];

@@ -6,7 +6,6 @@ namespace kagnn {
 thread_local char g_err[512] = "";
 thread_local bool g_half_products = false;      // KAGNN_PREC_HALF for the duration of an entry-point call (split_common.h)
 thread_local DwDefer* g_dw_defer = nullptr;       // deferred weight-gradient slab reductions of a stack call (common.h)
-thread_local MomDefer* g_mom_defer = nullptr;     // column moments whose finish is folded into the norm's apply kernel (common.h)
 thread_local bool g_stack_prepacked = false;      // kagnn_kagin_model_fwd has packed the stack's layers together with the read-out's (one launch)
 
 size_t aggregate_ws_bytes(long num_hub_seg, int F);
@@ -107,7 +106,6 @@ size_t bn_ws_bytes(long N, int F);
 int bn_fwd(const float*, long, long, int, const float*, const float*, float*, float*, float, float, int, const float*, const float*, float, unsigned long long, float*, long, float*, float*, void*, size_t, hipStream_t);
 int bn_bwd(const float*, long, const float*, long, long, int, const float*, const float*, const float*, int, float, unsigned long long, float*, long, float*, float*, void*, size_t, hipStream_t);
 int bn_bwd_stats(const float*, long, const float*, long, long, int, const float*, const float*, const float*, float*, float*, float*, int, void*, size_t, hipStream_t);
-int bn_fwd_partial_moments(const float*, long, long, int, const float*, const float*, float*, float*, float, float, const float*, int, float*, long, float*, float*, hipStream_t);
 int bn_stats_affine(const float*, const float*, long, int, const float*, const float*, float*, float*, float, float, float*, float*, float*, hipStream_t);
 bool kan_split_dx_bn_ok(long, int, int, int, int, const BnBack&, const void*);
 int kan_split_dx_bn(const float*, long, const float*, long, long, const float*, int, int, int, int, const void*, float*, long, const BnBack&, hipStream_t);
@@ -203,7 +201,7 @@ static bool use_split_dw(int in, int out, int G, int K, int mode) { return mode 
 #pragma GCC visibility push(default)
 extern "C" {
 
-int kagnn_version(void) { return 261; }
+int kagnn_version(void) { return 262; }
 const char* kagnn_last_error(void) { return g_err; }
 
 int kagnn_stage_timer_enable(const char* only) {
@@ -1521,11 +1519,6 @@ int kagnn_gine_kan_stack_workspace_bytes(int64_t N, int32_t nconv, int32_t L, co
     return KAGNN_OK;
 }
 
-static bool mom_defer_enabled() {             // OPT-IN (KAGNN_MOM_DEFER=1): measured slower on the device, see below; read per call for the test
-    const char* e = getenv("KAGNN_MOM_DEFER");
-    return e != nullptr && atoi(e) != 0;
-}
-
 int kagnn_gine_kan_stack_fwd(const float* x, int64_t ldx, const float* edge_attr, int64_t lde, int64_t N, const int32_t* rowptr,
                              const int32_t* col, const int32_t* perm, const float* self_scale, int32_t nconv,
                              int32_t L, const int32_t* widths, const float* const* bw, const float* const* sw,
@@ -1562,32 +1555,13 @@ int kagnn_gine_kan_stack_fwd(const float* x, int64_t ldx, const float* edge_attr
     for (int i = 0; i < nconv; ++i) {
         GineStage gs{in, ldin, edge_attr, lde, perm, nullptr, 0};
         gs.prepacked = batch ? 1 : 0;
-        // (round 6, opt-in: KAGNN_MOM_DEFER=1) the last forward kernel leaves its <= 32 per-workgroup moment rows where they are and the
-        // norm's apply kernel folds them: no moments_finish launch, same merge order, same bits.  One launch fewer per convolution, but
-        // every one of the apply kernel's ~370 workgroups repeats the 24-row merge chain: 15.7 us against 5.0 + 5.1 for the two
-        // launches (profiles/r06_experiments.md 3) -- and a launch costs the host ~1 us.  Off by default.
-        kagnn::MomDefer md{nullptr, 0};
-        {
-            struct MomScope {
-                kagnn::MomDefer* prev;
-                explicit MomScope(kagnn::MomDefer* d) : prev(kagnn::g_mom_defer) { kagnn::g_mom_defer = d; }
-                ~MomScope() { kagnn::g_mom_defer = prev; }
-            } mom_scope_(mom_defer_enabled() ? &md : nullptr);
-            rc = layer_fwd_impl(in, KAGNN_DTYPE_F32, ldin, N, rowptr, col, nullptr, 0, 0, self_scale[i], nullptr, nullptr, L, widths, bw + i * L,
-                                sw + i * L, sc ? sc + i * L : nullptr, knots, G, K, mode, acts + i * (L + 1), pack_fwd + i * L, pack_dx + i * L,
-                                mom, mom + H, ws, al256z(lf), stream, __func__, &gs);
-        }
+        rc = layer_fwd_impl(in, KAGNN_DTYPE_F32, ldin, N, rowptr, col, nullptr, 0, 0, self_scale[i], nullptr, nullptr, L, widths, bw + i * L,
+                            sw + i * L, sc ? sc + i * L : nullptr, knots, G, K, mode, acts + i * (L + 1), pack_fwd + i * L, pack_dx + i * L,
+                            mom, mom + H, ws, al256z(lf), stream, __func__, &gs);
         if (rc) return rc;
-        if (md.P > 0) {
-            KAGNN_STAGE_AS("kagnn_batchnorm_fwd", stream);
-            rc = bn_fwd_partial_moments(acts[i * (L + 1) + L], H, N, H, bn_weight[i], bn_bias[i], running_mean ? running_mean[i] : nullptr,
-                                        running_var ? running_var[i] : nullptr, momentum[i], eps[i], md.partial, md.P, h[i], H,
-                                        save_mean[i], save_rstd[i], as_stream(stream));
-        } else {
-            rc = kagnn_batchnorm_fwd(acts[i * (L + 1) + L], H, N, H, bn_weight[i], bn_bias[i], running_mean ? running_mean[i] : nullptr,
-                                     running_var ? running_var[i] : nullptr, momentum[i], eps[i], 1, mom, mom + H, 0.0f, 0ULL, h[i], H,
-                                     save_mean[i], save_rstd[i], ws_bn, bnb, stream);
-        }
+        rc = kagnn_batchnorm_fwd(acts[i * (L + 1) + L], H, N, H, bn_weight[i], bn_bias[i], running_mean ? running_mean[i] : nullptr,
+                                 running_var ? running_var[i] : nullptr, momentum[i], eps[i], 1, mom, mom + H, 0.0f, 0ULL, h[i], H,
+                                 save_mean[i], save_rstd[i], ws_bn, bnb, stream);
         if (rc) return rc;
         in = h[i]; ldin = H;
     }
@@ -1658,8 +1632,6 @@ struct KmLayout {
     // `saved`: byte offsets
     size_t x0, ea, acts, h, stats, packs, pooled, ro_act[KAGNN_MODEL_MAX_READOUT], ro_pf[KAGNN_MODEL_MAX_READOUT], ro_pd[KAGNN_MODEL_MAX_READOUT], saved_total;
     size_t fb, db;                       // one stack layer's forward / input-gradient pack, 256-aligned
-    size_t csr[6];                       // rowptr, col, perm, rowptr_t, col_t, perm_t (int32) when the library builds the CSR itself
-    size_t fwd_csr_ws, csr_ws_bytes;     // ... and that build's scratch inside the forward workspace
     // workspaces: byte offsets of the fixed parts, then the shared scratch of the sub-calls
     size_t fwd_scratch, fwd_total;
     size_t bwd_gy[2], bwd_gh, bwd_gx0, bwd_gea, bwd_scratch, bwd_total;
@@ -1669,22 +1641,6 @@ struct KmLayout {
     size_t g_ro_bw[KAGNN_MODEL_MAX_READOUT], g_ro_sw[KAGNN_MODEL_MAX_READOUT], g_ro_sc[KAGNN_MODEL_MAX_READOUT];   // float offsets into grads
     bool ro_batch;                       // the read-out's packs in one launch (kagnn_kan_pack_batch)
 };
-
-// a stream + two events of the library's own, per host thread and device (created on first use, never destroyed: process lifetime)
-struct SideStream { hipStream_t st; hipEvent_t fork, join; };
-SideStream* side_stream() {
-    thread_local SideStream pool[64];
-    thread_local bool made[64] = {};
-    int d = 0;
-    if (hipGetDevice(&d) != hipSuccess || d < 0 || d > 63) return nullptr;
-    if (!made[d]) {
-        if (hipStreamCreateWithFlags(&pool[d].st, hipStreamNonBlocking) != hipSuccess) return nullptr;
-        if (hipEventCreateWithFlags(&pool[d].fork, hipEventDisableTiming) != hipSuccess) return nullptr;
-        if (hipEventCreateWithFlags(&pool[d].join, hipEventDisableTiming) != hipSuccess) return nullptr;
-        made[d] = true;
-    }
-    return &pool[d];
-}
 
 int km_check(const kagnn_kagin_model_t* m, const char* fn) {
     if (!m) return fail(KAGNN_ERR_ARG, "%s: null model", fn);
@@ -1728,14 +1684,6 @@ int km_layout(const kagnn_kagin_model_t* m, KmLayout& L, const char* fn) {
         batch = batch && rm == (int)m->readout_modes[0] && (rm == KAGNN_PREC_SPLIT || rm == KAGNN_PREC_HALF) && fout <= 64;
     }
     L.ro_batch = batch;
-    for (int k = 0; k < 6; ++k) L.csr[k] = 0;
-    L.csr_ws_bytes = 0;
-    if (m->edge_src) {
-        if (!m->edge_dst || !m->csr_flags || !kagnn_csr_small_ok((int64_t)E, (int64_t)N))
-            return fail(KAGNN_ERR_ARG, "%s: edge_src needs edge_dst, csr_flags and a graph kagnn_csr_build_small covers", fn);
-        for (int k = 0; k < 6; ++k) L.csr[k] = take(((k % 3 == 0) ? N + 1 : (E ? E : 1)) * sizeof(int32_t));
-        rc = kagnn_csr_small_workspace_bytes((int64_t)E, &L.csr_ws_bytes); if (rc) return rc;
-    }
     L.saved_total = o + 256;
     // forward workspace: the stack's, the read-out forwards' split-K scratch
     int32_t widths[9];
@@ -1761,7 +1709,7 @@ int km_layout(const kagnn_kagin_model_t* m, KmLayout& L, const char* fn) {
         rc = kagnn_embedding_bwd_workspace_bytes((int64_t)E, (int)m->bond_rows[t], (int)H, &a); if (rc) return rc;
         scratch_b = scratch_b > a ? scratch_b : a;
     }
-    L.fwd_scratch = 0; L.fwd_csr_ws = al256z(scratch_f); L.fwd_total = al256z(scratch_f) + al256z(L.csr_ws_bytes) + 256;
+    L.fwd_scratch = 0; L.fwd_total = al256z(scratch_f) + 256;
     size_t wmax = 1;
     for (int i = 0; i <= nr; ++i) wmax = wmax > (size_t)m->readout_widths[i] ? wmax : (size_t)m->readout_widths[i];
     o = 0;
@@ -1805,8 +1753,8 @@ int kagnn_kagin_model_fwd(const kagnn_kagin_model_t* m, void* stream) {
     KmLayout L;
     int rc = km_layout(m, L, __func__);
     if (rc) return rc;
-    KAGNN_CHECK_ARG(m->saved && m->workspace && m->out && m->x_index && (m->rowptr || m->edge_src) && m->seg_ptr && m->knots, "null array");
-    KAGNN_CHECK_ARG(m->num_edges == 0 || (m->e_index && (m->edge_src || (m->col && m->perm))), "null edge array");       // (a batch of single atoms has none)
+    KAGNN_CHECK_ARG(m->saved && m->workspace && m->out && m->x_index && m->rowptr && m->seg_ptr && m->knots, "null array");
+    KAGNN_CHECK_ARG(m->num_edges == 0 || (m->e_index && m->col && m->perm), "null edge array");       // (a batch of single atoms has none)
     KAGNN_CHECK_ARG((size_t)m->saved_bytes >= L.saved_total && (size_t)m->workspace_bytes >= L.fwd_total,
                     "saved / workspace too small (kagnn_kagin_model_sizes)");
     const int64_t N = m->num_nodes, E = m->num_edges, B = m->num_graphs;
@@ -1815,23 +1763,6 @@ int kagnn_kagin_model_fwd(const kagnn_kagin_model_t* m, void* stream) {
     unsigned char* ws = static_cast<unsigned char*>(m->workspace);
     float* x0 = reinterpret_cast<float*>(sv + L.x0);
     float* ea = reinterpret_cast<float*>(sv + L.ea);
-    // the batch's CSR + transpose, built by the library on a stream of its own: nothing before the first GINE aggregation depends on
-    // it, so the one-workgroup-per-direction sort (55 us for a 256-molecule batch) runs beside the encoders and the weight packs
-    const int32_t* rowptr = m->rowptr; const int32_t* col = m->col; const int32_t* perm = m->perm;
-    SideStream* side = nullptr;
-    if (m->edge_src) {
-        int32_t* a[6];
-        for (int k = 0; k < 6; ++k) a[k] = reinterpret_cast<int32_t*>(sv + L.csr[k]);
-        rowptr = a[0]; col = a[1]; perm = a[2];
-        side = side_stream();
-        if (side == nullptr) return fail(KAGNN_ERR_HIP, "%s: no side stream", __func__);
-        KAGNN_HIP(hipEventRecord(side->fork, as_stream(stream)));
-        KAGNN_HIP(hipStreamWaitEvent(side->st, side->fork, 0));
-        rc = kagnn_csr_build_small(m->edge_src, m->edge_dst, E, N, a[0], a[1], a[2], a[3], a[4], a[5], m->csr_flags, ws + L.fwd_csr_ws,
-                                   L.csr_ws_bytes, side->st);
-        if (rc) return rc;
-        KAGNN_HIP(hipEventRecord(side->join, side->st));
-    }
     // encoders: sum over the feature columns of one table each (models.py:244-281)
     for (int t = 0; t < (int)m->num_atom_tables; ++t) {
         rc = kagnn_embedding_fwd(m->x_index + t, m->x_stride, N, m->atom_table[t], (int32_t)m->atom_rows[t], H, x0, H, t > 0, stream);
@@ -1885,10 +1816,9 @@ int kagnn_kagin_model_fwd(const kagnn_kagin_model_t* m, void* stream) {
         explicit PrepackedScope(bool on) : prev(kagnn::g_stack_prepacked) { kagnn::g_stack_prepacked = on; }
         ~PrepackedScope() { kagnn::g_stack_prepacked = prev; }
     };
-    if (side) KAGNN_HIP(hipStreamWaitEvent(as_stream(stream), side->join, 0));
     {
     PrepackedScope prepacked_scope_(packed_all);
-    rc = kagnn_gine_kan_stack_fwd(x0, H, ea, H, N, rowptr, col, perm, m->self_scale, nconv, nl, widths, m->base_weight, m->spline_weight,
+    rc = kagnn_gine_kan_stack_fwd(x0, H, ea, H, N, m->rowptr, m->col, m->perm, m->self_scale, nconv, nl, widths, m->base_weight, m->spline_weight,
                                   m->spline_scaler, m->knots, G, K, mode, acts, pf, pd, m->bn_weight, m->bn_bias,
                                   const_cast<float* const*>(m->running_mean), const_cast<float* const*>(m->running_var), m->momentum, m->eps, h, mean, rstd,
                                   ws + L.fwd_scratch, (size_t)m->workspace_bytes - L.fwd_scratch, stream);
@@ -1924,8 +1854,8 @@ int kagnn_kagin_model_bwd(const kagnn_kagin_model_t* m, void* stream) {
     KmLayout L;
     int rc = km_layout(m, L, __func__);
     if (rc) return rc;
-    KAGNN_CHECK_ARG(m->saved && m->workspace && m->g_out && m->grads && m->x_index && (m->rowptr_t || m->edge_src) && m->seg_ptr && m->knots, "null array");
-    KAGNN_CHECK_ARG(m->num_edges == 0 || (m->e_index && (m->edge_src || (m->col_t && m->perm_t))), "null edge array");
+    KAGNN_CHECK_ARG(m->saved && m->workspace && m->g_out && m->grads && m->x_index && m->rowptr_t && m->seg_ptr && m->knots, "null array");
+    KAGNN_CHECK_ARG(m->num_edges == 0 || (m->e_index && m->col_t && m->perm_t), "null edge array");
     KAGNN_CHECK_ARG((size_t)m->saved_bytes >= L.saved_total && (size_t)m->workspace_bytes >= L.bwd_total,
                     "saved / workspace too small (kagnn_kagin_model_sizes)");
     const int64_t N = m->num_nodes, E = m->num_edges, B = m->num_graphs;
@@ -1979,13 +1909,7 @@ int kagnn_kagin_model_bwd(const kagnn_kagin_model_t* m, void* stream) {
     const float* ea = reinterpret_cast<const float*>(sv + L.ea);
     float* gx0 = reinterpret_cast<float*>(ws + L.bwd_gx0);
     float* gea = reinterpret_cast<float*>(ws + L.bwd_gea);
-    const int32_t* rowptr_t = m->rowptr_t; const int32_t* col_t = m->col_t; const int32_t* perm_t = m->perm_t;
-    if (m->edge_src) {                      // (built by the forward into `saved`)
-        rowptr_t = reinterpret_cast<const int32_t*>(static_cast<unsigned char*>(m->saved) + L.csr[3]);
-        col_t = reinterpret_cast<const int32_t*>(static_cast<unsigned char*>(m->saved) + L.csr[4]);
-        perm_t = reinterpret_cast<const int32_t*>(static_cast<unsigned char*>(m->saved) + L.csr[5]);
-    }
-    rc = kagnn_gine_kan_stack_bwd(gh, H, x0, H, ea, H, N, rowptr_t, col_t, perm_t, m->self_scale, nconv, nl, widths, m->spline_weight,
+    rc = kagnn_gine_kan_stack_bwd(gh, H, x0, H, ea, H, N, m->rowptr_t, m->col_t, m->perm_t, m->self_scale, nconv, nl, widths, m->spline_weight,
                                   m->spline_scaler, m->knots, G, K, mode, acts, pd, h, m->bn_weight, mean, rstd, gx0, H, gea, H, g_bn_w, g_bn_b, g_bw, g_sw,
                                   g_sc, ws + L.bwd_scratch, (size_t)m->workspace_bytes - L.bwd_scratch, stream);
     if (rc) return rc;

@@ -278,11 +278,6 @@ def train_graph_batches(model, batches, nb_epochs: int = 1, warmup: int = 0, lr:
     model.train()
     on_gpu = any(p.is_cuda for p in model.parameters())
 
-    import os
-    # (opt-in: on the round-6 boxes the step is HOST-bound, and the prefetch's stream switch + events cost the host more than the
-    # 55 us of device time they hide -- same-box A/B in profiles/r06_experiments.md; a device-bound loop can turn it on)
-    prefetch = on_gpu and os.environ.get("KAGNN_PREFETCH_CSR", "0") == "1"
-
     root = []
 
     def one(like):
@@ -290,23 +285,9 @@ def train_graph_batches(model, batches, nb_epochs: int = 1, warmup: int = 0, lr:
             root[:] = [torch.ones(like.shape, dtype=like.dtype, device=like.device)]
         return root[0]
 
-    def lookahead(it):
-        it = iter(it)
-        try:
-            cur = next(it)
-        except StopIteration:
-            return
-        for nxt in it:
-            yield cur, nxt
-            cur = nxt
-        yield cur, None
-
     def epoch():
         losses, weights = [], []
-        for data, upcoming in lookahead(batches):
-            if prefetch and upcoming is not None and hasattr(upcoming, "edge_index") and torch.is_tensor(getattr(upcoming, "x", None)):
-                # the NEXT batch's CSR is built on a side stream beside this step's kernels (a loader worker's job; ops.prefetch_graph_index)
-                ops_mod.prefetch_graph_index(upcoming.edge_index, upcoming.x.size(0))
+        for data in batches:
             optimizer.zero_grad(set_to_none=True)
             loss = loss_fn(model(data).squeeze(), data.y.squeeze())
             if replicas is None:
@@ -330,6 +311,7 @@ def train_graph_batches(model, batches, nb_epochs: int = 1, warmup: int = 0, lr:
     # worker thread costs more than running it (host issue time of the ZINC-shaped step on the round-6 boxes: 1.41-1.50 ms per
     # step with the engine's threads, 0.85-0.90 ms on the calling thread -- tools/host_profile_cfg4.py, profiles/r06_experiments.md).
     # One device, one stream: nothing runs concurrently in that backward anyway.
+    import os
     mt_was = torch.autograd.is_multithreading_enabled()
     torch.autograd.set_multithreading_enabled(os.environ.get("KAGNN_CFG4_MT", "0") == "1")     # (=1: the engine's worker threads, for A/B)
     try:

@@ -382,57 +382,14 @@ def flush_graph_checks(device=None) -> None:
 
 _graph_cache: "dict[tuple, GraphIndex]" = {}
 _GRAPH_CACHE_MAX = 8
-_prefetched: "dict[tuple, tuple]" = {}          # key of graph_index -> (GraphIndex built on the side stream, its completion event)
-_prefetch_streams: "dict[int, torch.cuda.Stream]" = {}
-
-
-def prefetch_graph_index(edge_index: torch.Tensor, num_nodes: int) -> bool:
-    """Index a LATER mini-batch's graph now, on a side stream, so that the one-workgroup-per-direction CSR build (55 us for a
-    256-molecule batch: 7 % of a step's device time, and nothing in the step depends on it) runs beside the current step's kernels
-    instead of in front of the next step's.  ``graph_index(edge_index, num_nodes, cache=False)`` on the same tensor then adopts the
-    arrays after making the compute stream wait for the build.  What a data loader's worker would do; ``harness.train_graph_batches``
-    calls it for batch k + 1 before it issues step k.  Small graphs only (``kagnn_csr_small_ok``); returns whether it was queued."""
-    if not (edge_index.is_cuda and edge_index.dim() == 2 and edge_index.size(0) == 2 and edge_index.dtype == torch.int64 and _SMALL_CSR):
-        return False
-    if not _lib.load().kagnn_csr_small_ok(int(edge_index.size(1)), int(num_nodes)):
-        return False
-    dev = edge_index.device
-    key = (edge_index.data_ptr(), edge_index._version, tuple(edge_index.shape), int(num_nodes), dev.index)
-    if key in _prefetched:
-        return True
-    while len(_prefetched) >= 4:                 # (never consumed: a loop that ended, an evaluation pass that took another path)
-        _prefetched.pop(next(iter(_prefetched)))
-    side = _prefetch_streams.get(dev.index)
-    if side is None:
-        side = _prefetch_streams[dev.index] = torch.cuda.Stream(device=dev)
-    ready = torch.cuda.Event()
-    ready.record(torch.cuda.current_stream(dev))        # edge_index is complete once everything queued so far has run
-    with torch.cuda.stream(side):
-        side.wait_event(ready)
-        g = GraphIndex(edge_index, num_nodes, defer_validation=True)
-        done = torch.cuda.Event()
-        done.record(side)
-    edge_index.record_stream(side)
-    _prefetched[key] = (g, done)
-    return True
-
-
 def graph_index(edge_index: torch.Tensor, num_nodes: int, cache: bool = True) -> GraphIndex:
     """Cached GraphIndex keyed on the identity and version of ``edge_index`` (SURVEY 8(b) ownership): full-batch node
     models see the same ``edge_index`` every epoch.  ``cache=False`` (the graph-level models' mini-batches, which never
     repeat): build and drop -- a cache that never hits only pins the last 8 batches and both of their CSRs."""
+    if not cache:
+        return GraphIndex(edge_index, num_nodes, defer_validation=True)
     key = (edge_index.data_ptr(), edge_index._version, tuple(edge_index.shape), int(num_nodes),
            edge_index.device.index)
-    if not cache:
-        hit = _prefetched.pop(key, None) if _prefetched else None
-        if hit is not None:                     # built ahead on the side stream (prefetch_graph_index): wait for it, adopt its arrays
-            g, ev = hit
-            cur = torch.cuda.current_stream(edge_index.device)
-            cur.wait_event(ev)
-            for t in (g.rowptr, g.col, g.perm, g.rowptr_t, g.col_t, g.perm_t):
-                t.record_stream(cur)            # (allocated under the side stream, read from now on by this one)
-            return g
-        return GraphIndex(edge_index, num_nodes, defer_validation=True)
     g = _graph_cache.get(key)
     if g is None:
         if len(_graph_cache) >= _GRAPH_CACHE_MAX:
@@ -445,7 +402,6 @@ def graph_index(edge_index: torch.Tensor, num_nodes: int, cache: bool = True) ->
 
 def clear_graph_cache() -> None:
     _graph_cache.clear()
-    _prefetched.clear()
     _gcn_cache.clear()
 
 

@@ -788,7 +788,7 @@ def test_l1_loss_is_torch_l1loss():
         ops.l1_loss(p2.cpu(), t2.cpu())
 
 
-def test_gine_conv_one_library_call_each_way_matches_the_composition(golden, monkeypatch):
+def test_gine_one_library_call_each_way_matches_the_composition(golden, monkeypatch):
     """Round 5 (BASELINE config 4): the whole GINE stack as ONE tape node (kagnn_gine_kan_stack_fwd / _bwd), ``GINEKANLayer`` + the
     BatchNorm1d behind it as one node per convolution (kagnn_gine_kan_layer_fwd / _bwd; KAGNN_GINE_STACK_ABI=0), both
     against the per-operation composition (aggregate_gine -> pack -> KANLinear x 2 -> BatchNorm; KAGNN_GINE_LAYER_ABI=0) on the
@@ -810,11 +810,10 @@ def test_gine_conv_one_library_call_each_way_matches_the_composition(golden, mon
     pre = "kan.state."
     state = {k[len(pre):]: T(z[k], DEV) for k in z.files if k.startswith(pre)}
     res = {}
-    for how in ("call", "call_own_csr", "model", "stack", "layer", "ops"):
-        monkeypatch.setattr(graph_ops, "_GINE_MODEL_CALL", how.startswith("call"))
-        monkeypatch.setattr(graph_ops, "_GINE_MODEL_CSR", how == "call")       # the batch's CSR built inside the call / by ops.graph_index before it
-        monkeypatch.setattr(graph_ops, "_GINE_MODEL_NODE", how.startswith("call") or how == "model")
-        monkeypatch.setattr(graph_ops, "_GINE_STACK_ABI", how.startswith("call") or how in ("model", "stack"))
+    for how in ("call", "model", "stack", "layer", "ops"):
+        monkeypatch.setattr(graph_ops, "_GINE_MODEL_CALL", how == "call")
+        monkeypatch.setattr(graph_ops, "_GINE_MODEL_NODE", how in ("call", "model"))
+        monkeypatch.setattr(graph_ops, "_GINE_STACK_ABI", how in ("call", "model", "stack"))
         monkeypatch.setattr(graph_ops, "_GINE_LAYER_ABI", how != "ops")
         m.load_state_dict(state, strict=True)
         m = m.to(DEV).train()
@@ -836,12 +835,7 @@ def test_gine_conv_one_library_call_each_way_matches_the_composition(golden, mon
     cn_ = [n_ for n_ in res["call"][4] if not n_.endswith(("_bytes", "_sizes"))]
     assert type(res["call"][5]).__name__ == "_KaginModelCallFnBackward", type(res["call"][5]).__name__
     assert cn_.count("kagnn_kagin_model_fwd") == 1 and cn_.count("kagnn_kagin_model_bwd") == 1 and "kagnn_gine_kan_stack_fwd" not in cn_, cn_
-    assert len(cn_) <= 5 and "kagnn_csr_build_small" not in cn_, cn_        # + the loss's two calls; the CSR build is inside the forward call
-    on_ = [n_ for n_ in res["call_own_csr"][4] if not n_.endswith(("_bytes", "_sizes"))]
-    assert on_.count("kagnn_csr_build_small") == 1 and on_.count("kagnn_kagin_model_fwd") == 1, on_
-    assert torch.equal(res["call"][0], res["call_own_csr"][0]) and res["call"][1] == res["call_own_csr"][1]
-    for k, gref in res["call_own_csr"][2].items():
-        assert torch.equal(res["call"][2][k], gref), k
+    assert len(cn_) <= 5 and cn_.count("kagnn_csr_build_small") == 1, cn_        # + the loss's two calls and the batch's CSR build (ops.graph_index)
     assert torch.equal(res["call"][0], res["model"][0]) and res["call"][1] == res["model"][1]
     assert set(res["call"][2]) == set(res["model"][2])
     for k, gref in res["model"][2].items():
@@ -880,58 +874,6 @@ def test_gine_conv_one_library_call_each_way_matches_the_composition(golden, mon
         assert_close(res["layer"][2][k], gref, 1e-4, what=f"gine one-call grad.{k}", noise=prenorm_bias_noise(k, res["ops"][2]), elementwise=False)
     for k, v in res["ops"][3].items():
         assert_close(res["layer"][3][k], v, 1e-5, what=f"gine one-call {k}")
-
-
-def test_norm_launch_merges_of_the_graph_level_step_are_bit_identical(golden, monkeypatch):
-    """Round 6 (config 4 is launch-bound): (i) the convolution's column moments are folded by the norm's apply kernel itself
-    (``bn_apply_from_partial_moments_kernel``: no ``moments_finish`` launch), (ii) the last workgroup of the norm's backward
-    statistics pass writes the sums and the table (no ``bn_finish_table`` launch).  Both in the fold order of the launches they
-    replace: prediction, loss, every gradient and the running statistics are the SAME BITS with ``KAGNN_MOM_DEFER=1`` /
-    ``KAGNN_BN_TAIL=1`` as with the two-launch forms (the default: the merged kernels measured SLOWER on the device,
-    profiles/r06_experiments.md 3), on the ZINC-shaped fixture batch and on a batch of 40 000 rows (> 32 moment rows and
-    > 128 statistics rows: the merged forms step aside there)."""
-    z = golden("g8b_zinc_batch")
-
-    class Data:
-        pass
-    small = Data()
-    small.x, small.edge_index, small.batch = T(z["x"], DEV), T(z["edge_index"], DEV), T(z["batch"], DEV)
-    small.edge_attr, small.num_graphs = T(z["edge_attr"], DEV), 256
-    g = torch.Generator().manual_seed(3)
-    big = Data()
-    nb, eb, gb = 40000, 60000, 1000
-    big.x = torch.randint(0, 21, (nb, 1), generator=g).to(DEV)
-    big.edge_index = torch.randint(0, nb, (2, eb), generator=g).to(DEV)
-    big.edge_attr = torch.randint(0, 4, (eb, 1), generator=g).to(DEV)
-    big.batch = torch.sort(torch.randint(0, gb, (nb,), generator=g)).values.to(DEV)
-    big.num_graphs = gb
-    pre = "kan.state."
-    state = {k[len(pre):]: T(z[k], DEV) for k in z.files if k.startswith(pre)}
-    m = kagnn_amd.KAGINRegression(1, 1, 3, 32, 2, 4, 3, 1, 0.0, True)
-    m.atom_encoder = kagnn_amd.graph_models.AtomEncoder(32, [21])
-    m.bond_encoder.bond_embedding_list = torch.nn.ModuleList([torch.nn.Embedding(4, 32)])
-    for d in (small, big):
-        res = {}
-        on = {"KAGNN_MOM_DEFER": "1", "KAGNN_BN_TAIL": "1"}
-        for how, env in (("merged", on), ("two-launch", {}), ("merged again", on)):
-            for k in ("KAGNN_MOM_DEFER", "KAGNN_BN_TAIL"):
-                monkeypatch.delenv(k, raising=False)
-            for k, v in env.items():
-                monkeypatch.setenv(k, v)
-            m.load_state_dict(state, strict=True)
-            m = m.to(DEV).train()
-            m.zero_grad()
-            pred = m(d)
-            pred.abs().mean().backward()
-            res[how] = (pred.detach().clone(), {k: p.grad.clone() for k, p in m.named_parameters()},
-                        {k: v.clone() for k, v in m.state_dict().items() if "running" in k})
-        for other in ("two-launch", "merged again"):
-            assert torch.equal(res["merged"][0], res[other][0]), other
-            for k, gref in res[other][1].items():
-                assert torch.equal(res["merged"][1][k], gref), (other, k)
-            for k, v in res[other][2].items():
-                assert torch.equal(res["merged"][2][k], v), (other, k)
-    ops.flush_graph_checks()
 
 
 def test_model_node_steps_aside_when_it_does_not_cover_the_call(golden):
