@@ -3,7 +3,7 @@
 (sum-aggregate + KAN([F,F,F])) forward AND backward on the synthetic power-law graph of
 SURVEY.md 8(d) (1M nodes / 10M edges, fp32 I/O).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload headline|config3|fastkan|model] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload headline|config3|fastkan|model] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 One JSON line on stdout (rank 0).  Besides the contract's fields it carries
@@ -11,8 +11,16 @@ One JSON line on stdout (rank 0).  Besides the contract's fields it carries
   roofline              the dominant entry point (largest device time per step), HIP events in the timed region
   roofline_kernels      the four hot kernels (aggregation, KAN forward, dX, dW), each against BOTH its HBM bytes and
                         its matrix-core flops -- the limiting ones are the KAN kernels, not the aggregation
-  fp32_mode_ms_per_step the same step on the exact-fp32 MFMA kernels (KAGNN_PRECISION=fp32)
+and, with --full only (measurements of their own, after the timed region; the --no-* options drop parts of them):
+  fp32_mode_ms_per_step the same step on the exact-fp32 MFMA kernels (KAGNN_PRECISION=fp32); half_mode_ms_per_step likewise
+  hbm_copy_GBs          a device copy's bandwidth, and every HBM figure again as a fraction of it
+  secondary             the node model's training step, the other two layer workloads, config 4's graph-level step
+  roofline.traffic      HBM-side bytes of the dominant kernel from rocprofv3 --pmc passes this run spawns
   cpu_baseline          the oracle (the reference's algorithm, "port") on the host cores, bounded sample
+  graph_index_build_ms.steady  a second build of the graph index (a plain run reports the first one only)
+A plain run (no --full) sets up, warms up, runs the three untimed stage-timer steps the roofline block comes from (they also
+pick the kernel the timed region times live, and at --workload model they are Adam steps the timed ones start from), times
+the K steps, writes --dump-outputs and prints the line.
 ms_per_step is the wall time of one of the K timed steps.  --dump-outputs DIR writes what the last timed step computed (the
 layer workloads: y, x_grad and the parameter gradients; model: loss, the state after the Adam step and the gradients) as
 DIR/<name>.npy; every input is seeded, so two builds run with the same arguments can be compared output for output.
@@ -225,9 +233,8 @@ def measure_traffic(args, kernel_prefix):
     issue; WRITE_SIZE is uncalibrated there.  Counts Infinity-Cache hits (fabric-side, not physical HBM)."""
     if shutil.which("rocprofv3") is None or _profiler_active():
         return None, "rocprofv3 unavailable or this process is itself being profiled"
-    argv = ["--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-extras", "--no-traffic", "--no-fp32",
-            "--workload", args.workload, "--nodes", str(args.nodes), "--edges", str(args.edges), "--order", str(args.order),
-            "--precision", args.precision, "--act", args.act]
+    argv = ["--steps", "2", "--warmup", "1", "--workload", args.workload, "--nodes", str(args.nodes), "--edges", str(args.edges),
+            "--order", str(args.order), "--precision", args.precision, "--act", args.act]
     fetch = _pmc_pass("FETCH_SIZE", argv, 150)
     write = _pmc_pass("WRITE_SIZE", argv, 150)
     per_kernel = {}
@@ -469,6 +476,9 @@ def main():
     ap.add_argument("--precision", default=os.environ.get("KAGNN_PRECISION", "split"))
     ap.add_argument("--act", default=os.environ.get("KAGNN_ACT", "fp32"), choices=["fp32", "bf16"],
                     help="bf16: the rows the aggregation gathers are stored as bf16 (build-defined mode for config 2; NOT the headline)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure everything beside the headline figure (exact-fp32 and half-mode steps, "
+                         "copy bandwidth, secondary figures, rocprofv3 traffic passes, CPU baseline, a second graph-index build)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample", type=int, default=100_000, help="nodes in the CPU-baseline sample")
     ap.add_argument("--cpu-full", action="store_true", help="(default behaviour now) CPU baseline at the full workload size when MemAvailable >= 48 GB")
@@ -551,10 +561,12 @@ def main():
     graph = ops.GraphIndex(ei, n)
     torch.cuda.synchronize()
     graph_build_first_ms = (time.perf_counter() - t0) * 1e3
-    t0 = time.perf_counter()
-    graph = ops.GraphIndex(ei, n)                       # (both directions: CSR by destination and its transpose)
-    torch.cuda.synchronize()
-    graph_build_ms = (time.perf_counter() - t0) * 1e3       # one-time per edge_index (cached on its identity): NOT in the timed region
+    graph_build_ms = None
+    if args.full:
+        t0 = time.perf_counter()
+        graph = ops.GraphIndex(ei, n)                   # (both directions: CSR by destination and its transpose)
+        torch.cuda.synchronize()
+        graph_build_ms = (time.perf_counter() - t0) * 1e3   # one-time per edge_index (cached on its identity): NOT in the timed region
 
     def sync():
         if dist is not None:
@@ -818,7 +830,7 @@ def main():
         dog.clear()
 
     fp32_ms = None
-    if not args.no_fp32 and not fp32_mode and world == 1 and not model_wl:
+    if args.full and not args.no_fp32 and not fp32_mode and world == 1 and not model_wl:
         for l in conv.nn.layers:
             l.precision = ops.PREC_FP32
         for _ in range(2):
@@ -830,7 +842,7 @@ def main():
     # the build-defined reduced-precision mode of BASELINE config 2 (KAGNN_PRECISION=half: one fp16 product per fp32 product) on
     # the same layer, measured after the timed region like the exact-fp32 figure -- reported beside the headline, never as it
     half_ms = None
-    if not args.no_fp32 and not fp32_mode and not half_mode and world == 1 and not fastkan and not model_wl:
+    if args.full and not args.no_fp32 and not fp32_mode and not half_mode and world == 1 and not fastkan and not model_wl:
         for l in conv.nn.layers:
             l.precision = ops.PREC_HALF
         for _ in range(2):
@@ -948,21 +960,21 @@ def main():
             out["per_rank"] = per_rank
             out["per_rank_note"] = ("library_ms_per_step: HIP-event time of this rank's kernels (3 profile steps); not_in_library: the rest of "
                                     "the step = exposed waiting on RCCL collectives + launch gaps")
-        if world == 1:
+        if args.full and world == 1:
             copy_gbs = copy_bandwidth(dev)
             out["hbm_copy_GBs"] = copy_gbs
             out["layer_frac_of_copy_bw"] = layer_gbs / copy_gbs
             roof["frac_of_copy_bw"] = (roof["achieved"] / copy_gbs) if roof["unit"] == "GB/s" else None
             for k in kernels:
                 k["hbm_frac_of_copy_bw"] = k["hbm_GBs"] / copy_gbs
-        if not args.no_extras and world == 1 and not fastkan and not model_wl:
+        if args.full and not args.no_extras and world == 1 and not fastkan and not model_wl:
             out["secondary"] = secondary_figures(dev, conv, graph, x.detach().float(), n, e, f, grid, args.order)
             conv_ms = 3 * ms
             out["secondary"]["model_step"]["conv_layers_share"] = conv_ms / out["secondary"]["model_step"]["ms_per_step"]
             if args.workload == "headline" and args.act == "fp32" and not fp32_mode:
                 out["secondary"]["other_layers"] = other_layer_figures(dev, graph, n, e)
                 out["secondary"]["graph_level_step"] = graph_level_step_figures(dev)
-        if not args.no_traffic and world == 1 and not model_wl:
+        if args.full and not args.no_traffic and world == 1 and not model_wl:
             torch.cuda.synchronize()
             prefix = {"kagnn_aggregate_sum": "agg_rows", "kagnn_kan_linear_fwd": "kan_sparse_fwd",
                       "kagnn_kan_linear_bwd_input": "kan_split_dx", "kagnn_kan_linear_bwd_weight": "kan_split_dw",
@@ -974,7 +986,7 @@ def main():
                                    "fabric-side bytes, Infinity-Cache hits included") if traffic else str(detail)
             if isinstance(detail, dict):
                 out["traffic_per_kernel_bytes"] = detail
-        if not args.no_cpu_baseline and world == 1 and not model_wl:
+        if args.full and not args.no_cpu_baseline and world == 1 and not model_wl:
             # the FULL workload when the host has the memory for the reference algorithm's ~46 GB of dense
             # bases (1 warm-up + 1 timed pass at 32 threads, ~75 s on the GPU boxes' 2 x 64-core hosts), else the 1/10 sample
             mem = _mem_available_gb()

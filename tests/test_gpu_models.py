@@ -1278,14 +1278,14 @@ def test_uncached_graph_index_is_the_same_index():
 
 @pytest.mark.parametrize("workload", ["headline", "config3", "fastkan", "model"])
 def test_bench_single_gpu_line_carries_the_contract(workload):
-    """`python bench.py --workload X` at a small size: ONE JSON line with the driver's contract fields, the roofline block, the memory
-    contract, and -- for the headline -- the cpu_baseline block and the secondary figures (model step, other layers, graph-level step)"""
+    """`python bench.py --full --workload X` at a small size: ONE JSON line with the driver's contract fields, the roofline block, the
+    memory contract, and -- for the headline -- the cpu_baseline block and the secondary figures (model step, other layers, graph-level step)"""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--workload", workload, "--nodes", "30000", "--edges", "300000", "--steps", "3",
-           "--warmup", "1", "--no-traffic", "--cpu-sample", "3000", "--cpu-sample-only"]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--full", "--workload", workload, "--nodes", "30000", "--edges", "300000",
+           "--steps", "3", "--warmup", "1", "--no-traffic", "--cpu-sample", "3000", "--cpu-sample-only"]
     r = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=900)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, (r.returncode, r.stdout[-1000:], r.stderr[-2000:])
@@ -1307,6 +1307,27 @@ def test_bench_single_gpu_line_carries_the_contract(workload):
         sec = d["secondary"]
         assert sec["model_step"]["ms_per_step"] > 0 and sec["graph_level_step"]["ms_per_step"] > 0 and len(sec["graph_level_step"]["repeats_ms_per_step"]) == 3
         assert set(sec["other_layers"]) == {"config3", "fastkan"} and d["fp32_mode_ms_per_step"] > d["ms_per_step"]
+
+
+def test_bench_plain_run_measures_only_the_headline():
+    """`python bench.py` without --full: the contract fields and the roofline block of the timed region, and none of the measurements
+    --full adds (other precisions, copy bandwidth, secondary figures, rocprofv3 passes, CPU baseline, a second graph-index build)"""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--nodes", "30000", "--edges", "300000", "--steps", "3", "--warmup", "1"]
+    r = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=600)
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert r.returncode == 0 and len(lines) == 1, (r.returncode, r.stdout[-1000:], r.stderr[-2000:])
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["complete"] is True and d["config"]["workload"].startswith("headline")
+    assert abs(d["value"] - 300000 / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+    assert d["layer_hbm_frac"] > 0 and d["roofline"]["frac"] > 0 and d["roofline"]["traffic"] is None and d["roofline_kernels"]
+    assert d["fp32_mode_ms_per_step"] is None and d["half_mode_ms_per_step"] is None
+    assert d["graph_index_build_ms"]["first_call"] > 0 and d["graph_index_build_ms"]["steady"] is None
+    for k in ("secondary", "cpu_baseline", "hbm_copy_GBs", "traffic_per_kernel_bytes"):
+        assert k not in d, k
 
 
 def test_bench_dump_outputs_are_the_last_timed_steps_results(tmp_path):

@@ -6,7 +6,7 @@ set -u
 TAG=${1:-r01}
 R=$PWD; OUT=$R/gpurun_out/profiles_$TAG; RAW=$R/gpurun_out/prof_$TAG
 rm -rf $OUT $RAW; mkdir -p $OUT
-python bench.py 2>/dev/null | tail -1 > $OUT/${TAG}_bench.json
+python bench.py --full 2>/dev/null | tail -1 > $OUT/${TAG}_bench.json
 tools/prof.sh $TAG > /dev/null 2>&1
 python tools/profsum.py $RAW > $OUT/${TAG}_bench_kernel_trace_and_pmc.txt
 python - <<PY
@@ -30,16 +30,16 @@ KAGNN_ACT=bf16 python tools/configs_sweep.py 2 2>/dev/null | grep "cfg2 " > $OUT
 for a in fp32 bf16; do for p in split half; do
   echo "KAGNN_ACT=$a KAGNN_PRECISION=$p: $(KAGNN_ACT=$a KAGNN_PRECISION=$p python tools/configs_sweep.py 2 2>/dev/null | grep 'cfg2 ')"
 done; done > $OUT/${TAG}_config2_modes.txt
-python bench.py --precision half --no-cpu-baseline --no-extras --no-traffic 2>/dev/null | tail -1 > $OUT/${TAG}_bench_half.json
-python bench.py --precision half --act bf16 --no-cpu-baseline --no-extras --no-traffic 2>/dev/null | tail -1 > $OUT/${TAG}_bench_half_bf16_gather.json
-python bench.py --act bf16 --no-cpu-baseline --no-extras --no-fp32 2>/dev/null | tail -1 > $OUT/${TAG}_bench_bf16_gather.json
-python bench.py --workload config3 --no-cpu-baseline --no-extras --no-traffic 2>/dev/null | tail -1 > $OUT/${TAG}_bench_config3.json
-python bench.py --workload fastkan 2>/dev/null | tail -1 > $OUT/${TAG}_bench_fastkan.json
+python bench.py --full --precision half --no-cpu-baseline --no-extras --no-traffic 2>/dev/null | tail -1 > $OUT/${TAG}_bench_half.json
+python bench.py --full --precision half --act bf16 --no-cpu-baseline --no-extras --no-traffic 2>/dev/null | tail -1 > $OUT/${TAG}_bench_half_bf16_gather.json
+python bench.py --full --act bf16 --no-cpu-baseline --no-extras --no-fp32 2>/dev/null | tail -1 > $OUT/${TAG}_bench_bf16_gather.json
+python bench.py --full --workload config3 --no-cpu-baseline --no-extras --no-traffic 2>/dev/null | tail -1 > $OUT/${TAG}_bench_config3.json
+python bench.py --full --workload fastkan 2>/dev/null | tail -1 > $OUT/${TAG}_bench_fastkan.json
 tools/prof_fastkan.sh ${TAG}_fk 40 > $OUT/${TAG}_fastkan_layer_kernel_trace.txt 2>&1
 python tools/shard_plan_probe.py --link-gbs=50 2>/dev/null | grep -v amdgpu.ids > $OUT/${TAG}_shard_plan.txt; cp gpurun_out/shard_plan.json $OUT/${TAG}_shard_plan.json
 # round 6: the other sharded paths (FastKAN-GIN layer, GKAN_Nodes step), the model workload as a bench line, config 4's step repeated
 python tools/shard_plan_probe_e2.py --link-gbs=50 2>/dev/null | grep -v amdgpu.ids > $OUT/${TAG}_shard_plan_e2.txt; cp gpurun_out/shard_plan_e2.json $OUT/${TAG}_shard_plan_e2.json
-python bench.py --workload model 2>/dev/null | tail -1 > $OUT/${TAG}_bench_model.json
+python bench.py --full --workload model 2>/dev/null | tail -1 > $OUT/${TAG}_bench_model.json
 python tools/cfg4_step.py 2>/dev/null | tail -1 > $OUT/${TAG}_config4_step.json
 KAGNN_CFG4_MT=1 python tools/cfg4_step.py 2>/dev/null | tail -1 > $OUT/${TAG}_config4_step_autograd_threads.json
 python tools/kernel_resources.py > $OUT/${TAG}_kernel_resources.txt 2>&1
