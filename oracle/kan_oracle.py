@@ -390,7 +390,8 @@ def node_model_forward(x: Tensor, edge_index, state: dict, arch: str, conv_type:
     """``GKAN_Nodes.forward`` (``models.py:192-203``) / ``GFASTKAN_Nodes.forward`` (``:246-257``) on a state_dict with
     the reference's keys (``convs.{i}.nn.layers.{j}.* | convs.{i}.lin.* + convs.{i}.bias``, ``bns.{i}.*``,
     ``lay_out.*``): ``mp_layers`` x {conv -> BatchNorm1d -> dropout(p=0)}, skip-concat of the input and every layer
-    output, KANLinear / FastKANLayer read-out.  ``arch``: 'kan' | 'fastkan'; ``conv_type``: 'gin' | 'gcn'.
+    output, KANLinear / FastKANLayer read-out.  ``arch``: 'kan' | 'fastkan'; ``conv_type``: 'gin' | 'gcn' | 'gat' (keys
+    ``convs.{i}.lin.*``, ``convs.{i}.att_src|att_dst|bias``; heads from ``att_src.shape[1]``).
     ``edge_index`` may be a torch sparse ``adj_t`` for 'gcn' (``gcn_norm_sparse``).  BatchNorm in training mode uses
     batch statistics (running buffers are not updated here)."""
     def sub(prefix):
@@ -428,6 +429,10 @@ def node_model_forward(x: Tensor, edge_index, state: dict, arch: str, conv_type:
                 x = sum_aggregate(lin(x), ei, x.size(0), w) + c["bias"]
             else:
                 x = gcn_conv(x, edge_index, lin, c["bias"])
+        elif conv_type == "gat":
+            # GATConv keys: lin.*, att_src / att_dst [1, heads, C], bias [heads * C] (models.py:39-46,76-83)
+            x = gat_conv(x, edge_index, one(sub(f"convs.{i}.lin.")), c["att_src"], c["att_dst"], c.get("bias"),
+                         c["att_src"].shape[1])
         else:
             raise ValueError("unknown conv_type")
         b = sub(f"bns.{i}.")

@@ -111,6 +111,16 @@ def prenorm_bias_noise(name, wants):
     return 1e-4 * peak
 
 
+def gat_att_noise(n, scale=1.0):
+    """Noise floor for the gradients of the GAT attention vectors ``att_src`` / ``att_dst``: sums over all ``n`` nodes of
+    (logit gradient) x (features).  Where a node has one incoming edge its softmax is the constant 1 and the exact term is 0
+    (and with every logit of a row on one side of the leaky ReLU's kink its whole att_dst term is), so what fp32 adds up is
+    rounding noise that grows like sqrt(n): 2e-5 x max(1, 0.05 sqrt(n)) at unit-scale operands (n = 20 000, e = 0: 5e-5).
+    ``scale``: the operands' magnitude relative to that unit scale -- max|xh| x max(1, max|logit|), since the fp32 rounding of
+    a logit perturbs every softmax weight of its row by eps32 x |logit|.  Only for att_src / att_dst."""
+    return 2e-5 * max(1.0, 0.05 * float(n) ** 0.5) * max(1.0, float(scale))
+
+
 def must_fail(got, want, tol=TOL, what="", **kw):
     """mutation guard: the SAME assertion the test just passed has to reject this ``got`` (with the old
     ``max(1, .)`` scale an all-zero input gradient passed the arxiv-shaped model tests)"""

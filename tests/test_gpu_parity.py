@@ -1274,7 +1274,8 @@ def test_kagat_conv_vs_oracle(shape):
     torch.manual_seed(sum(shape))
     ei = torch.randint(0, n - 10, (2, e))
     ei[:, :20] = torch.arange(20).repeat(2, 1)                    # self loops
-    ei[1, 20:20 + (1500 if e > 10000 else 200)] = 7               # a hub destination (beyond the 512-edge hub threshold in the big case)
+    ei[1, 20:20 + (1500 if e > 10000 else 200)] = 7               # a long row (beyond ops.HUB_THRESHOLD = 96 edges; these small
+                                                                  # graphs take the one-launch CSR build, so the row kernels walk it)
     ei[:, 300:320] = ei[:, 320:340]                               # duplicates
     conv = kagnn_amd.KAGATConv(fi, c, heads, grid_size=5, spline_order=3)
     conv.bias.data.uniform_(-0.2, 0.2)

@@ -164,6 +164,36 @@ def _node_model(arch, kind, dropout):
     return build
 
 
+def _gat_node_model(arch, hidden):
+    """GKAN_Nodes / GFASTKAN_Nodes('gat', 4 heads) on a graph the rocPRIM CSR build indexes (> 65 536 edges: hub segments) with
+    explicit self loops (their slots of the per-edge logit gradient, indexed through perm, must be written), duplicate edges and
+    a 1000-edge destination hub"""
+    def build():
+        n, f, classes = 3001, 40, 7
+        ei = orc.powerlaw_graph(n, 70_000, seed=9)
+        ei[:, :30] = torch.arange(30).repeat(2, 1)
+        ei[:, 30:60] = ei[:, 60:90].clone()
+        ei[1, 100:1100] = 5
+        ei = ei.to(DEV)
+        torch.manual_seed(13)
+        if arch == "kan":
+            model = kagnn_amd.GKAN_Nodes("gat", 2, f, hidden, classes, skip=True, grid_size=5, spline_order=3, heads=4).to(DEV)
+        else:
+            model = kagnn_amd.GFASTKAN_Nodes("gat", 2, f, hidden, classes, skip=True, grid_size=4, heads=4).to(DEV)
+        x = (torch.randn(n, f, generator=torch.Generator().manual_seed(14)) * 0.4).to(DEV)
+        y = torch.randint(0, classes, (n,), generator=torch.Generator().manual_seed(15)).to(DEV)
+
+        def run():
+            g = ops.GraphIndex(ei, n)
+            assert g.num_hub_seg > 0
+            loss = ops.softmax_cross_entropy(model(x, g), y)
+            loss.backward()
+            return [loss] + [p.grad for p in model.parameters() if p.grad is not None] + \
+                   [b for b in model.buffers() if b.dtype.is_floating_point] + [g.rowptr, g.col, g.perm, g.rowptr_t, g.col_t, g.perm_t]
+        return model, run
+    return build
+
+
 def _graph_level(flavour):
     """the ZINC-shaped mini-batch step: embedding encoders, single-launch CSR, the GINE stack as one tape node, pooling, read-out"""
     def build():
@@ -212,6 +242,8 @@ CASES["KAN GIN layer half mode"] = ("half", _gin("kan", 5000, 60000, 64, 64))
 for _a, _k, _p in [("kan", "gin", 0.0), ("kan", "gin", 0.3), ("kan", "gcn", 0.0), ("fastkan", "gin", 0.0), ("fastkan", "gcn", 0.2)]:
     CASES[f"{_a} {_k} node model dropout {_p}"] = ("split", _node_model(_a, _k, _p))
 CASES["kan gin node model half mode"] = ("half", _node_model("kan", "gin", 0.0))
+CASES["kan gat node model 4x16 hubs"] = ("split", _gat_node_model("kan", 16))          # packed heads
+CASES["fastkan gat node model 4x20 hubs"] = ("split", _gat_node_model("fastkan", 20))  # wave kernels
 
 
 @pytest.mark.parametrize("case", list(CASES))

@@ -295,6 +295,34 @@ def test_hot_path_kernels_do_not_spill_registers():
     assert all(k["vgpr_count"] <= 512 for k in rows)
 
 
+def test_gat_kernel_cases_reach_every_gat_kernel_and_variant():
+    """tests/test_gpu_gat.py restates how csrc/gat.hip and ops._GatFn choose their kernels (``gat_kernels``) and parametrises its
+    kernel-level cases so that each of them runs.  Without a GPU: the restated thresholds are still the ones in the sources, and
+    the case list still reaches every kernel, every KC instantiation of gat_att_grad_partial, the torch fallback, the hub kernels
+    behind both row paths, a long row inside the row kernels, a source hub, the last channel chunk and the layout refusal of the
+    packed path -- moving a threshold fails here instead of thinning the coverage."""
+    import test_gpu_gat as tg
+    from kagnn_amd import ops
+    gat = open(os.path.join(ROOT, "kagnn_amd", "csrc", "gat.hip")).read()
+    csr = open(os.path.join(ROOT, "kagnn_amd", "csrc", "csr.hip")).read()
+    for snippet in ("constexpr int kGatMaxK = 8;", "constexpr int kPk = 2;", "C == 4 || C == 8 || C == 16 || C == 32 || C == 64",
+                    "H * C <= 64 * kPk", "if (C > 16 * kGatMaxK)", "if (H * C > 1024)",
+                    "if (kc <= 1) L(1); else if (kc <= 2) L(2); else if (kc <= 4) L(4); else if (kc <= 8) L(8); else L(16);"):
+        assert snippet in gat, f"gat.hip no longer holds {snippet!r}: update gat_kernels in tests/test_gpu_gat.py"
+    for snippet in ("constexpr int kSmallMax = 1 << 16;", "E >= 1 && E <= kSmallMax && N >= 1 && N <= kSmallMax",
+                    "if (t - s <= T) return;"):
+        assert snippet in csr, f"csr.hip no longer holds {snippet!r}: update gat_kernels in tests/test_gpu_gat.py"
+    assert "heads * channels <= 1024" in inspect.getsource(ops._GatFn.backward)
+    assert (tg.PACKED_C, tg.PACKED_MAX_HC, tg.MAX_C, tg.ATT_GRAD_MAX_HC, tg.SMALL_CSR_MAX) == ((4, 8, 16, 32, 64), 128, 128, 1024, 1 << 16)
+    reached = set().union(*(tg.case_kernels(c) for c in tg.KERNEL_CASES))
+    need = {"gat_logits", "gat_fwd_rows", "gat_bwd_dst_rows", "gat_bwd_src_rows", "gat_fwd", "gat_bwd_dst", "gat_bwd_src",
+            "gat_fwd_hub", "gat_bwd_dst hub", "packed + hub", "wave + hub", "long row in the row kernels", "source hub",
+            "packed refused by layout", "wave chunks 8", "hub chunks 8", "att grad torch fallback", "gat_att_grad_finish"}
+    need |= {f"gat_att_grad_partial<{k}>" for k in (1, 2, 4, 8, 16)}
+    assert not need - reached, sorted(need - reached)
+    assert tg.gat_kernels(1, 129, 10, 10, 1) == {"refused"}
+
+
 def test_assert_close_scales_by_the_reference_itself_and_can_fail():
     """tests/helpers.assert_close (round 5): the bound is relative to max|reference| of the tensor, so small
     tensors are held to the same RELATIVE accuracy as large ones; zeros and 1e-3 perturbations are rejected whatever the

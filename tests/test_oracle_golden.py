@@ -378,3 +378,45 @@ def test_g13_graph_classification_restatement(golden, name, family, arch, bi):
         zero_in = orc.graph_classification_forward(torch.zeros(1, 16, dtype=torch.float64), torch.zeros(2, 0, dtype=torch.int64),
                                                    torch.zeros(1, dtype=torch.int64), 1, {k: v.detach() for k, v in st.items()}, arch, family, 0)
         close(empty, zero_in[0], 1e-12)
+
+
+@pytest.mark.parametrize("arch", ["kan", "fastkan"])
+def test_node_model_forward_gat_is_gat_conv_norm_concat_read_out(arch):
+    """oracle.node_model_forward(conv_type='gat') on a state_dict with the reference's keys (convs.{i}.lin.*, att_src, att_dst,
+    bias; bns.{i}.*; lay_out.*) is the hand composition gat_conv -> batch_norm on batch statistics -> skip concat -> read-out,
+    with the heads taken from att_src.shape[1]"""
+    import torch.nn.functional as F
+    import kagnn_amd
+    n, fin, c, heads, classes, k = 40, 6, 3, 2, 4, 2
+    torch.manual_seed(0)
+    if arch == "kan":
+        model = kagnn_amd.GKAN_Nodes("gat", 2, fin, c, classes, grid_size=4, spline_order=k, heads=heads)
+    else:
+        model = kagnn_amd.GFASTKAN_Nodes("gat", 2, fin, c, classes, grid_size=4, heads=heads)
+    g = torch.Generator().manual_seed(1)
+    st = {}
+    for name, v in model.state_dict().items():
+        v = v.double() if v.is_floating_point() else v
+        if name.endswith(("att_src", "att_dst")) or (name.startswith(("convs.", "bns.")) and name.count(".") == 2
+                                                     and name.endswith(("bias", "weight"))):
+            v = torch.randn(v.shape, generator=g, dtype=torch.float64)      # nothing at its zero / one initialisation
+        st[name] = v
+    ei = torch.randint(0, n, (2, 150), generator=g)
+    ei[:, :6] = torch.arange(6).repeat(2, 1)                                  # explicit self loops
+    x = torch.randn(n, fin, generator=g, dtype=torch.float64)
+    got = orc.node_model_forward(x, ei, st, arch, "gat", 2, spline_order=k)
+
+    def lin(prefix, h):
+        p = {q[len(prefix):]: v for q, v in st.items() if q.startswith(prefix)}
+        if arch == "kan":
+            return orc.kan_linear_forward(h, p["base_weight"], p["spline_weight"], p["spline_scaler"], p["grid"], k)
+        return orc.fastkan_forward(h, [p])
+
+    h, outs = x, [x]
+    for i in range(2):
+        h = orc.gat_conv(h, ei, lambda t: lin(f"convs.{i}.lin.", t), st[f"convs.{i}.att_src"], st[f"convs.{i}.att_dst"],
+                         st[f"convs.{i}.bias"], heads)
+        h = F.batch_norm(h, None, None, st[f"bns.{i}.weight"], st[f"bns.{i}.bias"], True, 0.0, 1e-5)
+        outs.append(h)
+    want = lin("lay_out.", torch.cat(outs, dim=1))
+    assert got.shape == (n, classes) and torch.equal(got, want)
