@@ -11,9 +11,11 @@ import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
-from .ops import (PREC_FP32, GraphIndex, _same_knots, _batchnorm_fwd_raw, _call, _fits32, _kan_bwd_input_raw, _kan_bwd_weight_raw, _kan_fwd_raw, _ld,
-                  _need_cuda, _on_operand_device, _ptr, _ptr_array, _rows, _segment_broadcast_raw, _segment_pool_raw, _sizes, _stream,
-                  _weights_key, _ws, default_precision, graph_index, kan_pack_chain, split_like)
+from .ops import (PREC_FP32, GraphIndex, _batchnorm_fwd_raw, _call, _chain_bwd_buffers, _chain_bwd_result, _chain_fwd_call,
+                  _chain_layers, _chain_plan, _chain_saved, _chain_unsaved, _fits32, _fixed_args, _kan_bwd_input_raw,
+                  _kan_bwd_weight_raw, _kan_fwd_raw, _ld, _need_cuda, _on_operand_device, _ptr, _ptr_array, _rows, _same_knots,
+                  _segment_broadcast_raw, _segment_pool_raw, _sizes, _stream, _weights_key, _ws, default_precision, graph_index,
+                  kan_pack_chain, split_like)
 
 
 class _GineKanLayerFn(Function):
@@ -27,81 +29,56 @@ class _GineKanLayerFn(Function):
 
     @staticmethod
     @_on_operand_device
-    def forward(ctx, x, edge_attr, g, self_scale, knots, grid_size, spline_order, mode, bn_w, bn_b, rm, rv, momentum, eps, *params):
+    def forward(ctx, x, edge_attr, bn_w, bn_b, g, self_scale, knots, grid_size, spline_order, mode, rm, rv, momentum, eps, *params):
         """``bn_w`` .. ``eps``: the training-mode BatchNorm1d (affine) that follows the convolution, or ``bn_w is None``: none"""
         _need_cuda(x, edge_attr, bn_w, bn_b, rm, rv, *params)
-        bn = None if bn_w is None else True
-        nl = len(params) // 3
-        layers = [(params[3 * i].contiguous(), params[3 * i + 1].contiguous(), params[3 * i + 2].contiguous()) for i in range(nl)]
+        layers, widths = _chain_layers(params)
         xg, ea = _rows(x), _rows(edge_attr)
         n, dev = xg.size(0), xg.device
-        widths = [layers[0][1].size(1)] + [sw.size(0) for _, sw, _ in layers]
         if n != g.num_nodes or ea.shape != (g.num_edges, widths[0]) or xg.size(1) != widths[0]:
             raise ValueError("x must be [N, F] and edge_attr [E, F] with F the chain's input width, N / E those of the graph")
-        acts = [torch.empty((n, w), dtype=torch.float32, device=dev) for w in widths]
-        pfs, pds = [], []
-        for i in range(nl):
-            fb, db = _sizes("kagnn_kan_pack_bytes", widths[i], widths[i + 1], grid_size, spline_order, mode, outputs=2)
-            pfs.append(_ws(fb, dev)); pds.append(_ws(db, dev))
-        warr = (ctypes.c_int32 * (nl + 1))(*widths)
-        wf, _ = _sizes("kagnn_gin_kan_layer_workspace_bytes", n, nl, tuple(widths), grid_size, spline_order, mode, 0, 0, outputs=2)
-        ws = _ws(wf, dev)
-        mom = torch.empty((2, widths[nl]), dtype=torch.float32, device=dev) if bn is not None else None
         if ea.numel() == 0:              # a batch without edges: the library wants non-null edge arrays; it reads no element of them
             ea = torch.zeros((1, widths[0]), dtype=torch.float32, device=dev)
         perm = g.perm if g.num_edges else torch.zeros(1, dtype=torch.int32, device=dev)
-        _call("kagnn_gine_kan_layer_fwd", _ptr(xg), _ld(xg), _ptr(ea), _ld(ea), n, _ptr(g.rowptr), _ptr(g.col), _ptr(perm),
-              float(self_scale), nl, warr, _ptr_array([l[0] for l in layers]), _ptr_array([l[1] for l in layers]),
-              _ptr_array([l[2] for l in layers]), _ptr(knots), grid_size, spline_order, mode, _ptr_array(acts), _ptr_array(pfs),
-              _ptr_array(pds), _ptr(mom[0]) if mom is not None else None, _ptr(mom[1]) if mom is not None else None,
-              _ptr(ws), ws.numel(), _stream())
-        y = acts[nl]
-        saved = [xg, ea]
-        for i in range(nl):
-            saved += [acts[i], layers[i][1], layers[i][2], pds[i]]
-        ctx.meta = (g, self_scale, grid_size, spline_order, mode, nl, widths, bn is not None)
-        if bn is None:
-            ctx.save_for_backward(*saved, knots)
+        head = (_ptr(xg), _ld(xg), _ptr(ea), _ld(ea), n, _ptr(g.rowptr), _ptr(g.col), _ptr(perm), float(self_scale))
+        acts, pds, mom = _chain_fwd_call("kagnn_gine_kan_layer_fwd", head, n, dev, layers, widths, knots, grid_size, spline_order, mode,
+                                         (0, 0), bn_w is not None)
+        y = acts[-1]
+        ctx.meta = (g, self_scale, grid_size, spline_order, mode, len(layers), widths)
+        if bn_w is None:
+            ctx.save_for_backward(*_chain_saved(acts, layers, pds, knots, xg, ea))
             return y
         h, mean, rstd = _batchnorm_fwd_raw(y, bn_w, bn_b, rm, rv, True, momentum, eps, mom)
-        ctx.save_for_backward(*saved, knots, y, bn_w, mean, rstd)
+        ctx.save_for_backward(*_chain_saved(acts, layers, pds, knots, xg, ea, y, bn_w, mean, rstd))
         return h
 
     @staticmethod
     @once_differentiable
     @_on_operand_device
     def backward(ctx, gh):
-        g, self_scale, G, K, mode, nl, widths, has_bn = ctx.meta
-        t = ctx.saved_tensors
-        xg, ea = t[0], t[1]
-        knots = t[2 + 4 * nl]
+        g, self_scale, G, K, mode, nl, widths = ctx.meta
+        acts, sws, scs, pds, knots, (xg, ea, *norm) = _chain_unsaved(ctx.saved_tensors, nl)
         gh = _rows(gh)
         n, dev = gh.size(0), gh.device
         f32 = dict(dtype=torch.float32, device=dev)
-        acts = [t[2 + 4 * i] for i in range(nl)]
-        sws, scs, pds = [t[3 + 4 * i] for i in range(nl)], [t[4 + 4 * i] for i in range(nl)], [t[5 + 4 * i] for i in range(nl)]
-        gbw = [torch.empty((widths[i + 1], widths[i]), **f32) for i in range(nl)]
-        gsw = [torch.empty((widths[i + 1], widths[i], G + K), **f32) for i in range(nl)]
-        gsc = [torch.empty((widths[i + 1], widths[i]), **f32) for i in range(nl)]
+        gbw, gsw, gsc, warr, wb = _chain_bwd_buffers(n, dev, widths, G, K, mode, (0, 0))
         gx = torch.empty((n, widths[0]), **f32)
         gea = torch.empty((g.num_edges, widths[0]), **f32) if ctx.needs_input_grad[1] else None
-        _, wb = _sizes("kagnn_gin_kan_layer_workspace_bytes", n, nl, tuple(widths), G, K, mode, 0, 0, outputs=2)
         y = bn_w = mean = rstd = g_bnw = g_bnb = None
-        if has_bn:
-            y, bn_w, mean, rstd = t[3 + 4 * nl:7 + 4 * nl]
+        if norm:
+            y, bn_w, mean, rstd = norm
             wb += _sizes("kagnn_gin_kan_layer_bwd_bn_workspace_bytes", n, widths[nl])
             g_bnw, g_bnb = torch.empty(widths[nl], **f32), torch.empty(widths[nl], **f32)
         ws = _ws(wb, dev)
-        warr = (ctypes.c_int32 * (nl + 1))(*widths)
         perm_t = g.perm_t if g.num_edges else torch.zeros(1, dtype=torch.int32, device=dev)
         _call("kagnn_gine_kan_layer_bwd", _ptr(gh), _ld(gh), _ptr(y), _ld(y) if y is not None else 0, _ptr(bn_w), _ptr(mean), _ptr(rstd),
               _ptr(g_bnw), _ptr(g_bnb), _ptr(xg), _ld(xg), _ptr(ea), _ld(ea), n, _ptr(g.rowptr_t), _ptr(g.col_t), _ptr(perm_t),
               float(self_scale), nl, warr, _ptr_array(sws), _ptr_array(scs), _ptr(knots), G, K, mode, _ptr_array(acts), _ptr_array(pds),
               _ptr(gx), widths[0], _ptr(gea), widths[0], _ptr_array(gbw), _ptr_array(gsw), _ptr_array(gsc), _ptr(ws), ws.numel(), _stream())
-        grads = []
-        for i in range(nl):
-            grads += [gbw[i], gsw[i], gsc[i]]
-        return (gx, gea, None, None, None, None, None, None, g_bnw, g_bnb, None, None, None, None, *grads)
+        return _chain_bwd_result(_GINE_FIXED, (gx, gea, g_bnw, g_bnb), gbw, gsw, gsc)
+
+
+_GINE_FIXED = _fixed_args(_GineKanLayerFn)
 
 
 class _StackState:
@@ -317,30 +294,18 @@ def gine_kan_layer(x, edge_attr, g: "GraphIndex", self_scale: float, net, batch_
     layers = list(getattr(net, "layers", []))
     if not (1 <= len(layers) <= 8) or any(type(l).__name__ != "KANLinear" for l in layers):
         return None
+    plan = _chain_plan(layers)
+    if plan is None or not split_like(plan[0]):
+        return None
+    mode, knots, params = plan
     first = layers[0]
-    mode = first.precision if first.precision is not None else default_precision()
-    if not split_like(mode) or first.grid_size + first.spline_order > 16:
-        return None
-    if any(l.precision != first.precision or l.grid_size != first.grid_size or l.spline_order != first.spline_order
-           or not l.enable_standalone_scale_spline for l in layers):
-        return None
-    #  the library evaluates the whole chain on ONE knot vector: layers with uniform but different grids (another
-    # grid_range, update_grid with grid_eps = 1) must not be folded onto the first layer's -- the guards of ops.gin_kan_layer
-    knots = [l._knots() for l in layers]
-    if any(k.dim() != 1 or k.numel() != knots[0].numel() for k in knots) or not _same_knots(layers, knots):
-        return None
-    if max(max(l.in_features, l.out_features) for l in layers) > 7680:
-        return None
-    params = []
-    for l in layers:
-        params += [l.base_weight, l.spline_weight, l.spline_scaler]
     bn = (None, None, None, None, 0.0, 0.0)
     if batch_norm is not None:
         factor, use_running = batch_norm.step()
         bn = (batch_norm.weight, batch_norm.bias, batch_norm.running_mean if use_running else None,
               batch_norm.running_var if use_running else None, factor, batch_norm.eps)
-    return _GineKanLayerFn.apply(x, edge_attr, g, float(self_scale), knots[0], first.grid_size, first.spline_order, mode, *bn, *params)
-
+    return _GineKanLayerFn.apply(x, edge_attr, bn[0], bn[1], g, float(self_scale), knots[0], first.grid_size, first.spline_order, mode,
+                                 *bn[2:], *params)
 
 
 def _embedding_sum_fwd_raw(x, tables):

@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import ctypes
 import functools
+import inspect
 import os
 import weakref
 from ctypes import byref, c_int64, c_size_t
@@ -22,6 +23,8 @@ from . import _lib
 from ._lib import PREC_FP32, PREC_FP32_GRID, PREC_HALF, PREC_SPLIT
 
 HUB_THRESHOLD = int(os.environ.get("KAGNN_HUB_THRESHOLD", "96"))       # rows above this many edges are split into segments
+_LAYER_ABI = os.environ.get("KAGNN_LAYER_ABI", "1") != "0"     # 1: kagnn_gin_kan_layer_fwd / _bwd (one library call each way)
+_FOLD_NORM_STATS = os.environ.get("KAGNN_FOLD_NORM_STATS", "1") != "0"
 
 
 def default_precision() -> int:
@@ -500,8 +503,13 @@ def aggregate_sum_affine(x, g: GraphIndex, self_scale: float, affine: torch.Tens
     return out
 
 
+def _bf16_gather_width_ok(f: int) -> bool:
+    """a row width the bf16 aggregation takes (the rule is api.hip's; this is its one copy on the Python side)"""
+    return f % 8 == 0 and f <= 512
+
+
 def _bf16_rows_ok(t: torch.Tensor) -> bool:
-    return t.size(1) % 8 == 0 and t.size(1) <= 512 and _ld(t) % 8 == 0 and t.data_ptr() % 16 == 0
+    return _bf16_gather_width_ok(t.size(1)) and _ld(t) % 8 == 0 and t.data_ptr() % 16 == 0
 
 
 def to_bf16_rows(x: torch.Tensor) -> torch.Tensor:
@@ -823,41 +831,181 @@ class _KANLinearFn(Function):
         return gx, gbw, gsw, gsc, None, None, None, None, None, None
 
 
-_LAYER_ABI = os.environ.get("KAGNN_LAYER_ABI", "1") != "0"     # 1: kagnn_gin_kan_layer_fwd / _bwd (one library call each way)
-
-
 def _ptr_array(tensors):
     return (ctypes.c_void_p * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])
 
 
-def _gin_kan_layer_fwd_raw(xg, g, self_scale, knots, grid_size, spline_order, mode, layers, widths, moments, in_affine=None):
-    """``kagnn_gin_kan_layer_fwd``: -> (acts [h0, ..., y], input-gradient packs per layer, column moments of y or None)"""
-    n, dev, nl = xg.size(0), xg.device, len(layers)
+# ------------------------------------------------------------------------ one "aggregate + KAN chain (+ BatchNorm)" library call:
+# the host side that _GinKanLayerFn, _GinKanBnLayerFn and graph_ops._GineKanLayerFn share
+
+def _fixed_args(node) -> int:
+    """how many arguments ``node.forward`` takes in front of ``*params`` (``ctx`` not counted): its backward returns that many
+    gradients before the parameters', and the parameters' ``needs_input_grad`` entries start there"""
+    return len(inspect.signature(node.forward).parameters) - 2
+
+
+def _chain_layers(params):
+    """a node's ``*params`` (``base_weight, spline_weight, spline_scaler`` per layer) -> (contiguous triples per layer, the
+    chain's widths ``[in, out_0, ..., out]``)"""
+    nl = len(params) // 3
+    layers = [(params[3 * i].contiguous(), params[3 * i + 1].contiguous(), params[3 * i + 2].contiguous()) for i in range(nl)]
+    return layers, [layers[0][1].size(1)] + [sw.size(0) for _, sw, _ in layers]
+
+
+def _chain_fwd_call(name, head, n, dev, layers, widths, knots, grid_size, spline_order, mode, hub_segs, moments):
+    """One chain forward entry point: allocates what it writes, then calls ``name`` with ``head`` (the arguments up to the layer
+    count: the rows, the graph) and the arguments all of them end with -> (acts ``[h0, ..., y]``, input-gradient packs per layer,
+    the [2, out] column moments of y or None).  ``hub_segs``: the graph's hub segments by destination and by source."""
+    nl = len(layers)
     acts = [torch.empty((n, w), dtype=torch.float32, device=dev) for w in widths]
     pfs, pds = [], []
     for i in range(nl):
         fb, db = _sizes("kagnn_kan_pack_bytes", widths[i], widths[i + 1], grid_size, spline_order, mode, outputs=2)
         pfs.append(_ws(fb, dev)); pds.append(_ws(db, dev))
     warr = (ctypes.c_int32 * (nl + 1))(*widths)
-    wf, _ = _sizes("kagnn_gin_kan_layer_workspace_bytes", n, nl, tuple(widths), grid_size, spline_order, mode,
-                   g.num_hub_seg, g.num_hub_seg_t, outputs=2)
+    wf, _ = _sizes("kagnn_gin_kan_layer_workspace_bytes", n, nl, tuple(widths), grid_size, spline_order, mode, *hub_segs, outputs=2)
     ws = _ws(wf, dev)
     mom = torch.empty((2, widths[nl]), dtype=torch.float32, device=dev) if moments else None
-    if in_affine is not None:          # the gathered rows are in_affine[0] * xg + in_affine[1]: a folded BatchNorm1d (AffineRows)
-        _call("kagnn_gin_kan_layer_fwd_affine", _ptr(xg), _ld(xg), n,
-              _ptr(g.rowptr), _ptr(g.col), _ptr(g.hub_seg) if g.num_hub_seg else None, g.num_hub_seg, g.hub_threshold,
-              float(self_scale), _ptr(in_affine[0]), _ptr(in_affine[1]), nl, warr, _ptr_array([l[0] for l in layers]),
-              _ptr_array([l[1] for l in layers]), _ptr_array([l[2] for l in layers]), _ptr(knots), grid_size, spline_order, mode,
-              _ptr_array(acts), _ptr_array(pfs), _ptr_array(pds), _ptr(mom[0]) if moments else None,
-              _ptr(mom[1]) if moments else None, _ptr(ws), ws.numel(), _stream())
-        return acts, pds, mom
-    _call("kagnn_gin_kan_layer_fwd", _ptr(xg), _lib.DTYPE_BF16 if xg.dtype == torch.bfloat16 else _lib.DTYPE_F32, _ld(xg), n,
-          _ptr(g.rowptr), _ptr(g.col), _ptr(g.hub_seg) if g.num_hub_seg else None, g.num_hub_seg, g.hub_threshold,
-          float(self_scale), nl, warr, _ptr_array([l[0] for l in layers]), _ptr_array([l[1] for l in layers]),
-          _ptr_array([l[2] for l in layers]), _ptr(knots), grid_size, spline_order, mode, _ptr_array(acts),
-          _ptr_array(pfs), _ptr_array(pds), _ptr(mom[0]) if moments else None, _ptr(mom[1]) if moments else None,
-          _ptr(ws), ws.numel(), _stream())
+    _call(name, *head, nl, warr, _ptr_array([l[0] for l in layers]), _ptr_array([l[1] for l in layers]),
+          _ptr_array([l[2] for l in layers]), _ptr(knots), grid_size, spline_order, mode, _ptr_array(acts), _ptr_array(pfs),
+          _ptr_array(pds), _ptr(mom[0]) if moments else None, _ptr(mom[1]) if moments else None, _ptr(ws), ws.numel(), _stream())
     return acts, pds, mom
+
+
+def _chain_saved(acts, layers, pds, knots, *extras):
+    """the tensors a chain node saves: per layer its input, spline weight, spline scaler and input-gradient pack; the knot
+    vector; then the node's own ``extras``"""
+    saved = []
+    for h, (_, sw, sc), pack_d in zip(acts, layers, pds):
+        saved += [h, sw, sc, pack_d]
+    return (*saved, knots, *extras)
+
+
+def _chain_unsaved(t, nl):
+    """``_chain_saved`` read back -> (acts, sws, scs, pds, knots, extras)"""
+    return t[0:4 * nl:4], t[1:4 * nl:4], t[2:4 * nl:4], t[3:4 * nl:4], t[4 * nl], t[4 * nl + 1:]
+
+
+def _chain_bwd_buffers(n, dev, widths, G, K, mode, hub_segs):
+    """-> (the gradients of base weight, spline weight and spline scaler per layer, the widths as int32[], the bytes of the
+    chain's backward workspace)"""
+    nl = len(widths) - 1
+    f32 = dict(dtype=torch.float32, device=dev)
+    gbw = [torch.empty((widths[i + 1], widths[i]), **f32) for i in range(nl)]
+    gsw = [torch.empty((widths[i + 1], widths[i], G + K), **f32) for i in range(nl)]
+    gsc = [torch.empty((widths[i + 1], widths[i]), **f32) for i in range(nl)]
+    warr = (ctypes.c_int32 * (nl + 1))(*widths)
+    _, wb = _sizes("kagnn_gin_kan_layer_workspace_bytes", n, nl, tuple(widths), G, K, mode, *hub_segs, outputs=2)
+    return gbw, gsw, gsc, warr, wb
+
+
+def _chain_bwd_result(fixed, lead, gbw, gsw, gsc):
+    """what a chain node's backward returns: ``lead`` for its first forward arguments, None for the rest of the ``fixed`` ones
+    (``_fixed_args``), then the parameter gradients in the order of ``*params``"""
+    return (*lead, *(None,) * (fixed - len(lead)), *[t for trio in zip(gbw, gsw, gsc) for t in trio])
+
+
+def _gin_chain_prepare(ctx, x, g, self_scale, grid_size, spline_order, mode, act_bf16, skip_gradient, params):
+    """Forward opening of the two GIN nodes -> (the rows the aggregation gathers, layers, widths); leaves ``ctx.meta`` and
+    ``ctx.skip_gradient`` for ``_gin_bwd_prepare``"""
+    layers, widths = _chain_layers(params)
+    xg = _rows(x, allow_bf16=True)
+    if xg.size(0) != g.num_nodes:            # (the library call indexes rowptr / x by this count)
+        raise ValueError(f"x has {xg.size(0)} rows but the graph has {g.num_nodes} nodes")
+    if act_bf16 and xg.dtype != torch.bfloat16 and _bf16_gather_width_ok(xg.size(1)):
+        xg = to_bf16_rows(xg)                # (rows the bf16 aggregation cannot take stay fp32 -- unrounded)
+    if xg.dtype == torch.bfloat16 and not _bf16_rows_ok(xg):
+        xg = xg.float()
+    ctx.meta = (g, self_scale, grid_size, spline_order, mode, act_bf16, len(layers), x.dtype, widths)
+    # a second gradient of x that another tape node (the skip-concat read-out) hands over outside the tape: this node's
+    # backward adds it inside the transposed aggregation's epilogue (SkipGradient)
+    ctx.skip_gradient = None
+    if (skip_gradient is not None and x.requires_grad and x.dtype == torch.float32 and xg.dtype == torch.float32
+            and not act_bf16):
+        skip_gradient.consumer = True
+        ctx.skip_gradient = skip_gradient
+    return xg, layers, widths
+
+
+def _take_skip_gradient(ctx, gy, fin):
+    """the gradient a ``SkipGradient`` holds for this node's input (as many rows as ``gy``, ``fin`` columns), or None"""
+    if ctx.skip_gradient is None:
+        return None
+    addend = ctx.skip_gradient.take()
+    if addend is not None:
+        addend = _rows(addend)
+        if addend.shape != (gy.size(0), fin) or not ctx.needs_input_grad[0]:
+            raise RuntimeError("SkipGradient: the gradient handed over does not belong to this convolution's input")
+    return addend
+
+
+def _gin_bwd_prepare(ctx, gy, addend, acts, sws, scs, pds, knots):
+    """Opening of the two GIN nodes' one-call backward -> (gx or None, gbw, gsw, gsc, the bytes of the chain's workspace, ``tail``:
+    the arguments ``kagnn_gin_kan_layer_bwd_add`` / ``_bwd_bn`` / ``_bwd_bn_sums`` share, from the row count to the last gradient
+    pointer).  ``gx`` has the input's dtype, or fp32 at widths the bf16 kernels do not take (``_gx_as_input`` converts it)."""
+    g, self_scale, G, K, mode, act_bf16, nl, x_dtype, widths = ctx.meta
+    n, dev = gy.size(0), gy.device
+    if n != g.num_nodes:
+        raise ValueError(f"the incoming gradient has {n} rows but the graph has {g.num_nodes} nodes")
+    gbw, gsw, gsc, warr, wb = _chain_bwd_buffers(n, dev, widths, G, K, mode, (g.num_hub_seg, g.num_hub_seg_t))
+    gx = torch.empty((n, widths[0]), dtype=x_dtype, device=dev) if ctx.needs_input_grad[0] else None
+    if gx is not None and x_dtype == torch.bfloat16 and not _bf16_rows_ok(gx):
+        gx = torch.empty((n, widths[0]), dtype=torch.float32, device=dev)      # widths the bf16 kernels do not take
+    tail = (n, _ptr(g.rowptr_t), _ptr(g.col_t), _ptr(g.hub_seg_t) if g.num_hub_seg_t else None, g.num_hub_seg_t, g.hub_threshold,
+            float(self_scale), nl, warr, _ptr_array(sws), _ptr_array(scs), _ptr(knots), G, K, mode, _ptr_array(acts), _ptr_array(pds),
+            _ptr(gx), _lib.DTYPE_BF16 if (gx is not None and gx.dtype == torch.bfloat16) else _lib.DTYPE_F32, widths[0],
+            int(bool(act_bf16) and _bf16_gather_width_ok(widths[0])), _ptr(addend), _ld(addend) if addend is not None else 0,
+            _ptr_array(gbw), _ptr_array(gsw), _ptr_array(gsc))
+    return gx, gbw, gsw, gsc, wb, tail
+
+
+def _gx_as_input(gx, x_dtype):
+    return gx if gx is None or gx.dtype == x_dtype else gx.to(x_dtype)
+
+
+def _gin_kan_layer_fwd_raw(xg, g, self_scale, knots, grid_size, spline_order, mode, layers, widths, moments, in_affine=None):
+    """``kagnn_gin_kan_layer_fwd``: -> (acts [h0, ..., y], input-gradient packs per layer, column moments of y or None)"""
+    n = xg.size(0)
+    graph = (n, _ptr(g.rowptr), _ptr(g.col), _ptr(g.hub_seg) if g.num_hub_seg else None, g.num_hub_seg, g.hub_threshold,
+             float(self_scale))
+    if in_affine is not None:          # the gathered rows are in_affine[0] * xg + in_affine[1]: a folded BatchNorm1d (AffineRows)
+        name, head = "kagnn_gin_kan_layer_fwd_affine", (_ptr(xg), _ld(xg), *graph, _ptr(in_affine[0]), _ptr(in_affine[1]))
+    else:
+        name, head = "kagnn_gin_kan_layer_fwd", (_ptr(xg), _lib.DTYPE_BF16 if xg.dtype == torch.bfloat16 else _lib.DTYPE_F32, _ld(xg), *graph)
+    return _chain_fwd_call(name, head, n, xg.device, layers, widths, knots, grid_size, spline_order, mode,
+                           (g.num_hub_seg, g.num_hub_seg_t), moments)
+
+
+def _gin_kan_layer_fwd_composed(xg, g, self_scale, knots, grid_size, spline_order, mode, layers, moments):
+    """``_gin_kan_layer_fwd_raw`` composed from the per-operation entry points (``KAGNN_LAYER_ABI=0``; ``knots``: per layer):
+    the same kernels, the same return"""
+    nl = len(layers)
+    acts, pds, mom = [_aggregate_raw(xg, g, False, self_scale, None, None, None, None, False)], [], None
+    packs = kan_pack_chain(layers, grid_size, spline_order, mode) if nl > 1 else None
+    for i, (bw, sw, sc) in enumerate(layers):
+        out = _kan_fwd_raw(acts[i], bw, sw, sc, knots[i], grid_size, spline_order, mode,
+                           None if packs is None else packs[i], None if packs is None else packs[i][2],
+                           moments=moments and i == nl - 1)
+        acts.append(out[0]); pds.append(out[1])
+        mom = out[2] if len(out) > 2 else mom
+    return acts, pds, mom
+
+
+def _gin_kan_layer_bwd_composed(ctx, gy, addend, acts, sws, scs, pds, knots):
+    """the backward of ``_GinKanLayerFn`` composed from the per-operation entry points -> (gx, gbw, gsw, gsc)"""
+    g, self_scale, G, K, mode, act_bf16, nl, x_dtype, widths = ctx.meta
+    need_x = ctx.needs_input_grad[0]
+    gbw, gsw, gsc = [None] * nl, [None] * nl, [None] * nl
+    for i in reversed(range(nl)):
+        fin, fout = widths[i], widths[i + 1]
+        if any(ctx.needs_input_grad[_GIN_FIXED + 3 * i:_GIN_FIXED + 3 * i + 3]):
+            gbw[i], gsw[i], gsc[i] = _kan_bwd_weight_raw(acts[i], gy, knots, sws[i], scs[i], fin, fout, G, K, mode, True)
+        if i > 0 or need_x:
+            bf16_out = (i == 0 and act_bf16 and split_like(mode) and K == 3 and G + K <= 8 and fout <= 128
+                        and _bf16_gather_width_ok(fin) and _fits32(acts[i], fout))     # the dX variant that stores bf16 rows
+            gy = _kan_bwd_input_raw(acts[i], gy, knots, pds[i], fin, fout, G, K, mode, bf16_out)
+    gx = _aggregate_raw(gy, g, True, self_scale, None, None, None, None, False, out_dtype=x_dtype, addend=addend) if need_x else None
+    return gx, gbw, gsw, gsc
 
 
 class AffineRows:
@@ -913,9 +1061,6 @@ class NormSums:
         return sums if same else None
 
 
-_FOLD_NORM_STATS = os.environ.get("KAGNN_FOLD_NORM_STATS", "1") != "0"
-
-
 class _MaterialiseAffineFn(Function):
     @staticmethod
     def forward(ctx, y, affine):
@@ -939,112 +1084,35 @@ class _GinKanLayerFn(Function):
     @_on_operand_device
     def forward(ctx, x, g, self_scale, knots, grid_size, spline_order, mode, act_bf16, moments, skip_gradient, *params):
         _need_cuda(x, *params)
-        nl = len(params) // 3
-        layers = [(params[3 * i].contiguous(), params[3 * i + 1].contiguous(), params[3 * i + 2].contiguous()) for i in range(nl)]
-        xg = _rows(x, allow_bf16=True)
-        if xg.size(0) != g.num_nodes:            # (the library call below indexes rowptr / x by this count)
-            raise ValueError(f"x has {xg.size(0)} rows but the graph has {g.num_nodes} nodes")
-        if act_bf16 and xg.dtype != torch.bfloat16 and xg.size(1) % 8 == 0 and xg.size(1) <= 512:
-            xg = to_bf16_rows(xg)                # (rows the bf16 aggregation cannot take stay fp32 -- unrounded)
-        if xg.dtype == torch.bfloat16 and not _bf16_rows_ok(xg):
-            xg = xg.float()
-        n, dev = xg.size(0), xg.device
-        widths = [layers[0][1].size(1)] + [sw.size(0) for _, sw, _ in layers]
-        ctx.meta = (g, self_scale, grid_size, spline_order, mode, act_bf16, nl, x.dtype, widths)
-        # a second gradient of x that another tape node (the skip-concat read-out) hands over outside the tape: this node's
-        # backward adds it inside the transposed aggregation's epilogue (SkipGradient)
-        ctx.skip_gradient = None
-        if (skip_gradient is not None and x.requires_grad and x.dtype == torch.float32 and xg.dtype == torch.float32
-                and not act_bf16):
-            skip_gradient.consumer = True
-            ctx.skip_gradient = skip_gradient
-        if not _LAYER_ABI:
-            h = _aggregate_raw(xg, g, False, self_scale, None, None, None, None, False)
-            packs = kan_pack_chain(layers, grid_size, spline_order, mode) if nl > 1 else None
-            saved = []
-            mom = None
-            for i, (bw, sw, sc) in enumerate(layers):
-                out = _kan_fwd_raw(h, bw, sw, sc, knots[i], grid_size, spline_order, mode,
-                                   None if packs is None else packs[i], None if packs is None else packs[i][2],
-                                   moments=moments and i == nl - 1)
-                y, pack_d = out[0], out[1]
-                mom = out[2] if len(out) > 2 else mom
-                saved += [h, sw, sc, pack_d]
-                h = y
-            ctx.save_for_backward(*saved, knots[0])
-            if moments:
-                ctx.mark_non_differentiable(mom)
-                return h, mom
-            return h
-        acts, pds, mom = _gin_kan_layer_fwd_raw(xg, g, self_scale, knots[0], grid_size, spline_order, mode, layers, widths, moments)
-        saved = []
-        for i in range(nl):
-            saved += [acts[i], layers[i][1], layers[i][2], pds[i]]
-        ctx.save_for_backward(*saved, knots[0])
+        xg, layers, widths = _gin_chain_prepare(ctx, x, g, self_scale, grid_size, spline_order, mode, act_bf16, skip_gradient, params)
+        if _LAYER_ABI:
+            acts, pds, mom = _gin_kan_layer_fwd_raw(xg, g, self_scale, knots[0], grid_size, spline_order, mode, layers, widths, moments)
+        else:
+            acts, pds, mom = _gin_kan_layer_fwd_composed(xg, g, self_scale, knots, grid_size, spline_order, mode, layers, moments)
+        ctx.save_for_backward(*_chain_saved(acts, layers, pds, knots[0]))
         if moments:
             ctx.mark_non_differentiable(mom)
-            return acts[nl], mom
-        return acts[nl]
+            return acts[-1], mom
+        return acts[-1]
 
     @staticmethod
     @once_differentiable
     @_on_operand_device
     def backward(ctx, gy, _g_moments=None):
         g, self_scale, G, K, mode, act_bf16, nl, x_dtype, widths = ctx.meta
-        t = ctx.saved_tensors
-        knots = t[4 * nl]
+        acts, sws, scs, pds, knots, _ = _chain_unsaved(ctx.saved_tensors, nl)
         gy = _rows(gy)
-        need_x = ctx.needs_input_grad[0]
-        gx_dtype = torch.bfloat16 if x_dtype == torch.bfloat16 else torch.float32
-        addend = None
-        if ctx.skip_gradient is not None:
-            addend = ctx.skip_gradient.take()
-            if addend is not None:
-                addend = _rows(addend)
-                if addend.shape != (gy.size(0), widths[0]) or not need_x:
-                    raise RuntimeError("SkipGradient: the gradient handed over does not belong to this convolution's input")
+        addend = _take_skip_gradient(ctx, gy, widths[0])
         if not _LAYER_ABI:
-            grads = [None] * (3 * nl)
-            for i in reversed(range(nl)):
-                h_in, sw, sc, pack_d = t[4 * i:4 * i + 4]
-                fin, fout = widths[i], widths[i + 1]
-                if any(ctx.needs_input_grad[10 + 3 * i:10 + 3 * i + 3]):
-                    grads[3 * i], grads[3 * i + 1], grads[3 * i + 2] = _kan_bwd_weight_raw(h_in, gy, knots, sw, sc, fin, fout,
-                                                                                           G, K, mode, True)
-                if i > 0 or need_x:
-                    bf16_out = (i == 0 and act_bf16 and split_like(mode) and K == 3 and G + K <= 8 and fout <= 128
-                                and fin % 8 == 0 and fin <= 512 and _fits32(h_in, fout))      # the dX variant that stores bf16 rows (<= 512: the bf16 aggregation's limit)
-                    gy = _kan_bwd_input_raw(h_in, gy, knots, pack_d, fin, fout, G, K, mode, bf16_out)
-            gx = _aggregate_raw(gy, g, True, self_scale, None, None, None, None, False, out_dtype=gx_dtype, addend=addend) if need_x else None
-            return (gx, None, None, None, None, None, None, None, None, None, *grads)
-        n, dev = gy.size(0), gy.device
-        if n != g.num_nodes:
-            raise ValueError(f"the incoming gradient has {n} rows but the graph has {g.num_nodes} nodes")
-        f32 = dict(dtype=torch.float32, device=dev)
-        acts = [t[4 * i] for i in range(nl)]
-        sws, scs, pds = [t[4 * i + 1] for i in range(nl)], [t[4 * i + 2] for i in range(nl)], [t[4 * i + 3] for i in range(nl)]
-        gbw = [torch.empty((widths[i + 1], widths[i]), **f32) for i in range(nl)]
-        gsw = [torch.empty((widths[i + 1], widths[i], G + K), **f32) for i in range(nl)]
-        gsc = [torch.empty((widths[i + 1], widths[i]), **f32) for i in range(nl)]
-        gx = torch.empty((n, widths[0]), dtype=gx_dtype, device=dev) if need_x else None
-        if gx is not None and gx_dtype == torch.bfloat16 and not _bf16_rows_ok(gx):
-            gx = torch.empty((n, widths[0]), **f32)                       # widths the bf16 kernels do not take
-        warr = (ctypes.c_int32 * (nl + 1))(*widths)
-        _, wb = _sizes("kagnn_gin_kan_layer_workspace_bytes", n, nl, tuple(widths), G, K, mode, g.num_hub_seg,
-                       g.num_hub_seg_t, outputs=2)
-        ws = _ws(wb, dev)
-        _call("kagnn_gin_kan_layer_bwd_add", _ptr(gy), _ld(gy), n, _ptr(g.rowptr_t), _ptr(g.col_t),
-              _ptr(g.hub_seg_t) if g.num_hub_seg_t else None, g.num_hub_seg_t, g.hub_threshold, float(self_scale), nl, warr,
-              _ptr_array(sws), _ptr_array(scs), _ptr(knots), G, K, mode, _ptr_array(acts), _ptr_array(pds), _ptr(gx),
-              _lib.DTYPE_BF16 if (gx is not None and gx.dtype == torch.bfloat16) else _lib.DTYPE_F32, widths[0],
-              int(bool(act_bf16) and widths[0] % 8 == 0 and widths[0] <= 512), _ptr(addend), _ld(addend) if addend is not None else 0,
-              _ptr_array(gbw), _ptr_array(gsw), _ptr_array(gsc), _ptr(ws), ws.numel(), _stream())
-        if gx is not None and gx.dtype != gx_dtype:
-            gx = gx.to(gx_dtype)
-        grads = []
-        for i in range(nl):
-            grads += [gbw[i], gsw[i], gsc[i]]
-        return (gx, None, None, None, None, None, None, None, None, None, *grads)
+            gx, gbw, gsw, gsc = _gin_kan_layer_bwd_composed(ctx, gy, addend, acts, sws, scs, pds, knots)
+            return _chain_bwd_result(_GIN_FIXED, (gx,), gbw, gsw, gsc)
+        gx, gbw, gsw, gsc, wb, tail = _gin_bwd_prepare(ctx, gy, addend, acts, sws, scs, pds, knots)
+        ws = _ws(wb, gy.device)
+        _call("kagnn_gin_kan_layer_bwd_add", _ptr(gy), _ld(gy), *tail, _ptr(ws), ws.numel(), _stream())
+        return _chain_bwd_result(_GIN_FIXED, (_gx_as_input(gx, x_dtype),), gbw, gsw, gsc)
+
+
+_GIN_FIXED = _fixed_args(_GinKanLayerFn)
 
 
 class _GinKanBnLayerFn(Function):
@@ -1057,34 +1125,19 @@ class _GinKanBnLayerFn(Function):
 
     @staticmethod
     @_on_operand_device
-    def forward(ctx, x, g, self_scale, knots, grid_size, spline_order, mode, act_bf16, skip_gradient, in_affine, lazy, in_stats, out_stats,
-                bn_weight, bn_bias, running_mean, running_var, momentum, eps, *params):
+    def forward(ctx, x, bn_weight, bn_bias, g, self_scale, knots, grid_size, spline_order, mode, act_bf16, skip_gradient, in_affine, lazy,
+                in_stats, out_stats, running_mean, running_var, momentum, eps, *params):
         """``in_affine``: the input is an ``AffineRows`` (``x`` = its y): the aggregation folds the previous layer's norm.
         ``lazy``: do not write the normalised rows -- return ``(y, affine)`` for an ``AffineRows`` (see its convention).
         ``in_stats`` / ``out_stats``: the ``NormSums`` of the input ``AffineRows`` / a fresh one for the output (lazy mode)."""
         _need_cuda(x, bn_weight, bn_bias, running_mean, running_var, in_affine, *params)
-        nl = len(params) // 3
-        layers = [(params[3 * i].contiguous(), params[3 * i + 1].contiguous(), params[3 * i + 2].contiguous()) for i in range(nl)]
-        xg = _rows(x, allow_bf16=True)
-        if xg.size(0) != g.num_nodes:
-            raise ValueError(f"x has {xg.size(0)} rows but the graph has {g.num_nodes} nodes")
-        if act_bf16 and xg.dtype != torch.bfloat16 and xg.size(1) % 8 == 0 and xg.size(1) <= 512:
-            xg = to_bf16_rows(xg)
-        if xg.dtype == torch.bfloat16 and not _bf16_rows_ok(xg):
-            xg = xg.float()
-        widths = [layers[0][1].size(1)] + [sw.size(0) for _, sw, _ in layers]
-        ctx.meta = (g, self_scale, grid_size, spline_order, mode, act_bf16, nl, x.dtype, widths)
-        ctx.skip_gradient = None
-        if (skip_gradient is not None and x.requires_grad and x.dtype == torch.float32 and xg.dtype == torch.float32
-                and not act_bf16):
-            skip_gradient.consumer = True
-            ctx.skip_gradient = skip_gradient
+        xg, layers, widths = _gin_chain_prepare(ctx, x, g, self_scale, grid_size, spline_order, mode, act_bf16, skip_gradient, params)
         acts, pds, mom = _gin_kan_layer_fwd_raw(xg, g, self_scale, knots[0], grid_size, spline_order, mode, layers, widths, True,
                                                 in_affine=in_affine)
-        y = acts[nl]
+        y = acts[-1]
         affine = None
         if lazy:
-            f = widths[nl]
+            f = widths[-1]
             mean = torch.empty(f, dtype=torch.float32, device=y.device)
             rstd = torch.empty(f, dtype=torch.float32, device=y.device)
             affine = torch.empty((2, f), dtype=torch.float32, device=y.device)
@@ -1092,9 +1145,6 @@ class _GinKanBnLayerFn(Function):
                   _ptr(running_mean), _ptr(running_var), float(momentum), float(eps), _ptr(mean), _ptr(rstd), _ptr(affine), _stream())
         else:
             h, mean, rstd = _batchnorm_fwd_raw(y, bn_weight, bn_bias, running_mean, running_var, True, momentum, eps, mom)
-        saved = []
-        for i in range(nl):
-            saved += [acts[i], layers[i][1], layers[i][2], pds[i]]
         # the norms' backward statistics travel with the gradients (NormSums): this node's own, and the previous norm's that
         # this node's transposed aggregation can produce -- fp32 rows of 17..256 columns (a multiple of 4), gradient wanted
         ctx.out_stats = ctx.in_stats = None
@@ -1107,7 +1157,7 @@ class _GinKanBnLayerFn(Function):
                 and x.data_ptr() % 16 == 0 and _ld(x) % 4 == 0):
             ctx.in_stats = in_stats
             extra = [x]                                   # x = the previous norm's input
-        ctx.save_for_backward(*saved, knots[0], y, mean, rstd, bn_weight, *extra)
+        ctx.save_for_backward(*_chain_saved(acts, layers, pds, knots[0], y, mean, rstd, bn_weight, *extra))
         ctx.has_bias = bn_bias is not None
         if lazy:
             ctx.mark_non_differentiable(affine)
@@ -1120,47 +1170,21 @@ class _GinKanBnLayerFn(Function):
     @_on_operand_device
     def backward(ctx, gh, _g_affine=None):
         g, self_scale, G, K, mode, act_bf16, nl, x_dtype, widths = ctx.meta
-        t = ctx.saved_tensors
-        knots, y, mean, rstd, bn_w = t[4 * nl:4 * nl + 5]
+        acts, sws, scs, pds, knots, (y, mean, rstd, bn_w, *norm_input) = _chain_unsaved(ctx.saved_tensors, nl)
         if gh is None:                                # (lazy mode does not materialise absent gradients: an unused output)
             gh = torch.zeros_like(y)
         gh_in = gh
         gh = _rows(gh)
-        need_x = ctx.needs_input_grad[0]
-        gx_dtype = torch.bfloat16 if x_dtype == torch.bfloat16 else torch.float32
-        addend = None
-        if ctx.skip_gradient is not None:
-            addend = ctx.skip_gradient.take()
-            if addend is not None:
-                addend = _rows(addend)
-                if addend.shape != (gh.size(0), widths[0]) or not need_x:
-                    raise RuntimeError("SkipGradient: the gradient handed over does not belong to this convolution's input")
+        addend = _take_skip_gradient(ctx, gh, widths[0])
+        gx, gbw, gsw, gsc, wb, tail = _gin_bwd_prepare(ctx, gh, addend, acts, sws, scs, pds, knots)
         n, dev = gh.size(0), gh.device
-        if n != g.num_nodes:
-            raise ValueError(f"the incoming gradient has {n} rows but the graph has {g.num_nodes} nodes")
         f32 = dict(dtype=torch.float32, device=dev)
-        acts = [t[4 * i] for i in range(nl)]
-        sws, scs, pds = [t[4 * i + 1] for i in range(nl)], [t[4 * i + 2] for i in range(nl)], [t[4 * i + 3] for i in range(nl)]
-        gbw = [torch.empty((widths[i + 1], widths[i]), **f32) for i in range(nl)]
-        gsw = [torch.empty((widths[i + 1], widths[i], G + K), **f32) for i in range(nl)]
-        gsc = [torch.empty((widths[i + 1], widths[i]), **f32) for i in range(nl)]
         gbn_w = torch.empty(widths[nl], **f32) if bn_w is not None else None
         gbn_b = torch.empty(widths[nl], **f32) if ctx.has_bias else None
-        gx = torch.empty((n, widths[0]), dtype=gx_dtype, device=dev) if need_x else None
-        if gx is not None and gx_dtype == torch.bfloat16 and not _bf16_rows_ok(gx):
-            gx = torch.empty((n, widths[0]), **f32)
-        warr = (ctypes.c_int32 * (nl + 1))(*widths)
-        _, wb = _sizes("kagnn_gin_kan_layer_workspace_bytes", n, nl, tuple(widths), G, K, mode, g.num_hub_seg,
-                       g.num_hub_seg_t, outputs=2)
         # statistics that came with the gradient (the next layer's aggregation made them for exactly this tensor), and the ones
         # this call makes for the previous norm
         my_sums = ctx.out_stats.take(gh_in) if ctx.out_stats is not None else None
         prev = ctx.in_stats if (ctx.in_stats is not None and gx is not None and gx.dtype == torch.float32) else None
-        tail = (n, _ptr(g.rowptr_t), _ptr(g.col_t), _ptr(g.hub_seg_t) if g.num_hub_seg_t else None, g.num_hub_seg_t, g.hub_threshold,
-                float(self_scale), nl, warr, _ptr_array(sws), _ptr_array(scs), _ptr(knots), G, K, mode, _ptr_array(acts), _ptr_array(pds),
-                _ptr(gx), _lib.DTYPE_BF16 if (gx is not None and gx.dtype == torch.bfloat16) else _lib.DTYPE_F32, widths[0],
-                int(bool(act_bf16) and widths[0] % 8 == 0 and widths[0] <= 512), _ptr(addend), _ld(addend) if addend is not None else 0,
-                _ptr_array(gbw), _ptr_array(gsw), _ptr_array(gsc))
         wbn = _sizes("kagnn_gin_kan_layer_bwd_bn_workspace_bytes", n, widths[nl])
         if my_sums is None and prev is None:
             ws = _ws(wb + wbn, dev)
@@ -1170,7 +1194,7 @@ class _GinKanBnLayerFn(Function):
             prev_sums = prev_y = None
             wst = 0
             if prev is not None:
-                prev_y = t[4 * nl + 5]
+                prev_y = norm_input[0]
                 prev_sums = torch.empty((2, widths[0]), **f32)
                 wst = _sizes("kagnn_gin_kan_layer_bwd_bn_sums_workspace_bytes", n, widths[0], g.num_hub_seg_t)
             ws = _ws(wb + wbn + wst, dev)
@@ -1180,12 +1204,10 @@ class _GinKanBnLayerFn(Function):
                   *tail, _ptr(ws), ws.numel(), _stream())
             if prev is not None:
                 prev.park(prev_sums, gx)
-        if gx is not None and gx.dtype != gx_dtype:
-            gx = gx.to(gx_dtype)
-        grads = []
-        for i in range(nl):
-            grads += [gbw[i], gsw[i], gsc[i]]
-        return (gx, None, None, None, None, None, None, None, None, None, None, None, None, gbn_w, gbn_b, None, None, None, None, *grads)
+        return _chain_bwd_result(_GIN_BN_FIXED, (_gx_as_input(gx, x_dtype), gbn_w, gbn_b), gbw, gsw, gsc)
+
+
+_GIN_BN_FIXED = _fixed_args(_GinKanBnLayerFn)
 
 
 _GRAPH_TASK_ID = getattr(torch._C, "_current_graph_task_id", None)
@@ -1240,6 +1262,29 @@ def _same_knots(layers, knots) -> bool:
     return hit
 
 
+def _chain_plan(layers):
+    """Can the fused convolution nodes run this chain of ``KANLinear`` layers as one library call?  ``None``, or ``(mode, one knot
+    vector per layer -- all equal --, the flat parameter list)``.  What ``gin_kan_layer`` and ``graph_ops.gine_kan_layer`` both
+    ask: one precision and one grid for all layers, at most 16 coefficients, the stand-alone spline scale, and -- the library
+    evaluates the whole chain on ONE knot vector -- uniform grids that ARE equal: layers with uniform but different grids (another
+    grid_range, update_grid with grid_eps = 1) must not be folded onto the first layer's."""
+    first = layers[0]
+    mode = first.precision if first.precision is not None else default_precision()
+    if any(l.precision != first.precision or l.grid_size != first.grid_size or l.spline_order != first.spline_order
+           or l.grid_size + l.spline_order > 16 or not l.enable_standalone_scale_spline for l in layers):
+        return None
+    knots = [l._knots() for l in layers]
+    if any(k.dim() != 1 or k.numel() != knots[0].numel() for k in knots) or not _same_knots(layers, knots):
+        return None
+    # (gin_kan_layer's condition: the split kernels' 32-bit addressing, see _fits32; gine_kan_layer takes split-like modes only)
+    if split_like(mode) and max(max(l.in_features, l.out_features) for l in layers) > 7680:
+        return None
+    params = []
+    for l in layers:
+        params += [l.base_weight, l.spline_weight, l.spline_scaler]
+    return mode, knots, params
+
+
 def gin_kan_layer(x, g: GraphIndex, self_scale: float, chain, act_dtype: Optional[torch.dtype] = None,
                   moments: bool = False, skip_gradient: Optional["SkipGradient"] = None, batch_norm=None,
                   in_affine: Optional[torch.Tensor] = None, lazy_norm: bool = False, in_stats: Optional["NormSums"] = None):
@@ -1251,23 +1296,12 @@ def gin_kan_layer(x, g: GraphIndex, self_scale: float, chain, act_dtype: Optiona
     convolution joins the node (``_GinKanBnLayerFn``: its element-wise backward runs inside the last input-gradient kernel)
     and the normalised rows are returned."""
     layers = list(chain.layers)
-    first = layers[0]
-    mode = first.precision if first.precision is not None else default_precision()
     act = default_activation_dtype() if act_dtype is None else act_dtype
-    if any(l.precision != first.precision or l.grid_size != first.grid_size or l.spline_order != first.spline_order
-           or l.grid_size + l.spline_order > 16 or not l.enable_standalone_scale_spline for l in layers):
+    plan = _chain_plan(layers)
+    if plan is None:
         return None
-    knots = [l._knots() for l in layers]
-    if any(k.dim() != 1 or k.numel() != knots[0].numel() for k in knots):
-        return None
-    if not _same_knots(layers, knots):
-        return None
-    width = max(max(l.in_features, l.out_features) for l in layers)
-    if split_like(mode) and width > 7680:
-        return None
-    params = []
-    for l in layers:
-        params += [l.base_weight, l.spline_weight, l.spline_scaler]
+    mode, knots, params = plan
+    first = layers[0]
     if batch_norm is not None:
         # (the library call keeps the norm's transformed rows in the chain's ping-pong gradient matrices, which are as wide as
         # the widest layer INPUT: a chain whose output is wider than every input stays on the two nodes)
@@ -1275,9 +1309,9 @@ def gin_kan_layer(x, g: GraphIndex, self_scale: float, chain, act_dtype: Optiona
             return None
         bw_, bb_, rm_, rv_, mom_, eps_ = batch_norm() if callable(batch_norm) else batch_norm      # (callable: evaluated only now that the node is certain -- the caller's per-call bookkeeping)
         out_stats = NormSums() if lazy_norm else None
-        out = _GinKanBnLayerFn.apply(x, g, float(self_scale), knots, first.grid_size, first.spline_order, int(mode),
+        out = _GinKanBnLayerFn.apply(x, bw_, bb_, g, float(self_scale), knots, first.grid_size, first.spline_order, int(mode),
                                      act == torch.bfloat16 or x.dtype == torch.bfloat16, skip_gradient, in_affine, bool(lazy_norm),
-                                     in_stats, out_stats, bw_, bb_, rm_, rv_, float(mom_), float(eps_), *params)
+                                     in_stats, out_stats, rm_, rv_, float(mom_), float(eps_), *params)
         return AffineRows(out[0], out[1], out_stats) if lazy_norm else out
     return _GinKanLayerFn.apply(x, g, float(self_scale), knots, first.grid_size, first.spline_order, int(mode),
                                 act == torch.bfloat16 or x.dtype == torch.bfloat16, bool(moments), skip_gradient, *params)
