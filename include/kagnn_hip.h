@@ -49,7 +49,7 @@ extern "C" {
 #define KAGNN_DTYPE_F32 0
 #define KAGNN_DTYPE_BF16 1
 
-int kagnn_version(void);          /* 262 = 261 - the fields edge_src, edge_dst, csr_flags of kagnn_kagin_model_t; 261 = 260 + kagnn_fastkan_fwd_stats_in_kernel; 260 = round 6: + the feature-sharded FastKAN entry points kagnn_fastkan_row_moments .. _shard_bwd_finish, + kagnn_kagin_model_*; 250 = 240 + KAGNN_PREC_HALF; 240 = 230 + kagnn_gin_kan_layer_bwd_bn_sums; 230 = 220 + the *_affine entry points of a folded BatchNorm1d; 220 = 210 + the stage timer) */
+int kagnn_version(void);          /* 263 = 262 + kagnn_batch_assemble; 262 = 261 - the fields edge_src, edge_dst, csr_flags of kagnn_kagin_model_t; 261 = 260 + kagnn_fastkan_fwd_stats_in_kernel; 260 = round 6: + the feature-sharded FastKAN entry points kagnn_fastkan_row_moments .. _shard_bwd_finish, + kagnn_kagin_model_*; 250 = 240 + KAGNN_PREC_HALF; 240 = 230 + kagnn_gin_kan_layer_bwd_bn_sums; 230 = 220 + the *_affine entry points of a folded BatchNorm1d; 220 = 210 + the stage timer) */
 const char* kagnn_last_error(void);
 
 /* Stage timer -- a measurement aid, off by default (no reference counterpart: the reference times whole epochs with
@@ -813,6 +813,51 @@ int kagnn_kagin_model_sizes(const kagnn_kagin_model_t* model, size_t* saved_byte
                             size_t* bwd_workspace_bytes_host, size_t* grads_floats_host);
 int kagnn_kagin_model_fwd(const kagnn_kagin_model_t* model, void* stream);
 int kagnn_kagin_model_bwd(const kagnn_kagin_model_t* model, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Mini-batch assembly from a DEVICE-RESIDENT dataset of disjoint graphs, one launch per batch.  Replaces, per training step,
+ * torch_geometric's DataLoader collation on the host + `data.to(device)` (reference graph_regression/optuna_zinc.py:59-66,
+ * graph_classification/graph_classification_utils.py:48-49,109-128) AND the per-batch kagnn_csr_build_small.
+ * The dataset is held as "one giant batch in dataset order": graph g owns nodes [node_ptr[g], node_ptr[g+1]) and edges
+ * [edge_ptr[g], edge_ptr[g+1]) of the flat arrays (edges grouped by graph, both endpoints inside their own graph -- the
+ * caller guarantees it), src_all / dst_all hold node ids in dataset order, and (rowptr_all, col_all, perm_all) /
+ * (rowptr_t_all, col_t_all, perm_t_all) are kagnn_csr_build's structures of the WHOLE dataset (by destination / by source; no
+ * hub segments are carried over).  A batch = the graphs ids[0..num_graphs) in that order (repeats allowed): per-graph slices of
+ * all of those arrays, concatenated, with node and edge offsets rebased.  A stable sort by destination never moves an edge
+ * across a graph boundary, so the assembled (rowptr, col, perm, rowptr_t, col_t, perm_t) equal what kagnn_csr_build_small makes
+ * from the assembled edge_index, bit for bit.
+ *   x_all / edge_attr_all / y_all: opaque rows of x_row_bytes / edge_attr_row_bytes / y_row_bytes bytes (multiples of 4, bases
+ *     4-byte aligned; copied with 16-byte accesses where row size and both bases allow, else 8 or 4); edge_attr_all, y_all may
+ *     be NULL (row size 0).  The dataset's N and E fit int32.
+ *   outputs (caller-allocated): x [num_nodes rows], edge_index [2, num_edges] int64, edge_attr [num_edges rows], y [num_graphs
+ *     rows], batch [num_nodes] int64, ptr [num_graphs + 1] int64; rowptr [num_nodes + 1], col, perm, rowptr_t, col_t, perm_t
+ *     int32 -- all six (then the dataset's six are required) or all NULL.
+ *   num_nodes / num_edges: the batch's totals, which the HOST knows from its copy of node_ptr / edge_ptr.  The kernel scans the
+ *     counts itself and verifies them: flags[0] = 1 when an id is outside [0, num_graphs_total), flags[1] = 1 when the scanned
+ *     totals differ from num_nodes / num_edges, else 0 -- `flags` is a DEVICE int32[2] the caller reads when convenient (no host
+ *     synchronisation here).  On a flagged input nothing is written outside the outputs and every index value written stays
+ *     inside the batch (clamped; rows past the scanned totals are empty), so kernels that consume the batch before the flags
+ *     are read cannot leave their buffers either; the contents are then meaningless.
+ * No workspace.  num_graphs <= KAGNN_BATCH_MAX_GRAPHS: every workgroup scans the batch's counts in LDS (int32 offsets, no
+ * pre-pass, no dependency between workgroups); a larger batch is refused with KAGNN_ERR_UNSUPPORTED.
+ * struct_bytes = sizeof(kagnn_batch_assemble_t) (checked: KAGNN_ERR_ARG on a mismatch).  All fields are 8 bytes wide.      */
+#define KAGNN_BATCH_MAX_GRAPHS 4096
+typedef struct kagnn_batch_assemble {
+    int64_t struct_bytes;
+    int64_t num_graphs_total, num_graphs, num_nodes, num_edges;            /* G of the dataset; B, N, E of this batch */
+    int64_t x_row_bytes, edge_attr_row_bytes, y_row_bytes;
+    const int64_t* node_ptr; const int64_t* edge_ptr;                      /* [G + 1] each */
+    const void* x_all; const void* edge_attr_all; const void* y_all;
+    const int64_t* src_all; const int64_t* dst_all;
+    const int32_t* rowptr_all; const int32_t* col_all; const int32_t* perm_all;
+    const int32_t* rowptr_t_all; const int32_t* col_t_all; const int32_t* perm_t_all;
+    const int64_t* ids;                                                    /* [B] */
+    void* x; int64_t* edge_index; void* edge_attr; void* y; int64_t* batch; int64_t* ptr;
+    int32_t* rowptr; int32_t* col; int32_t* perm; int32_t* rowptr_t; int32_t* col_t; int32_t* perm_t;
+    int32_t* flags;                                                        /* [2] */
+} kagnn_batch_assemble_t;
+int kagnn_batch_assemble_struct_bytes(void);                          /* sizeof(kagnn_batch_assemble_t): a binding checks its mirror */
+int kagnn_batch_assemble(const kagnn_batch_assemble_t* a, void* stream);
 
 #ifdef __cplusplus
 }

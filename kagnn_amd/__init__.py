@@ -14,5 +14,6 @@ from .norm import BatchNorm1d                                                   
 from .graph_models import (AtomEncoder, BondEncoder, FASTKAGAT, FASTKAGCN, FASTKAGCNRegression, FASTKAGIN, GINEKANLayer,   # noqa: F401
                            KAGAT, KAGCN, KAGCNRegression, KAGIN, KAGINRegression, FASTKAGINRegression,
                            KAGCN_Layer, KAGAT_Layer, FASTKAGCN_Layer, FASTKAGAT_Layer)
+from .data import DeviceBatch, DeviceBatchLoader, DeviceGraphDataset             # noqa: F401
 
 __version__ = "0.1.0"

@@ -141,6 +141,8 @@ _SIGNATURES = {
     "kagnn_kagin_model_sizes": (c_int32, [_P, POINTER(c_size_t), POINTER(c_size_t), POINTER(c_size_t), POINTER(c_size_t)]),
     "kagnn_kagin_model_fwd": (c_int32, [_P, _P]),
     "kagnn_kagin_model_bwd": (c_int32, [_P, _P]),
+    "kagnn_batch_assemble_struct_bytes": (c_int32, []),
+    "kagnn_batch_assemble": (c_int32, [_P, _P]),
     "kagnn_gat_att_grad_workspace_bytes": (c_int32, [c_int64, c_int32, c_int32, POINTER(c_size_t)]),
     "kagnn_gat_att_grad": (c_int32, [_P, c_int64, _P, _P, c_int64, c_int32, c_int32, _P, _P, _P, c_size_t, _P]),
     "kagnn_softmax_xent_workspace_bytes": (c_int32, [c_int64, POINTER(c_size_t)]),
@@ -199,6 +201,27 @@ class KaginModel(ctypes.Structure):
     ]
 
 
+BATCH_MAX_GRAPHS = 4096      # KAGNN_BATCH_MAX_GRAPHS
+
+
+class BatchAssemble(ctypes.Structure):
+    """mirror of ``kagnn_batch_assemble_t`` (include/kagnn_hip.h); ``load()`` checks its size against the library's"""
+    _fields_ = [
+        ("struct_bytes", c_int64),
+        ("num_graphs_total", c_int64), ("num_graphs", c_int64), ("num_nodes", c_int64), ("num_edges", c_int64),
+        ("x_row_bytes", c_int64), ("edge_attr_row_bytes", c_int64), ("y_row_bytes", c_int64),
+        ("node_ptr", c_void_p), ("edge_ptr", c_void_p),
+        ("x_all", c_void_p), ("edge_attr_all", c_void_p), ("y_all", c_void_p),
+        ("src_all", c_void_p), ("dst_all", c_void_p),
+        ("rowptr_all", c_void_p), ("col_all", c_void_p), ("perm_all", c_void_p),
+        ("rowptr_t_all", c_void_p), ("col_t_all", c_void_p), ("perm_t_all", c_void_p),
+        ("ids", c_void_p),
+        ("x", c_void_p), ("edge_index", c_void_p), ("edge_attr", c_void_p), ("y", c_void_p), ("batch", c_void_p), ("ptr", c_void_p),
+        ("rowptr", c_void_p), ("col", c_void_p), ("perm", c_void_p), ("rowptr_t", c_void_p), ("col_t", c_void_p), ("perm_t", c_void_p),
+        ("flags", c_void_p),
+    ]
+
+
 EXPORTED = tuple(_SIGNATURES)
 _lib = None
 
@@ -219,6 +242,9 @@ def load() -> ctypes.CDLL:
         if lib.kagnn_kagin_model_struct_bytes() != ctypes.sizeof(KaginModel):
             raise RuntimeError(f"kagnn_kagin_model_t is {lib.kagnn_kagin_model_struct_bytes()} bytes in {LIB_PATH}, its ctypes mirror "
                                f"{ctypes.sizeof(KaginModel)}: header and kagnn_amd/_lib.py disagree")
+        if lib.kagnn_batch_assemble_struct_bytes() != ctypes.sizeof(BatchAssemble):
+            raise RuntimeError(f"kagnn_batch_assemble_t is {lib.kagnn_batch_assemble_struct_bytes()} bytes in {LIB_PATH}, its ctypes mirror "
+                               f"{ctypes.sizeof(BatchAssemble)}: header and kagnn_amd/_lib.py disagree")
         _lib = lib
     return _lib
 

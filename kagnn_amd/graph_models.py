@@ -132,7 +132,7 @@ class KAGIN(_GraphLevel):
         self.dropout = nn.Dropout(dropout)
 
     def forward(self, data):
-        g = ops.graph_index(data.edge_index, data.x.size(0), cache=False)
+        g = ops.batch_graph_index(data, data.x.size(0))
         x = self._message_passing(data.x, g)
         return F.log_softmax(self.kan(self._pool(x, data)), dim=1)
 
@@ -149,7 +149,7 @@ class FASTKAGIN(_GraphLevel):
         self.dropout = nn.Dropout(dropout)
 
     def forward(self, data):
-        g = ops.graph_index(data.edge_index, data.x.size(0), cache=False)
+        g = ops.batch_graph_index(data, data.x.size(0))
         x = self._message_passing(data.x, g)
         return F.log_softmax(self.kan(self._pool(x, data)), dim=1)
 
@@ -211,7 +211,7 @@ class KAGINRegression(_GraphLevel):
             edge_attr = edge_attr.unsqueeze(1)
         x = self.atom_encoder(x)
         edge_attr = self.bond_encoder(edge_attr)
-        g = ops.graph_index(data.edge_index, x.size(0), cache=False)
+        g = ops.batch_graph_index(data, x.size(0))
         x = self._message_passing(x, g, edge_attr)
         return self.kan(self._pool(x, data))
 
@@ -257,7 +257,7 @@ class KAGCN(_ConvSiluStack):
         self.dropout = nn.Dropout(p=dropout)
 
     def forward(self, data):
-        x = self._stack(data.x, ops.graph_index(data.edge_index, data.x.size(0), cache=False))
+        x = self._stack(data.x, ops.batch_graph_index(data, data.x.size(0)))
         ptr = _segment_ptr(data)
         return F.log_softmax(self.readout(ops.segment_pool(x, ptr, mean=True)), dim=1)
 
@@ -275,7 +275,7 @@ class KAGAT(_ConvSiluStack):
         self.dropout = nn.Dropout(p=dropout)
 
     def forward(self, data):
-        x = self._stack(data.x, ops.graph_index(data.edge_index, data.x.size(0), cache=False))
+        x = self._stack(data.x, ops.batch_graph_index(data, data.x.size(0)))
         return F.log_softmax(self.readout(self._pool(x, data)), dim=1)
 
 
@@ -291,7 +291,7 @@ class FASTKAGCN(_ConvSiluStack):
         self.dropout = nn.Dropout(p=dropout)
 
     def forward(self, data):
-        x = self._stack(data.x, ops.graph_index(data.edge_index, data.x.size(0), cache=False))
+        x = self._stack(data.x, ops.batch_graph_index(data, data.x.size(0)))
         ptr = _segment_ptr(data)
         return F.log_softmax(self.readout(ops.segment_pool(x, ptr, mean=True)), dim=1)
 
@@ -309,7 +309,7 @@ class FASTKAGAT(_ConvSiluStack):
         self.dropout = nn.Dropout(p=dropout)
 
     def forward(self, data):
-        x = self._stack(data.x, ops.graph_index(data.edge_index, data.x.size(0), cache=False))
+        x = self._stack(data.x, ops.batch_graph_index(data, data.x.size(0)))
         return F.log_softmax(self.readout(self._pool(x, data)), dim=1)
 
 
@@ -329,7 +329,7 @@ class KAGCNRegression(_ConvSiluStack):
 
     def forward(self, data):
         x = self.atom_encoder(data.x)
-        x = self._stack(x, ops.graph_index(data.edge_index, x.size(0), cache=False))
+        x = self._stack(x, ops.batch_graph_index(data, x.size(0)))
         return self.readout(self._pool(x, data))
 
 
@@ -346,5 +346,5 @@ class FASTKAGCNRegression(_ConvSiluStack):
 
     def forward(self, data):
         x = self.atom_encoder(data.x)
-        x = self._stack(x, ops.graph_index(data.edge_index, x.size(0), cache=False))
+        x = self._stack(x, ops.batch_graph_index(data, x.size(0)))
         return self.readout(self._pool(x, data))

@@ -14,7 +14,7 @@ from torch.autograd.function import once_differentiable
 from .ops import (PREC_FP32, GraphIndex, _batchnorm_fwd_raw, _call, _chain_bwd_buffers, _chain_bwd_result, _chain_fwd_call,
                   _chain_layers, _chain_plan, _chain_saved, _chain_unsaved, _fits32, _fixed_args, _kan_bwd_input_raw,
                   _kan_bwd_weight_raw, _kan_fwd_raw, _ld, _need_cuda, _on_operand_device, _ptr, _ptr_array, _rows, _same_knots,
-                  _segment_broadcast_raw, _segment_pool_raw, _sizes, _stream, _weights_key, _ws, default_precision, graph_index,
+                  _segment_broadcast_raw, _segment_pool_raw, _sizes, _stream, _weights_key, _ws, batch_graph_index, default_precision,
                   kan_pack_chain, split_like)
 
 
@@ -623,7 +623,7 @@ def kagin_regression_forward(model, data):
     if ro[0].in_features != H:
         return None
     from .graph_models import _segment_ptr
-    g = graph_index(data.edge_index, x.size(0), cache=False)
+    g = batch_graph_index(data, x.size(0))
     seg = _segment_ptr(data)
     sparams, scales, running, momentum, eps = _gine_stack_args(convs, bns)
     plan = _ModelPlan()

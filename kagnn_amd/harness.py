@@ -254,7 +254,9 @@ def train_graph_batches(model, batches, nb_epochs: int = 1, warmup: int = 0, lr:
                         loss_fn=None):
     """The mini-batch training loop of the reference's graph-regression scripts (``graph_regression/optuna_zinc.py:56-66``: Adam,
     L1 loss, ``{zero_grad, loss(model(data).squeeze(), data.y), backward, step}`` per batch) over ``batches`` -- objects with
-    ``x, edge_index, edge_attr, batch, y`` (``num_graphs`` / ``ptr`` when the loader supplies them) already on the device.
+    ``x, edge_index, edge_attr, batch, y`` (``num_graphs`` / ``ptr`` when the loader supplies them) already on the device: a list
+    of premade batches, or any re-iterable with ``len()`` such as ``kagnn_amd.data.DeviceBatchLoader``, which assembles a fresh
+    (reshuffled) batch per step on the device and hands the model its CSR index with it.
     Returns ``(seconds per step, mean training loss per epoch)``.  Differences from the script, none of them in the mathematics:
     * the optimiser is ``kagnn_amd.harness.Adam`` unless one is passed (torch.optim.Adam's rule in fp32 as one library call;
       torch's own kernels round differently -- its fused one mixes double arithmetic -- so trajectories agree to rounding, not
@@ -327,6 +329,28 @@ def train_graph_batches(model, batches, nb_epochs: int = 1, warmup: int = 0, lr:
     finally:
         torch.autograd.set_multithreading_enabled(mt_was)
     return float(dt), [float(m) for m in means]
+
+
+def evaluate_graph_batches(model, batches, loss_fn=None) -> float:
+    """The evaluation loop of the same scripts (``graph_regression/optuna_zinc.py:68-73``: ``model.eval()``, no gradients,
+    ``total += loss(model(data).squeeze(), data.y).item() * data.num_graphs``, divided by the number of graphs): the mean loss per
+    graph over ``batches`` (as for ``train_graph_batches``).  The per-batch losses stay on the device and are read back ONCE; the
+    deferred graph checks of the loop are flushed before that.  Leaves the model in evaluation mode, as the scripts do."""
+    from . import ops as ops_mod
+    if loss_fn is None:
+        loss_fn = ops_mod.l1_loss
+    model.eval()
+    losses, weights = [], []
+    with torch.no_grad():
+        for data in batches:
+            losses.append(loss_fn(model(data).squeeze(), data.y.squeeze()).detach())
+            weights.append(float(int(getattr(data, "num_graphs", 0) or data.y.size(0))))
+    if any(p.is_cuda for p in model.parameters()):
+        ops_mod.flush_graph_checks()
+    if not losses:
+        return 0.0
+    w = torch.tensor(weights, dtype=losses[0].dtype).to(losses[0].device, non_blocking=True)
+    return float((torch.stack(losses) * w).sum() / max(sum(weights), 1.0))
 
 
 def count_params(model) -> int:

@@ -278,6 +278,20 @@ class GraphIndex:
               _ptr(self.rowptr_t), _ptr(self.col_t), _ptr(self.perm_t), _ptr(flags), _ptr(ws), ws.numel(), _stream())
         self._flags = _defer_flag_check(flags)
 
+    @classmethod
+    def from_arrays(cls, rowptr, col, perm, rowptr_t, col_t, perm_t, num_nodes: int, num_edges: int) -> "GraphIndex":
+        """A GraphIndex around six int32 device arrays that already ARE the two structures (``kagnn_batch_assemble``: slices of a
+        dataset's CSR -- ``kagnn_amd.data``).  Nothing is launched and nothing is validated here: no hub segments (as on the
+        small-graph path) and no pending flags -- whoever made the arrays vouches for them."""
+        g = cls.__new__(cls)
+        g.num_nodes, g.num_edges, g.hub_threshold, g.device = int(num_nodes), int(num_edges), HUB_THRESHOLD, rowptr.device
+        g.rowptr, g.col, g.perm, g.rowptr_t, g.col_t, g.perm_t = rowptr, col, perm, rowptr_t, col_t, perm_t
+        g.hub_seg = g.hub_seg_t = _no_hub_segments(rowptr.device)
+        g.num_hub_seg = g.num_hub_seg_t = 0
+        g._flags = None
+        g._dis = None
+        return g
+
     def validate(self, wait: bool = True) -> None:
         """raise if the edge list named node ids outside [0, num_nodes) (small-graph path; the rocPRIM path has already raised)"""
         if self._flags is not None:
@@ -316,16 +330,31 @@ class GraphIndex:
         return self.rowptr, self.col, self.perm, self.hub_seg, self.num_hub_seg
 
 
-def _defer_flag_check(flags: torch.Tensor):
+_NO_HUB: "dict[int, torch.Tensor]" = {}
+
+
+def _no_hub_segments(dev) -> torch.Tensor:
+    """the empty hub-segment list of an index that has none, one per device (``from_arrays`` runs once per mini-batch)"""
+    t = _NO_HUB.get(dev.index)
+    if t is None:
+        t = _NO_HUB[dev.index] = torch.empty(0, dtype=torch.int32, device=dev)
+    return t
+
+
+_CSR_FLAG_MESSAGE = "kagnn_csr_build_small: edge_index holds node ids outside [0, num_nodes)"
+
+
+def _defer_flag_check(flags: torch.Tensor, message: str = _CSR_FLAG_MESSAGE):
     """the out-of-range-id flags of a small-graph CSR build (2 ints on the device) travel to pinned host memory behind the launches
     queued so far; the entry joins ``_pending_checks`` and is looked at -- without waiting -- when a later small graph is indexed, or
-    by ``flush_graph_checks()`` / ``GraphIndex.validate()``"""
+    by ``flush_graph_checks()`` / ``GraphIndex.validate()``.  ``message``: what a raised flag means (the two flags of
+    ``kagnn_batch_assemble`` travel the same way)"""
     dev = flags.device
-    host = torch.empty(2, dtype=torch.int32, pin_memory=True)
+    host = torch.empty(flags.shape, dtype=torch.int32, pin_memory=True)       # (2 ints; [batches, 2] for a loader's epoch)
     host.copy_(flags, non_blocking=True)
     ev = torch.cuda.Event()
     ev.record(torch.cuda.current_stream(dev))
-    entry = [host, ev, flags, False]
+    entry = [host, ev, flags, False, message]
     _pending_checks.setdefault(dev.index, []).append(entry)
     return entry
 
@@ -343,8 +372,8 @@ def _check_flags(entry, wait: bool) -> bool:
         return False
     ev.synchronize()
     entry[3] = True
-    if int(host[0]) or int(host[1]):
-        raise RuntimeError("kagnn_csr_build_small: edge_index holds node ids outside [0, num_nodes)")
+    if (int(host[0]) or int(host[1])) if host.dim() == 1 else bool(host.any()):
+        raise RuntimeError(entry[4])
     return True
 
 
@@ -352,16 +381,25 @@ def _validate_pending(dev) -> None:
     """the deferred range checks of earlier small graphs on this device whose flags have arrived (never waits)"""
     lst = _pending_checks.get(dev.index)
     if lst:
-        keep, bad = [], False
+        keep, bad = [], []
         for en in lst:
             try:
                 if not _check_flags(en, False):
                     keep.append(en)
             except RuntimeError:
-                bad = True
+                bad.append(en[4])
         _pending_checks[dev.index] = keep
         if bad:
-            raise RuntimeError("kagnn_csr_build_small: an edge_index indexed earlier held node ids outside [0, num_nodes)")
+            raise RuntimeError(_earlier_failures(bad))
+
+
+def _earlier_failures(messages) -> str:
+    out = []
+    for m in messages:
+        m = "kagnn_csr_build_small: an edge_index indexed earlier held node ids outside [0, num_nodes)" if m == _CSR_FLAG_MESSAGE else m
+        if m not in out:
+            out.append(m)
+    return "; ".join(out)
 
 
 def flush_graph_checks(device=None) -> None:
@@ -371,16 +409,16 @@ def flush_graph_checks(device=None) -> None:
     before reading outputs back on the host (the last batch of a loop, or a single inference call, was never
     validated).  ``harness.train_graph_batches`` does so at the end of every epoch."""
     devs = list(_pending_checks) if device is None else [torch.device(device).index]
-    bad = False
+    bad = []
     for d in devs:
         for en in _pending_checks.get(d) or []:
             try:
                 _check_flags(en, True)
             except RuntimeError:
-                bad = True
+                bad.append(en[4])
         _pending_checks[d] = []
     if bad:
-        raise RuntimeError("kagnn_csr_build_small: an edge_index indexed earlier held node ids outside [0, num_nodes)")
+        raise RuntimeError(_earlier_failures(bad))
 
 
 _graph_cache: "dict[tuple, GraphIndex]" = {}
@@ -401,6 +439,18 @@ def graph_index(edge_index: torch.Tensor, num_nodes: int, cache: bool = True) ->
         g._keepalive = edge_index     # the key holds a raw pointer: pin the tensor it names
         _graph_cache[key] = g
     return g
+
+
+def batch_graph_index(data, num_nodes: int) -> GraphIndex:
+    """The index of a mini-batch object of the graph-level models: ``data.graph_index`` when the loader assembled one with the batch
+    (``kagnn_amd.data.DeviceBatchLoader``: slices of the dataset's CSR, the same bits as a build from ``data.edge_index``) and it
+    describes this ``edge_index``; else built from ``data.edge_index`` as for any other batch object (never cached: mini-batches
+    do not repeat)."""
+    g = getattr(data, "graph_index", None)
+    ei = data.edge_index
+    if isinstance(g, GraphIndex) and g.num_nodes == int(num_nodes) and g.num_edges == int(ei.size(1)) and g.device == ei.device:
+        return g
+    return graph_index(ei, num_nodes, cache=False)
 
 
 def clear_graph_cache() -> None:
