@@ -49,7 +49,7 @@ extern "C" {
 #define KAGNN_DTYPE_F32 0
 #define KAGNN_DTYPE_BF16 1
 
-int kagnn_version(void);          /* 263 = 262 + kagnn_batch_assemble; 262 = 261 - the fields edge_src, edge_dst, csr_flags of kagnn_kagin_model_t; 261 = 260 + kagnn_fastkan_fwd_stats_in_kernel; 260 = round 6: + the feature-sharded FastKAN entry points kagnn_fastkan_row_moments .. _shard_bwd_finish, + kagnn_kagin_model_*; 250 = 240 + KAGNN_PREC_HALF; 240 = 230 + kagnn_gin_kan_layer_bwd_bn_sums; 230 = 220 + the *_affine entry points of a folded BatchNorm1d; 220 = 210 + the stage timer) */
+int kagnn_version(void);          /* 264 = 263 + kagnn_degree_one_hot, kagnn_nll_loss_fwd / _bwd; 263 = 262 + kagnn_batch_assemble; 262 = 261 - the fields edge_src, edge_dst, csr_flags of kagnn_kagin_model_t; 261 = 260 + kagnn_fastkan_fwd_stats_in_kernel; 260 = round 6: + the feature-sharded FastKAN entry points kagnn_fastkan_row_moments .. _shard_bwd_finish, + kagnn_kagin_model_*; 250 = 240 + KAGNN_PREC_HALF; 240 = 230 + kagnn_gin_kan_layer_bwd_bn_sums; 230 = 220 + the *_affine entry points of a folded BatchNorm1d; 220 = 210 + the stage timer) */
 const char* kagnn_last_error(void);
 
 /* Stage timer -- a measurement aid, off by default (no reference counterpart: the reference times whole epochs with
@@ -693,6 +693,33 @@ int kagnn_softmax_xent_bwd(const float* logits, int64_t ld, int64_t num_rows, in
  * loss / g_loss: device scalars; one launch each way, deterministic (fixed summation order), no host sync. */
 int kagnn_l1_loss_fwd(const float* pred, const float* target, int64_t n, float* loss, void* stream);
 int kagnn_l1_loss_bwd(const float* pred, const float* target, int64_t n, const float* g_loss, float* g_pred, void* stream);
+
+/* What the graph-classification scripts wrap around their models (graph_classification/graph_classification_utils.py).
+ *
+ * Degree (:31-36), the node features of the unlabeled TU datasets: x = one_hot(clip(degree(edge_index[0]), 0, K - 1), K).float().
+ *   rowptr_by_source [num_nodes + 1]: the offsets of the CSR grouped by SOURCE node (rowptr_t of kagnn_csr_build_small); NULL = a
+ *   dataset without edges (every row gets its 1 in column 0).  x [num_nodes, num_classes] fp32, row stride ldx >= num_classes;
+ *   every element of every row is written (no memset needed), no atomics. */
+int kagnn_degree_one_hot(const int32_t* rowptr_by_source, int64_t num_nodes, int32_t num_classes, float* x, int64_t ldx, void* stream);
+
+/* train / val / test (:45-72): F.nll_loss(logp, y) of a mini-batch, reduction 'mean' and 'sum' from the same launch, and the
+ * arg-max accuracy count.  logp [rows, classes] fp32 log-probabilities (row stride ld), y [rows] int64.  ONE launch of ONE
+ * workgroup (rows <= KAGNN_BATCH_MAX_GRAPHS is the intended size; more rows work at one workgroup's pace).  The sum of
+ * -logp[r, y[r]] is taken in fp64 in a fixed order; loss_mean = sum / rows and loss_sum = sum are each rounded once to fp32
+ * (either may be NULL; rows == 0: NaN and 0).  accum, when not NULL, is an 8-byte aligned device record
+ *   { double nll_sum; int64_t correct; int64_t graphs; }
+ * to which the launch ADDS sum, the number of rows whose arg-max over the row equals y[r] (ties: the LOWEST class index; a row
+ * holding a NaN is never correct) and rows -- with plain loads and stores: launches on one stream are ordered, so no atomics and
+ * the same bits every run.  A label outside [0, classes): loss_mean, loss_sum (and nll_sum) are NaN, *flag is set to 1 (the launch
+ * never clears it), the row counts as wrong.  No host synchronisation.
+ * Backward: g_logp [rows, classes] (row stride ldg) is written whole: -(g_loss / rows) for KAGNN_REDUCTION_MEAN or -g_loss for
+ * KAGNN_REDUCTION_SUM at the label, exactly 0 elsewhere; rows with a label outside [0, classes) are all zero. */
+#define KAGNN_REDUCTION_MEAN 0
+#define KAGNN_REDUCTION_SUM 1
+int kagnn_nll_loss_fwd(const float* logp, int64_t ld, int64_t rows, int32_t classes, const int64_t* y, float* loss_mean,
+                       float* loss_sum, void* accum, int32_t* flag, void* stream);
+int kagnn_nll_loss_bwd(const int64_t* y, int64_t rows, int32_t classes, const float* g_loss, int32_t reduction, float* g_logp,
+                       int64_t ldg, void* stream);
 
 /* Optimiser of the same scripts (optuna_zinc.py:49,62: torch.optim.Adam(model.parameters(), lr), optimizer.step() per batch): one
  * update of `count` fp32 tensors in one launch per 32 tensors.  HOST arrays of device pointers / element counts; `step` = 1, 2, ...

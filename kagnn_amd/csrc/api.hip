@@ -98,6 +98,10 @@ int xent_fwd(const float*, long, long, int, const long*, const unsigned char*, i
 int xent_bwd(const float*, long, long, int, const long*, const unsigned char*, int, const float*, const float*, const float*, float*, long, hipStream_t);
 int l1_loss_fwd(const float* p, const float* t, long n, float* loss, hipStream_t st);
 int l1_loss_bwd(const float* p, const float* t, long n, const float* g_loss, float* g_p, hipStream_t st);
+int degree_one_hot(const int* rowptr, long N, int K, float* x, long ldx, hipStream_t st);
+int nll_loss_fwd(const float* logp, long ld, long rows, int C, const long* y, float* loss_mean, float* loss_sum, void* accum,
+                 int* flag, hipStream_t st);
+int nll_loss_bwd(const long* y, long rows, int C, const float* g_loss, int reduction, float* g_logp, long ldg, hipStream_t st);
 int adam_step(int count, float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
               const long* numel, float lr, float beta1, float beta2, float eps, float weight_decay, long step, hipStream_t st);
 size_t gat_att_grad_ws_bytes(long N, int H, int C);
@@ -201,7 +205,7 @@ static bool use_split_dw(int in, int out, int G, int K, int mode) { return mode 
 #pragma GCC visibility push(default)
 extern "C" {
 
-int kagnn_version(void) { return 263; }
+int kagnn_version(void) { return 264; }
 const char* kagnn_last_error(void) { return g_err; }
 
 int kagnn_stage_timer_enable(const char* only) {
@@ -996,6 +1000,32 @@ int kagnn_l1_loss_bwd(const float* pred, const float* target, int64_t n, const f
     KAGNN_STAGE(stream);
     KAGNN_CHECK_ARG(n >= 0 && (n == 0 || (pred && target && g_loss && g_pred)), "null array or negative size");
     return l1_loss_bwd(pred, target, n, g_loss, g_pred, as_stream(stream));
+}
+
+// the graph-classification scripts' node features, loss and accuracy bookkeeping (classify.hip)
+int kagnn_degree_one_hot(const int32_t* rowptr_by_source, int64_t num_nodes, int32_t num_classes, float* x, int64_t ldx, void* stream) {
+    KAGNN_STAGE(stream);
+    KAGNN_CHECK_ARG(num_nodes >= 0 && num_nodes < 2147483647LL && num_classes >= 1 && ldx >= num_classes, "bad shape");
+    KAGNN_CHECK_ARG(num_nodes == 0 || x, "null array");
+    return degree_one_hot(rowptr_by_source, num_nodes, num_classes, x, ldx, as_stream(stream));
+}
+
+int kagnn_nll_loss_fwd(const float* logp, int64_t ld, int64_t rows, int32_t classes, const int64_t* y, float* loss_mean,
+                       float* loss_sum, void* accum, int32_t* flag, void* stream) {
+    KAGNN_STAGE(stream);
+    KAGNN_CHECK_ARG(rows >= 0 && classes >= 1 && ld >= classes, "bad shape");
+    KAGNN_CHECK_ARG((loss_mean || loss_sum || accum) && flag && (rows == 0 || (logp && y)), "null array");
+    KAGNN_CHECK_ARG(((uintptr_t)accum & 7) == 0, "the record must be 8-byte aligned");
+    return nll_loss_fwd(logp, ld, rows, classes, (const long*)y, loss_mean, loss_sum, accum, flag, as_stream(stream));
+}
+
+int kagnn_nll_loss_bwd(const int64_t* y, int64_t rows, int32_t classes, const float* g_loss, int32_t reduction, float* g_logp,
+                       int64_t ldg, void* stream) {
+    KAGNN_STAGE(stream);
+    KAGNN_CHECK_ARG(rows >= 0 && classes >= 1 && ldg >= classes, "bad shape");
+    KAGNN_CHECK_ARG(reduction == KAGNN_REDUCTION_MEAN || reduction == KAGNN_REDUCTION_SUM, "reduction must be KAGNN_REDUCTION_MEAN or _SUM");
+    KAGNN_CHECK_ARG(rows == 0 || (y && g_loss && g_logp), "null array");
+    return nll_loss_bwd((const long*)y, rows, classes, g_loss, reduction, g_logp, ldg, as_stream(stream));
 }
 
 // one Adam update of `count` fp32 parameter tensors (HOST arrays of device pointers and element counts; step = 1, 2, ...: the

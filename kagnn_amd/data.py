@@ -56,6 +56,40 @@ def batch_plan(node_ptr: torch.Tensor, edge_ptr: torch.Tensor, ids: torch.Tensor
     return starts.tolist(), (ends - starts).tolist(), (cn[ends] - cn[starts]).tolist(), (ce[ends] - ce[starts]).tolist()
 
 
+def read_splits(path):
+    """The reference's 10-fold split files (``graph_classification/data_splits/<dataset>_splits.json``, read at
+    ``graph_classification_utils.py:88-91`` and used at ``:103-124``): ONE line of JSON,
+    ``[{"test": [...], "model_selection": [{"train": [...], "validation": [...]}]}, ...]``.  Returns one ``(train, validation, test)``
+    triple of int64 index tensors per fold -- ``dataset[train]`` etc. are the reference's ``dataset[train_index]`` views.  Like the
+    reference, the LAST non-empty line of the file counts and the first ``model_selection`` entry of a fold is the one used.  Host only."""
+    import json
+    splits = None
+    with open(path, "rt") as f:
+        for line in f:
+            if line.strip():
+                try:
+                    splits = json.loads(line)
+                except ValueError as ex:
+                    raise ValueError(f"{path}: not a split file (one line of JSON, a list of folds): {ex}") from None
+
+    def ids(fold, value, what):
+        if not isinstance(value, list) or not all(isinstance(i, int) and not isinstance(i, bool) and i >= 0 for i in value):
+            raise ValueError(f"{path}: fold {fold}: '{what}' must be a list of non-negative graph indices")
+        return torch.tensor(value, dtype=torch.int64)
+
+    if not isinstance(splits, list) or not splits:
+        raise ValueError(f"{path}: not a split file: expected a non-empty JSON list of folds "
+                         '[{"test": [...], "model_selection": [{"train": [...], "validation": [...]}]}, ...]')
+    out = []
+    for k, fold in enumerate(splits):
+        sel = fold.get("model_selection") if isinstance(fold, dict) else None
+        if not isinstance(fold, dict) or "test" not in fold or not isinstance(sel, list) or not sel or not isinstance(sel[0], dict) \
+                or "train" not in sel[0] or "validation" not in sel[0]:
+            raise ValueError(f"{path}: fold {k} is not {{'test': [...], 'model_selection': [{{'train': [...], 'validation': [...]}}]}}")
+        out.append((ids(k, sel[0]["train"], "train"), ids(k, sel[0]["validation"], "validation"), ids(k, fold["test"], "test")))
+    return out
+
+
 def _normalise_index(index, n: int) -> torch.Tensor:
     """``index`` (slice, list, int64 / bool tensor, anything ``torch.as_tensor`` takes) as int64 positions in [0, n)"""
     if isinstance(index, slice):
@@ -94,16 +128,24 @@ class DeviceGraphDataset:
     the whole dataset once (both CSR structures; no hub segments, as for any mini-batch of small graphs).
     ``ds[list / tensor / slice]`` is a subset VIEW on the same storage (the reference's ``dataset[train_index]``)."""
 
-    def __init__(self, x, edge_index, node_ptr, edge_ptr=None, edge_attr=None, y=None, device="cuda"):
+    def __init__(self, x, edge_index, node_ptr, edge_ptr=None, edge_attr=None, y=None, device="cuda", degree_features=None):
         device = torch.device(device)
         if device.type != "cuda":
             raise RuntimeError("kagnn_amd.data.DeviceGraphDataset keeps the dataset on an MI355X and assembles mini-batches there "
                                f"(libkagnn_hip.so); got device '{device}'. There is no CPU fallback in this package.")
-        x, edge_index = torch.as_tensor(x), torch.as_tensor(edge_index)
+        if (x is None) == (degree_features is None):
+            raise ValueError("give node features x, or x=None with degree_features=K (one-hot out-degree features, the reference's "
+                             "Degree transform for datasets without node features: K = 36)")
+        if degree_features is not None and int(degree_features) < 1:
+            raise ValueError("degree_features must be a positive number of classes")
+        if x is not None:
+            x = torch.as_tensor(x)
+        edge_index = torch.as_tensor(edge_index)
         node_ptr = torch.as_tensor(node_ptr).detach().cpu().to(torch.int64).reshape(-1)
         if edge_index.dim() != 2 or edge_index.size(0) != 2 or edge_index.dtype != torch.int64:
             raise ValueError("edge_index must be an int64 tensor of shape [2, E]")
-        G, N, E = node_ptr.numel() - 1, int(x.size(0)), int(edge_index.size(1))
+        G, E = node_ptr.numel() - 1, int(edge_index.size(1))
+        N = int(x.size(0)) if x is not None else (int(node_ptr[-1]) if node_ptr.numel() else 0)
         if G < 1 or int(node_ptr[0]) != 0 or int(node_ptr[-1]) != N or bool((node_ptr[1:] < node_ptr[:-1]).any()):
             raise ValueError("node_ptr must be non-decreasing offsets [G + 1] from 0 to the number of nodes, G >= 1")
         if N >= 2 ** 31 - 1 or E >= 2 ** 31 - 1:
@@ -125,8 +167,9 @@ class DeviceGraphDataset:
         st = _Storage()
         st.device, st.num_graphs, st.num_nodes, st.num_edges = device, G, N, E
         st.node_ptr_cpu, st.edge_ptr_cpu = node_ptr, derived
-        st.x = x.detach().contiguous().to(device)
-        st.x_row_bytes = _row_bytes(x)
+        if x is not None:
+            st.x = x.detach().contiguous().to(device)
+            st.x_row_bytes = _row_bytes(x)
         st.edge_attr, st.edge_attr_row_bytes = None, 0
         if edge_attr is not None:
             edge_attr = torch.as_tensor(edge_attr)
@@ -148,24 +191,39 @@ class DeviceGraphDataset:
         st.node_ptr, st.edge_ptr = node_ptr.to(device), derived.to(device)
         # both structures of the whole dataset, once; the hub threshold is out of reach: a mini-batch's index carries no hub segments
         st.index = ops.GraphIndex(eid, N, hub_threshold=2 ** 31 - 1) if E else None
+        if x is None:
+            # the reference's Degree transform, once, from the dataset's own by-source offsets (kagnn_degree_one_hot)
+            st.x = ops._degree_one_hot_raw(None if st.index is None else st.index.rowptr_t, N, int(degree_features), device)
+            st.x_row_bytes = 4 * int(degree_features)
         self._store = st
         self._index = None                      # None = the whole dataset, else int64 graph ids (CPU) of this view
 
     @classmethod
-    def from_graphs(cls, graphs: Iterable, device="cuda") -> "DeviceGraphDataset":
+    def from_graphs(cls, graphs: Iterable, device="cuda", degree_features=None) -> "DeviceGraphDataset":
         """from per-graph objects with ``x``, ``edge_index`` (LOCAL node ids), optionally ``edge_attr`` and ``y`` (one target row per
-        graph) -- duck-typed: torch_geometric ``Data`` objects work"""
+        graph) -- duck-typed: torch_geometric ``Data`` objects work.  ``degree_features=K``: the graphs' ``x`` is not read (the
+        unlabeled TU datasets have none; the node count is ``num_nodes``, else ``x.size(0)``) and the dataset's node features are
+        the one-hot out-degrees"""
         if torch.device(device).type != "cuda":
             cls(torch.zeros(1, 1), torch.zeros(2, 0, dtype=torch.int64), [0, 1], device=device)      # (raises: no CPU fallback)
         xs, eis, eas, ys, node_ptr = [], [], [], [], [0]
         for g in graphs:
-            x = torch.as_tensor(g.x)
             ei = torch.as_tensor(g.edge_index)
-            if ei.numel() and (int(ei.min()) < 0 or int(ei.max()) >= x.size(0)):
-                raise ValueError(f"graph {len(xs)}: edge_index holds node ids outside [0, {x.size(0)})")
+            if degree_features is None:
+                x = torch.as_tensor(g.x)
+                n = int(x.size(0))
+            else:
+                x, n = None, getattr(g, "num_nodes", None)
+                if n is None:
+                    if getattr(g, "x", None) is None:
+                        raise ValueError(f"graph {len(xs)}: neither num_nodes nor x says how many nodes it has")
+                    n = torch.as_tensor(g.x).size(0)
+                n = int(n)
+            if ei.numel() and (int(ei.min()) < 0 or int(ei.max()) >= n):
+                raise ValueError(f"graph {len(xs)}: edge_index holds node ids outside [0, {n})")
             xs.append(x)
             eis.append(ei.reshape(2, -1).to(torch.int64) + node_ptr[-1])
-            node_ptr.append(node_ptr[-1] + int(x.size(0)))
+            node_ptr.append(node_ptr[-1] + n)
             ea, y = getattr(g, "edge_attr", None), getattr(g, "y", None)
             if ea is not None:
                 eas.append(torch.as_tensor(ea))
@@ -176,8 +234,9 @@ class DeviceGraphDataset:
             raise ValueError("no graphs")
         if (eas and len(eas) != len(xs)) or (ys and len(ys) != len(xs)):
             raise ValueError("edge_attr / y must be present on every graph or on none")
-        return cls(torch.cat(xs), torch.cat(eis, dim=1), node_ptr, edge_attr=torch.cat(eas) if eas else None,
-                   y=torch.cat(ys) if ys else None, device=device)
+        return cls(torch.cat(xs) if degree_features is None else None, torch.cat(eis, dim=1), node_ptr,
+                   edge_attr=torch.cat(eas) if eas else None, y=torch.cat(ys) if ys else None, device=device,
+                   degree_features=degree_features)
 
     # -- views
     def __len__(self) -> int:

@@ -272,11 +272,42 @@ def train_graph_batches(model, batches, nb_epochs: int = 1, warmup: int = 0, lr:
     replicas = None
     if group is not None:
         replicas = GradientReplicas(model.parameters(), None if group is True else group)
-    if optimizer is None:
-        optimizer = Adam(model.parameters(), lr=lr)            # torch.optim.Adam's rule, one library call per step
     from . import ops as ops_mod
     if loss_fn is None:
         loss_fn = ops_mod.l1_loss      # = torch.nn.L1Loss() (mean |p - t|), one launch each way instead of six
+    losses, weights = [], []
+
+    def begin():
+        losses.clear()
+        weights.clear()
+
+    def batch_loss(data):
+        return loss_fn(model(data).squeeze(), data.y.squeeze())
+
+    def end():
+        if not losses:
+            return torch.zeros(())
+        # the epoch's mean training loss, weighted by graphs per batch: three small launches per EPOCH, still no read-back
+        # (the caller converts after the final synchronisation)
+        w = torch.tensor(weights, dtype=losses[0].dtype).to(losses[0].device, non_blocking=True)
+        return (torch.stack(losses) * w).sum() / max(sum(weights), 1.0)
+
+    dt, means = _train_minibatches(model, batches, nb_epochs, warmup, lr, optimizer, replicas, begin, batch_loss,
+                                   lambda loss, data: (losses.append(loss), weights.append(_graphs_in(data))), end)
+    return dt, [float(m) for m in means]
+
+
+def _graphs_in(data) -> float:
+    return float(int(getattr(data, "num_graphs", 0) or data.y.size(0)))
+
+
+def _train_minibatches(model, batches, nb_epochs, warmup, lr, optimizer, replicas, begin, batch_loss, record, end):
+    """the skeleton the mini-batch training loops share (``train_graph_batches``, ``train_graph_classification``): per epoch
+    ``begin()``, then per batch ``{zero_grad, loss = batch_loss(data), backward, step, record(loss.detach(), data)}``, then the
+    epoch's deferred graph checks and ``end()`` -- the epoch's figure.  Returns ``(seconds per step, [end() of every timed epoch])``."""
+    if optimizer is None:
+        optimizer = Adam(model.parameters(), lr=lr)            # torch.optim.Adam's rule, one library call per step
+    from . import ops as ops_mod
     model.train()
     on_gpu = any(p.is_cuda for p in model.parameters())
 
@@ -288,26 +319,20 @@ def train_graph_batches(model, batches, nb_epochs: int = 1, warmup: int = 0, lr:
         return root[0]
 
     def epoch():
-        losses, weights = [], []
+        begin()
         for data in batches:
             optimizer.zero_grad(set_to_none=True)
-            loss = loss_fn(model(data).squeeze(), data.y.squeeze())
+            loss = batch_loss(data)
             if replicas is None:
                 loss.backward(one(loss))           # (the implicit root gradient would be a torch.ones_like: one fill launch per step)
             else:
                 loss.backward(replicas.scale(loss))
                 replicas.sync()
             optimizer.step()
-            losses.append(loss.detach())           # (kept on the device: no kernel and no read-back per step)
-            weights.append(float(int(getattr(data, "num_graphs", 0) or data.y.size(0))))
+            record(loss.detach(), data)            # (kept on the device: no kernel and no read-back per step)
         if on_gpu:
             ops_mod.flush_graph_checks()       # the epoch's deferred node-id range checks (incl. the LAST batch's): one wait per epoch
-        if not losses:
-            return torch.zeros(())
-        # the epoch's mean training loss, weighted by graphs per batch: three small launches per EPOCH, still no read-back
-        # (the caller converts after the final synchronisation)
-        w = torch.tensor(weights, dtype=losses[0].dtype).to(losses[0].device, non_blocking=True)
-        return (torch.stack(losses) * w).sum() / max(sum(weights), 1.0)
+        return end()
 
     # The backward of a ~1 ms step is ~80 kernel launches from ~10 library calls: handing every tape node to autograd's per-device
     # worker thread costs more than running it (host issue time of the ZINC-shaped step on the round-6 boxes: 1.41-1.50 ms per
@@ -328,7 +353,7 @@ def train_graph_batches(model, batches, nb_epochs: int = 1, warmup: int = 0, lr:
         dt = (time.perf_counter() - t0) / max(1, nb_epochs * len(batches))
     finally:
         torch.autograd.set_multithreading_enabled(mt_was)
-    return float(dt), [float(m) for m in means]
+    return float(dt), means
 
 
 def evaluate_graph_batches(model, batches, loss_fn=None) -> float:
@@ -351,6 +376,75 @@ def evaluate_graph_batches(model, batches, loss_fn=None) -> float:
         return 0.0
     w = torch.tensor(weights, dtype=losses[0].dtype).to(losses[0].device, non_blocking=True)
     return float((torch.stack(losses) * w).sum() / max(sum(weights), 1.0))
+
+
+def _dataset_size(loader, seen: int) -> int:
+    """``len(loader.dataset)``, the divisor of the reference's loops; for a plain list of batches, the graphs it holds"""
+    ds = getattr(loader, "dataset", None)
+    return len(ds) if ds is not None else seen
+
+
+def train_graph_classification(model, loader, nb_epochs: int = 1, warmup: int = 0, lr: float = 1e-3, optimizer=None, loss_fn=None):
+    """The training loop of the reference's graph-classification scripts (``graph_classification/graph_classification_utils.py:45-55``:
+    ``loss = F.nll_loss(model(data), data.y)``, ``{zero_grad, backward, step}`` per batch, ``loss_all += data.num_graphs *
+    loss.item()``, ``loss_all / len(loader.dataset)``) over ``loader`` -- a ``kagnn_amd.data.DeviceBatchLoader``, or any
+    re-iterable of batch objects with ``len()``.  The skeleton is ``train_graph_batches``' (autograd on the calling thread, a
+    cached root gradient, ``kagnn_amd.harness.Adam`` unless an optimiser is passed, the deferred graph checks once per epoch).
+    Returns ``(seconds per step, [mean training loss per epoch])``.  The loss is ``ops.nll_loss`` with a ``ClassificationMeter``: one
+    launch per batch that also adds the batch's loss sum to a device record, which is read ONCE per epoch -- the script's
+    ``loss.item()`` per batch drains the stream every step.  With ``loss_fn=torch.nn.functional.nll_loss`` and
+    ``optimizer=torch.optim.Adam(..., fused=True)`` the parameter trajectory is the script's, bit for bit (the epoch's loss is then
+    ``sum(num_graphs * loss)`` over the batch losses kept on the device, summed in fp64, still one read per epoch)."""
+    from . import ops as ops_mod
+    meter = None
+    if loss_fn is None:
+        meter = ops_mod.ClassificationMeter(next(model.parameters()).device)
+    losses, weights = [], []
+
+    def begin():
+        losses.clear()
+        weights.clear()
+        if meter is not None:
+            meter.reset()
+
+    def batch_loss(data):
+        if meter is not None:
+            return ops_mod.nll_loss(model(data), data.y, accumulate=meter)
+        return loss_fn(model(data), data.y)
+
+    def record(loss, data):
+        if meter is None:
+            losses.append(loss)
+            weights.append(_graphs_in(data))
+
+    def end():
+        if meter is not None:
+            nll_sum, _correct, graphs = meter.read()
+            return nll_sum / max(_dataset_size(loader, graphs), 1)
+        if not losses:
+            return 0.0
+        w = torch.tensor(weights, dtype=torch.float64).to(losses[0].device, non_blocking=True)
+        return float((torch.stack(losses).double() * w).sum()) / max(_dataset_size(loader, int(sum(weights))), 1)
+
+    return _train_minibatches(model, loader, nb_epochs, warmup, lr, optimizer, None, begin, batch_loss, record, end)
+
+
+def evaluate_graph_classification(model, loader):
+    """``val`` and ``test`` of the same scripts (``graph_classification_utils.py:57-72``: ``model.eval()``, ``loss_all +=
+    F.nll_loss(model(data), data.y, reduction='sum').item()`` and ``correct += model(data).max(1)[1].eq(data.y).sum().item()``,
+    both over ``len(loader.dataset)``) in ONE pass: ``(mean nll per graph, accuracy)``.  One ``ops.nll_loss(..., reduction='sum',
+    accumulate=meter)`` launch per batch, under ``no_grad``; the deferred graph checks are flushed and the meter is read back ONCE,
+    at the end.  Leaves the model in evaluation mode, as the scripts do."""
+    from . import ops as ops_mod
+    model.eval()
+    meter = ops_mod.ClassificationMeter(next(model.parameters()).device)
+    with torch.no_grad():
+        for data in loader:
+            ops_mod.nll_loss(model(data), data.y, reduction="sum", accumulate=meter)
+    ops_mod.flush_graph_checks()
+    nll_sum, correct, graphs = meter.read()
+    n = max(_dataset_size(loader, graphs), 1)
+    return nll_sum / n, correct / n
 
 
 def count_params(model) -> int:

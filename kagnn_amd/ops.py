@@ -409,6 +409,10 @@ def flush_graph_checks(device=None) -> None:
     before reading outputs back on the host (the last batch of a loop, or a single inference call, was never
     validated).  ``harness.train_graph_batches`` does so at the end of every epoch."""
     devs = list(_pending_checks) if device is None else [torch.device(device).index]
+    if _nll_flags:
+        if device is None:
+            devs += [d for d in _nll_flags if d not in devs]
+        _defer_nll_flags(devs)           # the bad-label flag of every nll_loss launch so far joins the checks waited for below
     bad = []
     for d in devs:
         for en in _pending_checks.get(d) or []:
@@ -1881,6 +1885,130 @@ def l1_loss(pred, target) -> torch.Tensor:
     if pred.shape != target.shape:
         raise ValueError(f"l1_loss: prediction {tuple(pred.shape)} and target {tuple(target.shape)} must have the same shape")
     return _L1LossFn.apply(pred, target)
+
+
+# ======================================================================== graph classification: Degree, nll_loss, the epoch's meter
+_NLL_FLAG_MESSAGE = "kagnn_nll_loss_fwd: a target holds a class outside [0, num_classes) (the loss of that mini-batch is NaN)"
+_nll_flags: "dict[int, list]" = {}       # device index -> [int32[2] on the device (the kernel only ever SETS it), launches since the last flush]
+
+
+def _nll_flag(dev) -> torch.Tensor:
+    """the device's bad-label flag of ``kagnn_nll_loss_fwd``.  One per device, not one per launch: a launch only ever sets it, and
+    ``flush_graph_checks`` sends it through ``_defer_flag_check`` behind everything queued so far and clears it -- a training step
+    pays nothing for the check.  ONE STREAM per device is assumed, as everywhere in the loops of ``kagnn_amd.harness``: the copy and
+    the clearing fill run on the stream that is current when ``flush_graph_checks`` is called, so an ``nll_loss`` launched on
+    another stream has to be ordered before that call by its caller (``stream.synchronize()`` or ``wait_stream``), or its flag can
+    be missed"""
+    en = _nll_flags.get(dev.index)
+    if en is None:
+        en = _nll_flags[dev.index] = [torch.zeros(2, dtype=torch.int32, device=dev), 0]
+    en[1] += 1
+    return en[0]
+
+
+def _defer_nll_flags(devs) -> None:
+    for d in devs:
+        en = _nll_flags.get(d)
+        if en is not None and en[1]:
+            with torch.cuda.device(d):
+                _defer_flag_check(en[0], _NLL_FLAG_MESSAGE)
+                en[0].zero_()                    # (behind the copy on the same stream: the next epoch starts clean)
+            en[1] = 0
+
+
+class ClassificationMeter:
+    """The running figures of one epoch of the reference's classification loops (``graph_classification_utils.py:45-72``:
+    ``loss_all += ...item()`` and ``correct += ...item()`` per batch) as a 24-byte DEVICE record ``{double nll_sum; int64 correct;
+    int64 graphs}`` that ``nll_loss(..., accumulate=meter)`` adds to inside its one launch.  ``reset()`` is one asynchronous fill,
+    ``read()`` ONE read-back: ``(nll_sum, correct, graphs)`` as Python numbers."""
+
+    def __init__(self, device="cuda"):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("kagnn_amd.ops.ClassificationMeter keeps its record on an MI355X (kagnn_nll_loss_fwd adds to it there); "
+                               f"got device '{device}'. There is no CPU fallback in this package.")
+        self.record = torch.zeros(3, dtype=torch.int64, device=device)
+
+    def reset(self) -> None:
+        self.record.zero_()
+
+    def read(self) -> Tuple[float, int, int]:
+        host = self.record.cpu()
+        return float(host[:1].view(torch.float64)[0]), int(host[1]), int(host[2])
+
+
+_REDUCTIONS = {"mean": 0, "sum": 1}      # KAGNN_REDUCTION_MEAN / _SUM
+
+
+class _NllLossFn(Function):
+    @staticmethod
+    @_on_operand_device
+    def forward(ctx, logp, target, reduction, meter):
+        z = _rows(logp)
+        b, c = z.shape
+        y = target.contiguous()
+        out = torch.empty(2, dtype=torch.float32, device=z.device)          # (mean, sum)
+        _call("kagnn_nll_loss_fwd", _ptr(z), _ld(z), b, c, _ptr(y), _ptr(out), ctypes.c_void_p(out.data_ptr() + 4),
+              None if meter is None else _ptr(meter.record), _ptr(_nll_flag(z.device)), _stream())
+        ctx.save_for_backward(y)
+        ctx.classes, ctx.reduction = c, reduction
+        return out[reduction]
+
+    @staticmethod
+    @once_differentiable
+    @_on_operand_device
+    def backward(ctx, gloss):
+        y, = ctx.saved_tensors
+        b, c = y.numel(), ctx.classes
+        g = gloss.to(torch.float32).contiguous()
+        gz = torch.empty((b, c), dtype=torch.float32, device=y.device)
+        _call("kagnn_nll_loss_bwd", _ptr(y), b, c, _ptr(g), ctx.reduction, _ptr(gz), c, _stream())
+        return gz, None, None, None
+
+
+def nll_loss(logp, target, reduction: str = "mean", accumulate: Optional[ClassificationMeter] = None) -> torch.Tensor:
+    """``F.nll_loss(logp, target, reduction=...)`` for the fp32 ``[B, C]`` log-probabilities every graph-classification model here
+    returns and int64 targets ``[B]`` (the loss of the reference's loops, ``graph_classification_utils.py:50,62``): one launch each
+    way, the sum taken in fp64 and rounded once.  ``accumulate``: a ``ClassificationMeter`` on the same device to which the same
+    launch adds this batch's loss SUM (whatever ``reduction`` is), its number of correct arg-max predictions (``:70-71``) and its
+    number of graphs.  No read-back: a target outside ``[0, C)`` gives a NaN loss at once and raises at the next
+    ``flush_graph_checks()`` (called on the stream the losses were launched on: see ``_nll_flag``)."""
+    if reduction not in _REDUCTIONS:
+        raise ValueError(f"nll_loss: reduction must be 'mean' or 'sum' (one launch makes one number), got {reduction!r}")
+    _need_cuda(logp, target, None if accumulate is None else accumulate.record)
+    if logp.dim() != 2 or target.dim() != 1 or target.size(0) != logp.size(0):
+        raise ValueError(f"nll_loss: log-probabilities [B, C] and targets [B]; got {tuple(logp.shape)} and {tuple(target.shape)}")
+    if target.dtype != torch.int64:
+        raise TypeError(f"nll_loss: targets are int64 class indices, got {target.dtype}")
+    return _NllLossFn.apply(logp, target, _REDUCTIONS[reduction], accumulate)
+
+
+def _degree_one_hot_raw(rowptr_by_source: Optional[torch.Tensor], num_nodes: int, num_classes: int, device) -> torch.Tensor:
+    x = torch.empty((num_nodes, num_classes), dtype=torch.float32, device=device)
+    with _device_of(x):
+        _call("kagnn_degree_one_hot", _ptr(rowptr_by_source), num_nodes, num_classes, _ptr(x), num_classes, _stream())
+    return x
+
+
+def degree_one_hot(graph, num_nodes: int, num_classes: int = 36) -> torch.Tensor:
+    """The reference's ``Degree`` transform (``graph_classification_utils.py:31-36``), the node features of the unlabeled TU
+    datasets: ``F.one_hot(clip(degree(edge_index[0], num_nodes), 0, num_classes - 1), num_classes).float()`` in one launch.
+    ``graph``: a ``GraphIndex`` or an int64 ``edge_index [2, E]`` on the device (indexed here, uncached).  The degree is the OUT-degree
+    -- edges counted at their source -- read off the index's by-source offsets (``rowptr_t``)."""
+    num_nodes, num_classes = int(num_nodes), int(num_classes)
+    if num_classes < 1:
+        raise ValueError("degree_one_hot: num_classes >= 1")
+    if isinstance(graph, GraphIndex):
+        if graph.num_nodes != num_nodes:
+            raise ValueError(f"degree_one_hot: the index describes {graph.num_nodes} nodes, not {num_nodes}")
+        return _degree_one_hot_raw(graph.rowptr_t, num_nodes, num_classes, graph.device)
+    _need_cuda(graph)
+    if graph.dim() != 2 or graph.size(0) != 2 or graph.dtype != torch.int64:
+        raise ValueError("edge_index must be an int64 tensor of shape [2, E]")
+    if graph.size(1) == 0:
+        return _degree_one_hot_raw(None, num_nodes, num_classes, graph.device)
+    g = GraphIndex(graph, num_nodes)
+    return _degree_one_hot_raw(g.rowptr_t, num_nodes, num_classes, graph.device)
 
 
 # ======================================================================== GAT attention aggregation
