@@ -49,7 +49,7 @@ extern "C" {
 #define KAGNN_DTYPE_F32 0
 #define KAGNN_DTYPE_BF16 1
 
-int kagnn_version(void);          /* 264 = 263 + kagnn_degree_one_hot, kagnn_nll_loss_fwd / _bwd; 263 = 262 + kagnn_batch_assemble; 262 = 261 - the fields edge_src, edge_dst, csr_flags of kagnn_kagin_model_t; 261 = 260 + kagnn_fastkan_fwd_stats_in_kernel; 260 = round 6: + the feature-sharded FastKAN entry points kagnn_fastkan_row_moments .. _shard_bwd_finish, + kagnn_kagin_model_*; 250 = 240 + KAGNN_PREC_HALF; 240 = 230 + kagnn_gin_kan_layer_bwd_bn_sums; 230 = 220 + the *_affine entry points of a folded BatchNorm1d; 220 = 210 + the stage timer) */
+int kagnn_version(void);          /* 265 = 264 + kagnn_node_eval, kagnn_early_stop_update, kagnn_copy_if; 264 = 263 + kagnn_degree_one_hot, kagnn_nll_loss_fwd / _bwd; 263 = 262 + kagnn_batch_assemble; 262 = 261 - the fields edge_src, edge_dst, csr_flags of kagnn_kagin_model_t; 261 = 260 + kagnn_fastkan_fwd_stats_in_kernel; 260 = round 6: + the feature-sharded FastKAN entry points kagnn_fastkan_row_moments .. _shard_bwd_finish, + kagnn_kagin_model_*; 250 = 240 + KAGNN_PREC_HALF; 240 = 230 + kagnn_gin_kan_layer_bwd_bn_sums; 230 = 220 + the *_affine entry points of a folded BatchNorm1d; 220 = 210 + the stage timer) */
 const char* kagnn_last_error(void);
 
 /* Stage timer -- a measurement aid, off by default (no reference counterpart: the reference times whole epochs with
@@ -720,6 +720,42 @@ int kagnn_nll_loss_fwd(const float* logp, int64_t ld, int64_t rows, int32_t clas
                        float* loss_sum, void* accum, int32_t* flag, void* stream);
 int kagnn_nll_loss_bwd(const int64_t* y, int64_t rows, int32_t classes, const float* g_loss, int32_t reduction, float* g_logp,
                        int64_t ldg, void* stream);
+
+/* What the node-classification experiment does after the logits (node_classification_clean/utils.py: train_total, EarlyStopper),
+ * without a read-back: the loss and the accuracies of every split in one pass, the stopper as a device record, the best-weights
+ * save as a predicated copy.  All three: no host synchronisation, deterministic.
+ *
+ * kagnn_node_eval: logits [num_rows, num_classes] fp32 (row stride ld >= num_classes; 1 <= num_classes, tested to 1024), labels
+ * [num_rows] int64, split_bits [num_rows] bytes: bit s set = the row belongs to split s (splits may overlap; bits at or above
+ * num_splits are ignored; 1 <= num_splits <= 8).  records: an 8-byte aligned device array of num_splits
+ *   { double xent_sum; int64_t correct; int64_t rows; }
+ * which the call OVERWRITES: the sum over the split's rows of logsumexp(z) - z[y] (the row term max-subtracted in fp32, the sum in
+ * fp64 in a fixed order: per-workgroup partials in the workspace, added in index order -- no floating-point atomics, the same
+ * bits every run), the number of rows whose arg-max equals the label (ties: the LOWEST class index; a row holding a NaN is never
+ * correct, and its term is NaN) and the number of rows.  One read of the logits serves all splits; a row in no split costs its
+ * byte only.  A label outside [0, num_classes) in a row of some split: that split's xent_sum is NaN, the row counts as wrong,
+ * *flag is set to 1 (the launch never clears it), nothing is read out of bounds.  num_rows == 0: every record is zero.
+ *
+ * kagnn_early_stop_update: EarlyStopper(patience, min_delta).early_stop(val_loss) of one epoch on the device record
+ *   { float min_loss (start: +inf), min_delta; int32_t patience, counter, epochs, best_epoch (start: -1), improved, stopped; }
+ * with val_loss = (float)(xent_sum / rows) of eval_records[val_split] (rounded once; rows == 0: NaN) and fp32 comparisons:
+ *   val < min_loss: min_loss = val, counter = 0, best_epoch = epochs, improved = 1;
+ *   else val >= min_loss + min_delta: ++counter, stopped = 1 once counter >= patience;   anything else (NaN included): nothing.
+ * Before the rule the num_splits eval records are copied to history[epochs] (history: [max_epochs][num_splits] records, or
+ * NULL); after it epochs is incremented.  With stopped set, or epochs == max_epochs, the launch writes improved = 0 and nothing
+ * else: later epochs are inert.
+ *
+ * kagnn_copy_if: dst[k][0 .. bytes[k]) = src[k][..] for all k < count if the device word *flag != 0, else no store at all.
+ * HOST arrays of device pointers (4-byte aligned) and byte counts (multiples of 4), one launch per 32 tensors; 16-byte vectors
+ * where both pointers of a tensor allow, 4-byte words otherwise and for the tail.  Parameters and buffers alike go through it as
+ * bytes (running statistics, num_batches_tracked, grids): with flag = the record's `improved` it is the best-weights snapshot. */
+int kagnn_node_eval_workspace_bytes(int64_t num_rows, int32_t num_classes, int32_t num_splits, size_t* bytes_host);
+int kagnn_node_eval(const float* logits, int64_t ld, int64_t num_rows, int32_t num_classes, const int64_t* labels,
+                    const uint8_t* split_bits, int32_t num_splits, void* records, int32_t* flag, void* workspace,
+                    size_t workspace_bytes, void* stream);
+int kagnn_early_stop_update(const void* eval_records, int32_t num_splits, int32_t val_split, void* state, void* history,
+                            int32_t max_epochs, void* stream);
+int kagnn_copy_if(const int32_t* flag, int32_t count, void* const* dst, const void* const* src, const int64_t* bytes, void* stream);
 
 /* Optimiser of the same scripts (optuna_zinc.py:49,62: torch.optim.Adam(model.parameters(), lr), optimizer.step() per batch): one
  * update of `count` fp32 tensors in one launch per 32 tensors.  HOST arrays of device pointers / element counts; `step` = 1, 2, ...

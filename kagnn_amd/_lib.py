@@ -153,6 +153,10 @@ _SIGNATURES = {
     "kagnn_degree_one_hot": (c_int32, [_P, c_int64, c_int32, _P, c_int64, _P]),
     "kagnn_nll_loss_fwd": (c_int32, [_P, c_int64, c_int64, c_int32, _P, _P, _P, _P, _P, _P]),
     "kagnn_nll_loss_bwd": (c_int32, [_P, c_int64, c_int32, _P, c_int32, _P, c_int64, _P]),
+    "kagnn_node_eval_workspace_bytes": (c_int32, [c_int64, c_int32, c_int32, POINTER(c_size_t)]),
+    "kagnn_node_eval": (c_int32, [_P, c_int64, c_int64, c_int32, _P, _P, c_int32, _P, _P, _P, c_size_t, _P]),
+    "kagnn_early_stop_update": (c_int32, [_P, c_int32, c_int32, _P, _P, c_int32, _P]),
+    "kagnn_copy_if": (c_int32, [_P, c_int32, _P, _P, _P, _P]),
     "kagnn_adam_step": (c_int32, [c_int32, _P, _P, _P, _P, _P, c_float, c_float, c_float, c_float, c_float, c_int64, _P]),
     "kagnn_gat_logits": (c_int32, [_P, c_int64, c_int64, c_int32, c_int32, _P, _P, _P, _P, _P]),
     "kagnn_gat_fwd": (c_int32, [_P, c_int64, _P, _P, _P, _P, c_int64, c_int32, c_int32, _P, _P, c_int64, _P, _P, _P, c_int64,

@@ -102,6 +102,11 @@ int degree_one_hot(const int* rowptr, long N, int K, float* x, long ldx, hipStre
 int nll_loss_fwd(const float* logp, long ld, long rows, int C, const long* y, float* loss_mean, float* loss_sum, void* accum,
                  int* flag, hipStream_t st);
 int nll_loss_bwd(const long* y, long rows, int C, const float* g_loss, int reduction, float* g_logp, long ldg, hipStream_t st);
+size_t node_eval_ws_bytes(long N, int C, int S);
+int node_eval(const float* z, long ld, long N, int C, const long* y, const unsigned char* bits, int S, void* records, int* flag,
+              void* ws, size_t ws_bytes, hipStream_t st);
+int early_stop_update(const void* records, int S, int val_split, void* state, void* history, int max_epochs, hipStream_t st);
+int copy_if(const int* flag, int count, void* const* dst, const void* const* src, const long* bytes, hipStream_t st);
 int adam_step(int count, float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
               const long* numel, float lr, float beta1, float beta2, float eps, float weight_decay, long step, hipStream_t st);
 size_t gat_att_grad_ws_bytes(long N, int H, int C);
@@ -205,7 +210,7 @@ static bool use_split_dw(int in, int out, int G, int K, int mode) { return mode 
 #pragma GCC visibility push(default)
 extern "C" {
 
-int kagnn_version(void) { return 264; }
+int kagnn_version(void) { return 265; }
 const char* kagnn_last_error(void) { return g_err; }
 
 int kagnn_stage_timer_enable(const char* only) {
@@ -1042,6 +1047,46 @@ int kagnn_adam_step(int32_t count, float* const* params, const float* const* gra
                      (long)step, as_stream(stream));
 }
 
+
+// the node-classification experiment's bookkeeping after the logits (nodeclass.hip)
+int kagnn_node_eval_workspace_bytes(int64_t num_rows, int32_t num_classes, int32_t num_splits, size_t* bytes) {
+    KAGNN_CHECK_ARG(bytes != nullptr && num_rows >= 0 && num_classes >= 1 && num_splits >= 1 && num_splits <= 8, "bad argument");
+    *bytes = node_eval_ws_bytes(num_rows, num_classes, num_splits);
+    return KAGNN_OK;
+}
+
+int kagnn_node_eval(const float* logits, int64_t ld, int64_t num_rows, int32_t num_classes, const int64_t* labels,
+                    const uint8_t* split_bits, int32_t num_splits, void* records, int32_t* flag, void* workspace,
+                    size_t workspace_bytes, void* stream) {
+    KAGNN_STAGE(stream);
+    KAGNN_CHECK_ARG(num_rows >= 0 && num_classes >= 1 && ld >= num_classes, "bad shape");
+    KAGNN_CHECK_ARG(num_splits >= 1 && num_splits <= 8, "num_splits must be 1..8 (one bit of the row's byte each)");
+    KAGNN_CHECK_ARG(records && flag && (num_rows == 0 || (logits && labels && split_bits)), "null array");
+    KAGNN_CHECK_ARG(((uintptr_t)records & 7) == 0, "the records must be 8-byte aligned");
+    static_assert(sizeof(long) == sizeof(int64_t), "LP64");
+    return node_eval(logits, ld, num_rows, num_classes, (const long*)labels, split_bits, num_splits, records, flag, workspace,
+                     workspace_bytes, as_stream(stream));
+}
+
+int kagnn_early_stop_update(const void* eval_records, int32_t num_splits, int32_t val_split, void* state, void* history,
+                            int32_t max_epochs, void* stream) {
+    KAGNN_STAGE(stream);
+    KAGNN_CHECK_ARG(num_splits >= 1 && num_splits <= 8 && val_split >= 0 && val_split < num_splits && max_epochs >= 0, "bad split or epoch count");
+    KAGNN_CHECK_ARG(eval_records && state, "null array");
+    KAGNN_CHECK_ARG(((uintptr_t)eval_records & 7) == 0 && ((uintptr_t)history & 7) == 0 && ((uintptr_t)state & 3) == 0, "misaligned record");
+    return early_stop_update(eval_records, num_splits, val_split, state, history, max_epochs, as_stream(stream));
+}
+
+int kagnn_copy_if(const int32_t* flag, int32_t count, void* const* dst, const void* const* src, const int64_t* bytes, void* stream) {
+    KAGNN_STAGE(stream);
+    KAGNN_CHECK_ARG(flag && count >= 0 && (count == 0 || (dst && src && bytes)), "null array or bad count");
+    for (int k = 0; k < count; ++k) {
+        KAGNN_CHECK_ARG(bytes[k] >= 0 && (bytes[k] & 3) == 0, "sizes are multiples of 4 bytes");
+        KAGNN_CHECK_ARG(bytes[k] == 0 || (dst[k] && src[k]), "null tensor");
+        KAGNN_CHECK_ARG((((uintptr_t)dst[k] | (uintptr_t)src[k]) & 3) == 0, "pointers are 4-byte aligned");
+    }
+    return copy_if(flag, count, dst, src, reinterpret_cast<const long*>(bytes), as_stream(stream));
+}
 
 // ---------------------------------------------------------------- direct peer-to-peer exchange (p2p.hip)
 

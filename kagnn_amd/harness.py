@@ -447,6 +447,123 @@ def evaluate_graph_classification(model, loader):
     return nll_sum / n, correct / n
 
 
+class NodeClassificationResult:
+    """what ``train_node_classification`` returns: the figures the reference's ``train_total`` returns (``train_acc``, ``val_acc``,
+    ``val_loss``, ``test_acc``; NaN for an empty split), ``epochs_run`` / ``best_epoch`` / ``stopped`` as the device record counted
+    them, and ``history`` -- the ``ops.node_eval`` records of every counted epoch, a CPU int64 ``[epochs_run, 3, 3]`` tensor
+    (``history[e, s]`` = split ``s`` in {train, val, test}: xent_sum as the bits of a double, correct, rows)"""
+    __slots__ = ("train_acc", "val_acc", "val_loss", "test_acc", "epochs_run", "best_epoch", "stopped", "history")
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw[k])
+
+    def __repr__(self):
+        return "NodeClassificationResult(" + ", ".join(f"{k}={getattr(self, k)!r}" for k in self.__slots__[:-1]) + ")"
+
+
+def _split_figures(row: torch.Tensor):
+    """(mean loss rounded once to fp32, accuracy) of one ``[3]`` history entry; an empty split: NaN, NaN"""
+    xent, correct, rows = float(row[:1].view(torch.float64)[0]), int(row[1]), int(row[2])
+    if rows == 0:
+        return float("nan"), float("nan")
+    return float(np.float32(xent / rows)), correct / rows
+
+
+def train_node_classification(model, x, edge_index, y, train_mask, val_mask, test_mask=None, epochs: int = 1000, lr: float = 1e-2,
+                              patience: int = 100, min_delta: float = 0.0, poll_every: int = 16, optimizer=None, loss_fn=None,
+                              metrics_at: str = "last", _bits=None):
+    """The node-classification experiment of the reference (``node_classification_clean/utils.py:162-193``, ``train_total`` with its
+    ``EarlyStopper``): per epoch a training step on the ``train_mask`` rows, a second forward under ``no_grad`` STILL IN TRAIN MODE
+    (batch statistics, running statistics updated again, dropout drawn again -- the script never switches to ``eval()`` here), the
+    validation loss and the three accuracies of that output, the early stopper, the weights saved on every improvement and loaded
+    back at the end.  Everything after the second forward stays on the device: ``ops.node_eval`` (one pass for the three splits),
+    ``ops.EarlyStop.update`` and ``ops.copy_if(improved, snapshot, live)`` over every entry of the ``state_dict`` -- three launches
+    and two more per 32 tensors.  The host reads the 32-byte record every ``poll_every`` epochs and once, with the history, at
+    the end; it leaves the loop at the first poll that sees the stop.  Epochs run after the stop change neither the snapshot nor
+    the history (they do train the live weights, which the snapshot then replaces, and they advance the RNG).
+    ``poll_every=1`` is the script's one synchronisation per epoch.  The training loss is ``ops.softmax_cross_entropy(out, y,
+    train_mask)`` and the optimiser ``kagnn_amd.harness.Adam`` unless given; with ``loss_fn=torch.nn.CrossEntropyLoss()`` (applied
+    to ``out[train_mask], y[train_mask]``) and ``optimizer=torch.optim.Adam(...)`` the parameter trajectory is the script's, bit
+    for bit.  ``test_mask=None``: the validation mask.  ``metrics_at``: ``"last"`` -- the figures of the last counted epoch's
+    output, as the script returns them (NOT those of the reloaded weights) -- or ``"best"``, the best epoch's.  ``edge_index``:
+    int64 ``[2, E]`` or an ``ops.GraphIndex``; the index is built once."""
+    from . import ops as ops_mod
+    if metrics_at not in ("last", "best"):
+        raise ValueError(f"train_node_classification: metrics_at must be 'last' or 'best', got {metrics_at!r}")
+    epochs, poll_every = int(epochs), max(1, int(poll_every))
+    ops_mod._need_cuda(x, y, train_mask, val_mask, test_mask, *model.parameters())
+    if test_mask is None:
+        test_mask = val_mask
+    g = edge_index if isinstance(edge_index, ops_mod.GraphIndex) or edge_index.is_sparse else ops_mod.graph_index(edge_index, x.size(0))
+    bits = ops_mod.split_bits(train_mask, val_mask, test_mask, out=_bits)
+    if optimizer is None:
+        optimizer = Adam(model.parameters(), lr=lr)
+    live = list(model.state_dict().values())
+    if any(not t.is_contiguous() for t in live):
+        raise ValueError("train_node_classification: every state_dict entry must be contiguous (the snapshot copies them as bytes)")
+    snapshot = [t.detach().clone() for t in live]                 # the script saves the starting weights before the first epoch
+    stop = ops_mod.EarlyStop(patience, min_delta, max_epochs=epochs, num_splits=3, device=x.device)
+    records = torch.empty((3, 3), dtype=torch.int64, device=x.device)
+    root = None
+    model.train()
+    mt_was = torch.autograd.is_multithreading_enabled()
+    torch.autograd.set_multithreading_enabled(False)              # (a ~1 ms backward of short kernels: see _train_minibatches)
+    try:
+        for epoch in range(epochs):
+            optimizer.zero_grad(set_to_none=True)
+            out = model(x, g)
+            loss = ops_mod.softmax_cross_entropy(out, y, train_mask) if loss_fn is None else loss_fn(out[train_mask], y[train_mask])
+            if root is None:
+                root = torch.ones_like(loss)
+            loss.backward(root)
+            optimizer.step()
+            with torch.no_grad():
+                out = model(x, g)
+            ops_mod.node_eval(out, y, bits, 3, out=records)
+            stop.update(records, 1)
+            ops_mod.copy_if(stop.improved, snapshot, live)
+            if (epoch + 1) % poll_every == 0 and stop.read(history=False).stopped:
+                break
+    finally:
+        torch.autograd.set_multithreading_enabled(mt_was)
+    ops_mod.flush_graph_checks(x.device)
+    st = stop.read()
+    with torch.no_grad():
+        for t, saved in zip(live, snapshot):
+            t.copy_(saved)
+    at = st.epochs - 1 if metrics_at == "last" else st.best_epoch
+    nan = float("nan")
+    (_, train_acc), (val_loss, val_acc), (_, test_acc) = [_split_figures(st.history[at, s]) for s in range(3)] if at >= 0 else [(nan, nan)] * 3
+    return NodeClassificationResult(train_acc=train_acc, val_acc=val_acc, val_loss=val_loss, test_acc=test_acc, epochs_run=st.epochs,
+                                    best_epoch=st.best_epoch, stopped=st.stopped, history=st.history)
+
+
+def node_classification_splits(params: dict, x, edge_index, y, train_masks, val_masks, test_masks, **train_kw):
+    """``all_splits`` of the reference (``node_classification_clean/utils.py:195-211``): a fresh ``make_model(params)`` trained by
+    ``train_node_classification`` for every row of the ``[splits, N]`` mask tensors, with ``epochs``, ``lr`` and ``patience`` taken
+    from ``params`` as the script does (``train_kw`` overrides them and passes anything else on).  Returns ``(models, train_accs,
+    val_accs, val_losses, test_accs)`` -- lists with one entry per split.  The graph index and the split-bits byte buffer are built
+    once and reused by every split."""
+    from . import ops as ops_mod
+    ops_mod._need_cuda(x, y, train_masks, val_masks, test_masks)
+    g = edge_index if isinstance(edge_index, ops_mod.GraphIndex) or edge_index.is_sparse else ops_mod.graph_index(edge_index, x.size(0))
+    bits = torch.empty(x.size(0), dtype=torch.uint8, device=x.device)
+    kw = {k: params[k] for k in ("epochs", "lr", "patience") if k in params}
+    kw.update(train_kw)
+    models, train_accs, val_accs, val_losses, test_accs = [], [], [], [], []
+    for s in range(train_masks.size(0)):
+        model = make_model(params).to(x.device)
+        res = train_node_classification(model, x, g, y, train_masks[s], val_masks[s], None if test_masks is None else test_masks[s],
+                                        _bits=bits, **kw)
+        models.append(model)
+        train_accs.append(res.train_acc)
+        val_accs.append(res.val_acc)
+        val_losses.append(res.val_loss)
+        test_accs.append(res.test_acc)
+    return models, train_accs, val_accs, val_losses, test_accs
+
+
 def count_params(model) -> int:
     return int(sum(p.numel() for p in model.parameters()))
 

@@ -13,7 +13,7 @@ import inspect
 import os
 import weakref
 from ctypes import byref, c_int64, c_size_t
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import torch
 from torch.autograd import Function
@@ -409,10 +409,11 @@ def flush_graph_checks(device=None) -> None:
     before reading outputs back on the host (the last batch of a loop, or a single inference call, was never
     validated).  ``harness.train_graph_batches`` does so at the end of every epoch."""
     devs = list(_pending_checks) if device is None else [torch.device(device).index]
-    if _nll_flags:
-        if device is None:
-            devs += [d for d in _nll_flags if d not in devs]
-        _defer_nll_flags(devs)           # the bad-label flag of every nll_loss launch so far joins the checks waited for below
+    for flags, message in ((_nll_flags, _NLL_FLAG_MESSAGE), (_node_eval_flags, _NODE_EVAL_FLAG_MESSAGE)):
+        if flags:
+            if device is None:
+                devs += [d for d in flags if d not in devs]
+            _defer_label_flags(flags, devs, message)     # the bad-label flag of every nll_loss / node_eval launch so far joins the checks waited for below
     bad = []
     for d in devs:
         for en in _pending_checks.get(d) or []:
@@ -1892,26 +1893,28 @@ _NLL_FLAG_MESSAGE = "kagnn_nll_loss_fwd: a target holds a class outside [0, num_
 _nll_flags: "dict[int, list]" = {}       # device index -> [int32[2] on the device (the kernel only ever SETS it), launches since the last flush]
 
 
-def _nll_flag(dev) -> torch.Tensor:
-    """the device's bad-label flag of ``kagnn_nll_loss_fwd``.  One per device, not one per launch: a launch only ever sets it, and
+def _nll_flag(dev, flags=None) -> torch.Tensor:
+    """the device's bad-label flag of ``kagnn_nll_loss_fwd`` (``flags``: another entry point's table -- ``kagnn_node_eval`` keeps its
+    own flag, with its own message, in the same way).  One per device, not one per launch: a launch only ever sets it, and
     ``flush_graph_checks`` sends it through ``_defer_flag_check`` behind everything queued so far and clears it -- a training step
     pays nothing for the check.  ONE STREAM per device is assumed, as everywhere in the loops of ``kagnn_amd.harness``: the copy and
     the clearing fill run on the stream that is current when ``flush_graph_checks`` is called, so an ``nll_loss`` launched on
     another stream has to be ordered before that call by its caller (``stream.synchronize()`` or ``wait_stream``), or its flag can
     be missed"""
-    en = _nll_flags.get(dev.index)
+    flags = _nll_flags if flags is None else flags
+    en = flags.get(dev.index)
     if en is None:
-        en = _nll_flags[dev.index] = [torch.zeros(2, dtype=torch.int32, device=dev), 0]
+        en = flags[dev.index] = [torch.zeros(2, dtype=torch.int32, device=dev), 0]
     en[1] += 1
     return en[0]
 
 
-def _defer_nll_flags(devs) -> None:
+def _defer_label_flags(flags, devs, message) -> None:
     for d in devs:
-        en = _nll_flags.get(d)
+        en = flags.get(d)
         if en is not None and en[1]:
             with torch.cuda.device(d):
-                _defer_flag_check(en[0], _NLL_FLAG_MESSAGE)
+                _defer_flag_check(en[0], message)
                 en[0].zero_()                    # (behind the copy on the same stream: the next epoch starts clean)
             en[1] = 0
 
@@ -2009,6 +2012,157 @@ def degree_one_hot(graph, num_nodes: int, num_classes: int = 36) -> torch.Tensor
         return _degree_one_hot_raw(None, num_nodes, num_classes, graph.device)
     g = GraphIndex(graph, num_nodes)
     return _degree_one_hot_raw(g.rowptr_t, num_nodes, num_classes, graph.device)
+
+
+# ======================================================================== node classification: split metrics, early stopping, snapshot
+_NODE_EVAL_FLAG_MESSAGE = "kagnn_node_eval: a row of a split holds a label outside [0, num_classes) (that split's loss is NaN)"
+_node_eval_flags: "dict[int, list]" = {}     # as _nll_flags: device index -> [int32[2] on the device, launches since the last flush]
+NODE_EVAL_MAX_SPLITS = 8
+
+
+def split_bits(*masks, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One byte per node for ``node_eval``: bit ``s`` is set where ``masks[s]`` is.  Up to 8 boolean ``[N]`` masks of one length
+    on one device, overlapping or not (``test_mask=None`` of the reference's loop is the validation mask passed twice).  Plain
+    torch, built once per split; ``out``: a uint8 ``[N]`` tensor to refill."""
+    if not 1 <= len(masks) <= NODE_EVAL_MAX_SPLITS:
+        raise ValueError(f"split_bits: 1 to {NODE_EVAL_MAX_SPLITS} masks (one bit of the row's byte each), got {len(masks)}")
+    n = masks[0].numel()
+    for m in masks:
+        if m.dim() != 1 or m.dtype != torch.bool:
+            raise TypeError(f"split_bits: masks are 1-D bool tensors, got {m.dtype} of shape {tuple(m.shape)}")
+        if m.numel() != n or m.device != masks[0].device:
+            raise ValueError("split_bits: the masks must have one length and one device; "
+                             f"got {[int(q.numel()) for q in masks]} on {[str(q.device) for q in masks]}")
+    if out is None:
+        out = torch.zeros(n, dtype=torch.uint8, device=masks[0].device)
+    else:
+        if out.dtype != torch.uint8 or out.shape != (n,) or out.device != masks[0].device or not out.is_contiguous():
+            raise ValueError("split_bits: out must be a contiguous uint8 [N] tensor on the masks' device")
+        out.zero_()
+    for s, m in enumerate(masks):
+        out |= m.to(torch.uint8) << s
+    return out
+
+
+def node_eval(logits, labels, bits, num_splits: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Loss and accuracy figures of up to 8 node splits from ONE pass over the fp32 ``[N, C]`` logits (``kagnn_node_eval``): what
+    the reference's loop takes per epoch with a masked ``CrossEntropyLoss`` and three ``pred[mask] == y[mask]`` counts
+    (``node_classification_clean/utils.py:150-160,171-178``).  ``bits``: ``split_bits(...)``; ``labels`` int64 ``[N]``.  Returns the
+    records as an int64 ``[num_splits, 3]`` device tensor -- per split ``(xent_sum, correct, rows)``, the first as the bits of a
+    double (``records[:, 0].view(torch.float64)``); ``out`` is overwritten and returned when given.  No read-back: a label outside
+    ``[0, C)`` in a row of some split makes that split's sum NaN at once and raises at the next ``flush_graph_checks()``, exactly
+    as ``nll_loss``'s flag does (one stream per device: see ``_nll_flag``)."""
+    _need_cuda(logits, labels, bits, out)
+    num_splits = int(num_splits)
+    if logits.dim() != 2 or labels.dim() != 1 or bits.dim() != 1 or labels.size(0) != logits.size(0) or bits.size(0) != logits.size(0):
+        raise ValueError(f"node_eval: logits [N, C], labels [N] and bits [N]; got {tuple(logits.shape)}, {tuple(labels.shape)}, {tuple(bits.shape)}")
+    if labels.dtype != torch.int64 or bits.dtype != torch.uint8:
+        raise TypeError(f"node_eval: labels are int64 class indices and bits uint8 (split_bits), got {labels.dtype} and {bits.dtype}")
+    if not 1 <= num_splits <= NODE_EVAL_MAX_SPLITS:
+        raise ValueError(f"node_eval: num_splits must be 1..{NODE_EVAL_MAX_SPLITS}, got {num_splits}")
+    z = _rows(logits.detach())
+    n, c = z.shape
+    if out is None:
+        out = torch.empty((num_splits, 3), dtype=torch.int64, device=z.device)
+    elif out.dtype != torch.int64 or out.shape != (num_splits, 3) or not out.is_contiguous():
+        raise ValueError("node_eval: out must be a contiguous int64 [num_splits, 3] tensor")
+    y, b = labels.contiguous(), bits.contiguous()
+    nbytes = _sizes("kagnn_node_eval_workspace_bytes", n, c, num_splits)
+    ws = _ws(nbytes, z.device) if nbytes else None
+    with _device_of(z):
+        _call("kagnn_node_eval", _ptr(z), _ld(z), n, c, _ptr(y), _ptr(b), num_splits, _ptr(out), _ptr(_nll_flag(z.device, _node_eval_flags)),
+              _ptr(ws), nbytes, _stream())
+    return out
+
+
+class EarlyStopState(NamedTuple):
+    """what ``EarlyStop.read()`` returns: the device record's fields and ``history`` -- the eval records of the counted epochs as a
+    CPU int64 ``[epochs, num_splits, 3]`` tensor (``None`` when not asked for)"""
+    min_loss: float
+    min_delta: float
+    patience: int
+    counter: int
+    epochs: int
+    best_epoch: int
+    improved: bool
+    stopped: bool
+    history: Optional[torch.Tensor]
+
+
+class EarlyStop:
+    """The reference's ``EarlyStopper(patience, min_delta)`` (``node_classification_clean/utils.py:68-86``) as a 32-byte DEVICE record
+    that ``update(records)`` advances with one tiny launch (``kagnn_early_stop_update``): the validation split's mean loss against
+    the running minimum in fp32, the miss counter, the stop.  It also counts the epochs, remembers the best one and keeps every
+    counted epoch's ``node_eval`` records in ``history``, so the whole run's curves come back with ``read()`` -- ONE read-back.
+    ``improved`` is the device word ``copy_if`` takes as its flag.  Once stopped (or after ``max_epochs`` updates) further updates
+    only clear ``improved``."""
+
+    def __init__(self, patience: int, min_delta: float = 0.0, max_epochs: int = 1000, num_splits: int = 3, device="cuda"):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("kagnn_amd.ops.EarlyStop keeps its record on an MI355X (kagnn_early_stop_update advances it there); "
+                               f"got device '{device}'. There is no CPU fallback in this package.")
+        if not 1 <= int(num_splits) <= NODE_EVAL_MAX_SPLITS or int(max_epochs) < 0:
+            raise ValueError(f"EarlyStop: num_splits 1..{NODE_EVAL_MAX_SPLITS} and max_epochs >= 0")
+        self.num_splits, self.max_epochs = int(num_splits), int(max_epochs)
+        # one buffer: the record (32 bytes = 4 words of 8) in front of history, so read() is one copy
+        host = torch.zeros(4 + self.max_epochs * self.num_splits * 3, dtype=torch.int64)
+        head = host[:4].view(torch.int32)
+        host[:1].view(torch.float32)[0] = float("inf")
+        host[:1].view(torch.float32)[1] = float(min_delta)
+        head[2], head[5] = int(patience), -1
+        self._buf = host.to(device)
+        self.state = self._buf[:4].view(torch.int32)
+        self.improved = self.state[6:7]
+        self.history = self._buf[4:].view(self.max_epochs, self.num_splits, 3)
+
+    def update(self, records: torch.Tensor, val_split: int = 1) -> None:
+        _need_cuda(records)
+        if records.dtype != torch.int64 or records.shape != (self.num_splits, 3) or not records.is_contiguous() or records.device != self._buf.device:
+            raise ValueError(f"EarlyStop.update: records are node_eval's contiguous int64 [{self.num_splits}, 3] tensor on {self._buf.device}")
+        if not 0 <= int(val_split) < self.num_splits:
+            raise ValueError(f"EarlyStop.update: val_split must be in [0, {self.num_splits})")
+        with _device_of(self._buf):
+            _call("kagnn_early_stop_update", _ptr(records), self.num_splits, int(val_split), _ptr(self.state),
+                  _ptr(self.history) if self.max_epochs else None, self.max_epochs, _stream())
+
+    def read(self, history: bool = True) -> EarlyStopState:
+        """ONE read-back: the record, and with ``history`` the counted rows of the history (a poll needs the record alone)"""
+        host = (self._buf if history else self._buf[:4]).cpu()
+        f, i = host[:1].view(torch.float32).tolist(), host[:4].view(torch.int32).tolist()
+        hist = host[4:].view(self.max_epochs, self.num_splits, 3)[:i[4]] if history else None
+        return EarlyStopState(f[0], f[1], i[2], i[3], i[4], i[5], bool(i[6]), bool(i[7]), hist)
+
+
+_COPY_IF_TABLES: dict = {}
+_COPY_IF_TABLES_MAX = 16
+
+
+def copy_if(flag: torch.Tensor, dsts, srcs) -> None:
+    """``dst.copy_(src)`` for every pair if the device word ``flag`` (int32, e.g. ``EarlyStop.improved``) is non-zero, else nothing
+    -- decided ON the device, one launch per 32 tensors (``kagnn_copy_if``).  The tensors go as bytes: parameters and buffers of
+    any dtype alike, contiguous, pairwise the same dtype and shape, their sizes multiples of 4 bytes (an int64 counter is 8).  The
+    pointer tables are cached per set of tensors, as ``harness.Adam`` caches its own."""
+    dsts, srcs = list(dsts), list(srcs)
+    _need_cuda(flag, *dsts, *srcs)
+    if flag.dtype != torch.int32 or flag.numel() != 1:
+        raise TypeError(f"copy_if: the flag is one int32 on the device, got {flag.dtype} x {flag.numel()}")
+    if len(dsts) != len(srcs):
+        raise ValueError(f"copy_if: {len(dsts)} destinations for {len(srcs)} sources")
+    key = (tuple(t.data_ptr() for t in dsts), tuple(t.data_ptr() for t in srcs), tuple(t.numel() * t.element_size() for t in srcs))
+    tables = _COPY_IF_TABLES.get(key)
+    if tables is None:
+        for d, t in zip(dsts, srcs):
+            if d.dtype != t.dtype or d.shape != t.shape or not d.is_contiguous() or not t.is_contiguous():
+                raise ValueError(f"copy_if: pairs of contiguous tensors of one dtype and shape; got {d.dtype} {tuple(d.shape)} <- {t.dtype} {tuple(t.shape)}")
+            if (t.numel() * t.element_size()) % 4 or d.data_ptr() % 4 or t.data_ptr() % 4:
+                raise ValueError("copy_if: tensors are 4-byte aligned and their sizes multiples of 4 bytes")
+        n = len(dsts)
+        if len(_COPY_IF_TABLES) >= _COPY_IF_TABLES_MAX:
+            _COPY_IF_TABLES.clear()
+        tables = _COPY_IF_TABLES[key] = ((ctypes.c_void_p * n)(*key[0]), (ctypes.c_void_p * n)(*key[1]), (ctypes.c_int64 * n)(*key[2]))
+    with _device_of(flag):
+        _call("kagnn_copy_if", _ptr(flag), len(dsts), *tables, _stream())
 
 
 # ======================================================================== GAT attention aggregation
