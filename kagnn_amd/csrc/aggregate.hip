@@ -7,6 +7,7 @@
 // tensor, no atomics.  Rows above `hub_threshold` edges are split into segments handled by one
 // workgroup each (agg_hub_kernel) so a 10^4-degree hub does not serialise a single lane group.
 #include "common.h"
+#include "host.h"
 
 namespace kagnn {
 

@@ -12,6 +12,7 @@
 // Reference behaviour replaced: MessagePassing.propagate of torch_geometric as called from
 // node_classification_clean/models.py:31-37,48-56, at reduced storage precision.
 #include "common.h"
+#include "host.h"
 
 namespace kagnn {
 

@@ -7,6 +7,7 @@
 // never moves an edge across a graph boundary: the slices of the dataset's (rowptr, col, perm) ARE the batch's, element for
 // element.  No sort, one launch, no dependency between workgroups.
 #include "common.h"
+#include "host.h"
 
 namespace kagnn {
 

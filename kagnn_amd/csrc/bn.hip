@@ -12,6 +12,7 @@
 //     regenerated from (seed, row, column) in the backward: no mask tensor, no extra pass.  Counter-based hash, so the
 //     mask is a pure function of the seed; it is NOT torch's Philox stream (same distribution, different bits).
 #include "common.h"
+#include "host.h"
 
 namespace kagnn {
 

@@ -4,6 +4,7 @@
 // which ends in an `.item()` per batch.  Here the loss of a mini-batch is ONE launch that also keeps the epoch's running figures
 // in a 24-byte device record, so a loop reads back once per epoch.
 #include "common.h"
+#include "host.h"
 
 namespace kagnn {
 

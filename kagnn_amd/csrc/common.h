@@ -10,14 +10,17 @@ namespace kagnn {
 
 // ---------------------------------------------------------------- error plumbing
 extern thread_local char g_err[512];
+extern thread_local bool g_half_products;          // KAGNN_PREC_HALF for the duration of an entry-point call (host.h: ModeScope)
 inline int fail(int code, const char* fmt, const char* a = "", long b = 0, long c = 0) {
     snprintf(g_err, sizeof(g_err), fmt, a, b, c);
     return code;
 }
-#define KAGNN_CHECK_ARG(cond, msg)                                                       \
+// (_AS: the body of an entry point that lives in an internal function reports under the entry point's name)
+#define KAGNN_CHECK_ARG_AS(fn, cond, msg)                                                \
     do {                                                                                 \
-        if (!(cond)) return kagnn::fail(KAGNN_ERR_ARG, "%s: argument check failed: " msg, __func__); \
+        if (!(cond)) return kagnn::fail(KAGNN_ERR_ARG, "%s: argument check failed: " msg, fn); \
     } while (0)
+#define KAGNN_CHECK_ARG(cond, msg) KAGNN_CHECK_ARG_AS(__func__, cond, msg)
 #define KAGNN_HIP(...)                                                                   \
     do {                                                                                 \
         hipError_t e_ = (__VA_ARGS__);                                                   \
@@ -31,21 +34,20 @@ inline int fail(int code, const char* fmt, const char* a = "", long b = 0, long 
 
 // Deferred slab reductions of the weight gradient (kan_split_bwd.hip).  A weight-gradient call is {row-slab kernel, slab
 // reduction + unpack}; the second is a ~8 us launch per KANLinear, and the message-passing stack of a graph-level model runs
-// nconv * L of them per step on a mini-batch whose whole step is ~1 ms.  An entry point that owns a workspace ARENA for the slabs of
-// several layers sets g_dw_defer for its duration: a weight-gradient call whose slab lies inside the arena records its reduction
-// instead of launching it, and dw_defer_flush runs all recorded ones in ONE launch (same per-element code path: same bits).
+// nconv * L of them per step on a mini-batch whose whole step is ~1 ms.  An entry point that owns a workspace ARENA with one slab
+// area per layer hands a DwDefer down the weight-gradient path together with the layer's piece of the arena: the call records its
+// reduction instead of launching it, and dw_defer_flush runs all recorded ones in ONE launch (same per-element code path: same
+// bits).  Every other caller passes nullptr and gets the launch.
 struct DwReduceItem {
     const float* slab; long NS; int in, out, C, SG; long inP, outP;
     const float* sw; const float* sc; float* g_bw; float* g_sw; float* g_sc;
 };
 constexpr int kDwDeferMax = 16;
 struct DwDefer {
-    unsigned char* arena; size_t arena_bytes, used;
     int n;
     DwReduceItem item[kDwDeferMax];
 };
-extern thread_local DwDefer* g_dw_defer;
-int dw_defer_flush(hipStream_t st);                 // launches what g_dw_defer holds (no-op when empty) and empties it
+int dw_defer_flush(DwDefer* d, hipStream_t st);     // launches what d holds (no-op when empty) and empties it
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a PER-DEVICE setting: a process-wide "configured" flag leaves the kernel
 // at the 64 KB default on the second GPU a process drives and its launch fails there.  One bit per device ordinal.

@@ -3,6 +3,7 @@
 // contract SURVEY.md 8(c) G7 pins.  Built once per edge_index and cached by the host side; this
 // replaces the per-forward index bookkeeping of torch_geometric's propagate().
 #include "common.h"
+#include "host.h"
 #include <rocprim/rocprim.hpp>
 
 namespace kagnn {

@@ -8,27 +8,9 @@
 // the two k-lanes of an MFMA are two input features, one MFMA per grid point g (plus one for
 // the SiLU base branch).
 #include "split_common.h"
+#include "host.h"
 
 namespace kagnn {
-
-// split-precision kernels shared with the B-spline layer (K == 0 selects the RBF basis)
-bool kan_split_fwd_ok(int in, int out, int G, int K);
-size_t kan_split_pack_fwd_bytes(int in, int out, int C);
-size_t kan_split_pack_dx_bytes(int in, int out, int C, int K);
-size_t kan_split_dw_ws_bytes(long N, int in, int out, int C, int K);
-void kan_split_dw_slabs(long N, int in, int out, int C, int K, long* slabs, long* outP);
-int kan_split_pack_fwd_noscale(const float*, const float*, const float*, int, int, int, void*, hipStream_t);
-int kan_split_pack_dx_noscale(const float*, const float*, const float*, int, int, int, int, void*, hipStream_t);
-int kan_split_fwd_any(const float*, long, long, const float*, int, int, int, int, const void*, float*, long, const RbfArgs&, void*, size_t, hipStream_t);
-size_t kan_split_fwd_ws_bytes(long N, int in, int out, int C);
-int kan_split_dx_any(const float*, long, const float*, long, long, const float*, int, int, int, int, const void*, float*, long, const RbfArgs&, hipStream_t, int gx16);
-int kan_split_dw_any(const float*, long, const float*, long, long, const float*, int, int, int, int, const float*, const float*, float*, float*, float*, float*, size_t, const RbfArgs&, hipStream_t);
-
-int kan_f32_pack(const float*, const float*, const float*, int, int, int, float*, float*, hipStream_t);
-size_t kan_f32_pack_fwd_bytes(int in, int out, int C);
-size_t kan_f32_pack_dx_bytes(int in, int out, int C);
-int kan_dw_reduce(const float* slab, long NS, long per_slab, float* gcat, hipStream_t st);
-void dw_plan(long N, int in, int out, int* NBx, long* rpw);
 
 struct LnArgs {
     const float* w; const float* b; float eps;   // w == nullptr: no layernorm
@@ -875,7 +857,7 @@ int fastkan_bwd(const float* x, long ldx, const float* gy, long ldgy, long N, in
         kan_split_dw_slabs(N, in, out, ng, 0, &slabs, &outP);
         rbw.colpart = (g_bb && N > 0) ? colpart : nullptr;
         { int rc = kan_split_dw_any(x, ldx, gy, ldgy, N, nullptr, in, out, ng, 0, sw, nullptr, g_bw, g_sw, nullptr,
-                                    slab, p.slab, rbw, st); if (rc) return rc; }
+                                    slab, p.slab, rbw, st, nullptr); if (rc) return rc; }
         if (g_bb) {
             if (N > 0) {
                 sum_partials_kernel<<<cdiv(out, 32), 32 * kSumGroups, 0, st>>>(colpart, slabs, outP, out, g_bb, g_bb, out);

@@ -11,6 +11,7 @@
 //   S_i = <g_out_i, out_i>;  g_pre_ij = alpha_ij (<g_out_i, xh_j> - S_i) * leaky'(.)          (by-destination pass)
 //   g_xh_j = sum_i alpha_ij g_out_i + (sum_i g_pre_ij) att_src + (sum_j' g_pre_jj') att_dst   (by-source pass)
 #include "common.h"
+#include "host.h"
 
 namespace kagnn {
 

@@ -13,6 +13,7 @@
 // tensor of the reference never exists.
 #include "common.h"
 #include "split_common.h"
+#include "host.h"
 
 namespace kagnn {
 

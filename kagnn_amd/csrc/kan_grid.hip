@@ -11,6 +11,7 @@
 // a fixed order).  A second tiny kernel solves G S = X W per feature (fp64 Cholesky; a basis no sample touches has a
 // zero pivot and gets coefficient 0, the minimum-norm choice).  C = G + k <= 16.
 #include "common.h"
+#include "host.h"
 
 namespace kagnn {
 

@@ -18,6 +18,7 @@
 //
 // Reference behaviour replaced: node_classification_clean/ekan.py:79-112,146-162 (as kan_split.hip).
 #include "split_common.h"
+#include "host.h"
 
 namespace kagnn {
 
@@ -921,7 +922,6 @@ __global__ void sparse_sum_splits_kernel(const float* __restrict__ part, int spl
     y[(i / out) * ldy + (i % out)] = a;
 }
 
-int moments_finish(const float* partial, int P, int F, float* col_mean, float* col_m2, hipStream_t st);   // bn.hip
 
 static int sp_grid(long N) { return (int)min((long)cdiv(N, 256), 256L); }
 // column moments in the epilogue: whenever the launch is not split over the chunks (few-row inputs)
@@ -995,7 +995,6 @@ __global__ void hub_rows_scatter_kernel(const float* __restrict__ ytmp, const in
     for (int f = threadIdx.x; f < F; f += blockDim.x) y[(long)row * ldy + f] = ytmp[sidx * F + f];
 }
 
-int aggregate_hub_rows(const AggArgs& a, const int* hub_seg, long num_hub_seg, float* ws, size_t ws_bytes, hipStream_t st);   // aggregate.hip
 int kan_sparse_fwd(const float* x, long ldx, long N, const float* knots, int in, int out, int G, int K, const void* pack, float* y,
                    long ldy, void* ws, size_t ws_bytes, float* col_mean, float* col_m2, hipStream_t st);
 

@@ -21,6 +21,7 @@
 //
 // Reference behaviour replaced: node_classification_clean/ekan.py:79-112,146-162.
 #include "split_common.h"
+#include "host.h"
 
 namespace kagnn {
 

@@ -16,13 +16,9 @@
 // Reference behaviour replaced: the autograd backward of node_classification_clean/ekan.py:154-162.
 #include <type_traits>
 #include "split_common.h"
+#include "host.h"
 
 namespace kagnn {
-
-int kan_dw_reduce(const float* slab, long NS, long per_slab, float* gcat, hipStream_t st);
-
-int kan_dw_unpack(const float* gcat, int in, int out, int C, long inP, long outP, const float* sw,
-                  const float* sc, float* g_bw, float* g_sw, float* g_sc, hipStream_t st);
 
 // ====================================================================== input gradient
 
@@ -1791,8 +1787,7 @@ __global__ void kan_dw_reduce_unpack_batch_kernel(const DwReduceBatch b) {
                           blockIdx.y);
 }
 
-int dw_defer_flush(hipStream_t st) {
-    DwDefer* d = g_dw_defer;
+int dw_defer_flush(DwDefer* d, hipStream_t st) {
     if (d == nullptr || d->n == 0) return KAGNN_OK;
     DwReduceBatch b{};
     unsigned gx = 1, gy = 1;
@@ -1808,14 +1803,12 @@ int dw_defer_flush(hipStream_t st) {
     return KAGNN_OK;
 }
 
-// the slab reduction + unpack of one layer: launched now, or recorded when the slab lives in the caller's arena (DwDefer)
+// the slab reduction + unpack of one layer: launched now, or recorded in d (the slab then lives in the caller's arena: DwDefer)
 static int dw_reduce_unpack(const float* slab, long NS, int in, int out, int C, long inP, long outP, const float* sw, const float* sc,
-                            float* g_bw, float* g_sw, float* g_sc, hipStream_t st) {
+                            float* g_bw, float* g_sw, float* g_sc, hipStream_t st, DwDefer* d) {
     const int SG = max(1, min(3, 1024 / (32 * (C + 1))));
-    DwDefer* d = g_dw_defer;
-    const unsigned char* sp = reinterpret_cast<const unsigned char*>(slab);
-    if (d != nullptr && sp >= d->arena && sp < d->arena + d->arena_bytes) {
-        if (d->n > 0 && (d->item[0].C != C || d->n == kDwDeferMax)) { int rc = dw_defer_flush(st); if (rc) return rc; }
+    if (d != nullptr) {
+        if (d->n > 0 && (d->item[0].C != C || d->n == kDwDeferMax)) { int rc = dw_defer_flush(d, st); if (rc) return rc; }
         d->item[d->n++] = DwReduceItem{slab, NS, in, out, C, SG, inP, outP, sw, sc, g_bw, g_sw, g_sc};
         return KAGNN_OK;
     }
@@ -1855,7 +1848,7 @@ void kan_split_dw_slabs(long N, int in, int out, int C, int K, long* slabs, long
 // K == 0: Gaussian RBF basis with G = num_grids; sc == nullptr and g_sw laid out [out][in][G] either way
 int kan_split_dw_any(const float* x, long ldx, const float* gy, long ldgy, long N, const float* knots, int in,
                      int out, int G, int K, const float* sw, const float* sc, float* g_bw, float* g_sw,
-                     float* g_sc, float* ws, size_t ws_bytes, const RbfArgs& rb, hipStream_t st) {
+                     float* g_sc, float* ws, size_t ws_bytes, const RbfArgs& rb, hipStream_t st, DwDefer* defer) {
     const int C = G + K, nk = K ? G + 2 * K + 1 : 0;
     if (kan_dw_w2_ok(in, out, C, K) && rb.centers == nullptr) {
         const DwPlan p = split_dw_plan_w2(N, in, out, C);
@@ -1868,7 +1861,7 @@ int kan_split_dw_any(const float* x, long ldx, const float* gy, long ldgy, long 
 #undef W2N
 #undef W2
         KAGNN_LAUNCH_CHECK();
-        return dw_reduce_unpack(slab, p.NS, in, out, C, p.inP, p.outP, sw, sc, g_bw, g_sw, g_sc, st);
+        return dw_reduce_unpack(slab, p.NS, in, out, C, p.inP, p.outP, sw, sc, g_bw, g_sw, g_sc, st, defer);
     }
     const int sh = C > 8 ? 1 : 0, Ck = sh ? 8 : C;          // slots per (virtual) feature the kernel stores
     const DwPlan p = split_dw_plan(N, in, out, C, K);
@@ -1897,7 +1890,7 @@ int kan_split_dw_any(const float* x, long ldx, const float* gy, long ldgy, long 
         else        { if (SHn == 4) LS(3, 4); else LS(3, 2); }
 #undef LS
         KAGNN_LAUNCH_CHECK();
-        return dw_reduce_unpack(slab, p.NS, in, out, C, p.inP, p.outP, sw, sc, g_bw, g_sw, g_sc, st);
+        return dw_reduce_unpack(slab, p.NS, in, out, C, p.inP, p.outP, sw, sc, g_bw, g_sw, g_sc, st, defer);
     }
     // single-product mode (thread-local, set by the entry point): the cubic, <= 8-coefficient instantiations
     const bool half = g_half_products && K == 3 && !sh;
@@ -1933,7 +1926,7 @@ int kan_split_dw_any(const float* x, long ldx, const float* gy, long ldgy, long 
 #undef ARGS
     KAGNN_LAUNCH_CHECK();
     if (!sh) {
-        return dw_reduce_unpack(slab, p.NS, in, out, C, p.inP, p.outP, sw, sc, g_bw, g_sw, g_sc, st);
+        return dw_reduce_unpack(slab, p.NS, in, out, C, p.inP, p.outP, sw, sc, g_bw, g_sw, g_sc, st, defer);
     }
     { int rc = kan_dw_reduce(slab, p.NS, p.per, gcat, st); if (rc) return rc; }
     if (sh) {
@@ -1946,12 +1939,12 @@ int kan_split_dw_any(const float* x, long ldx, const float* gy, long ldgy, long 
 
 int kan_split_dw(const float* x, long ldx, const float* gy, long ldgy, long N, const float* knots, int in,
                  int out, int G, int K, const float* sw, const float* sc, float* g_bw, float* g_sw,
-                 float* g_sc, float* ws, size_t ws_bytes, hipStream_t st, const float* x_affine) {
+                 float* g_sc, float* ws, size_t ws_bytes, hipStream_t st, const float* x_affine, DwDefer* defer) {
     RbfArgs rb{};
     rb.x_affine = x_affine;
     if (x_affine && (kan_dw_w2_ok(in, out, G + K, K) || out > 64))
         return fail(KAGNN_ERR_UNSUPPORTED, "%s: an input affine needs a cubic layer with <= 8 coefficients and <= 64 outputs", "kan_split_dw");
-    return kan_split_dw_any(x, ldx, gy, ldgy, N, knots, in, out, G, K, sw, sc, g_bw, g_sw, g_sc, ws, ws_bytes, rb, st);
+    return kan_split_dw_any(x, ldx, gy, ldgy, N, knots, in, out, G, K, sw, sc, g_bw, g_sw, g_sc, ws, ws_bytes, rb, st, defer);
 }
 
 }  // namespace kagnn

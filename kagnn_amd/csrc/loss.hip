@@ -7,6 +7,7 @@
 // mean over the masked rows with the count taken on the device (no sync, capturable in a HIP graph); deterministic
 // (per-workgroup partial sums, combined in a fixed order).
 #include "common.h"
+#include "host.h"
 
 namespace kagnn {
 

@@ -5,6 +5,7 @@
 // a 32-byte device record updated by one tiny launch (kagnn_early_stop_update), and the best-weights save is a copy predicated on
 // a device word (kagnn_copy_if) -- a loop built from them never has to read anything back.
 #include "common.h"
+#include "host.h"
 
 namespace kagnn {
 

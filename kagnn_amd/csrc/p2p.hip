@@ -11,6 +11,7 @@
 // contiguous (w*4 bytes per row and peer: 32 B at out = 64, P = 8 -- the transfer granularity, not the kernel, is the limit there).
 // The reference has no multi-GPU code; the contract is BASELINE.json's north_star.
 #include "common.h"
+#include "host.h"
 
 namespace kagnn {
 

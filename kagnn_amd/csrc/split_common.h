@@ -323,10 +323,9 @@ __device__ __forceinline__ void split_f16x2_asm(const float (&v)[8], u32x4& hi, 
 // conversion), after the same exact power-of-two pre-scale as the hi part of the split mode -- no `lo` operands, so a third of
 // the matrix-core work and about half of the conversion / placement VALU work.  fp32 accumulation as before.  The HALF
 // instantiations of the three KAN kernels read only the `hi` fragments of the split mode's weight packs (the packs' hi parts
-// are already RNE roundings of w * 2^-e).  The thread-local flag is set by the C entry points (api.hip: ModeScope) for the
-// duration of a call with mode == KAGNN_PREC_HALF; the launchers below pick the HALF instantiation where one exists and the
-// three-product kernels (more accurate, never less) elsewhere.
-extern thread_local bool g_half_products;
+// are already RNE roundings of w * 2^-e).  The thread-local flag g_half_products (common.h) is set by the C entry points (host.h:
+// ModeScope) for the duration of a call with mode == KAGNN_PREC_HALF; the launchers below pick the HALF instantiation where one
+// exists and the three-product kernels (more accurate, never less) elsewhere.
 __device__ __forceinline__ unsigned pk_f16_rne(float a, float b) {
     const f16x2 v = {(_Float16)a, (_Float16)b};
     return __builtin_bit_cast(unsigned, v);

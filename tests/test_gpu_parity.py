@@ -1007,7 +1007,7 @@ def test_library_calls_follow_the_current_stream():
 
 
 def test_two_host_threads_with_different_precision_modes_do_not_interfere():
-    """the library keeps its per-call state (precision mode of the call, error text, deferred reductions) in thread-local storage
+    """the library keeps its per-call state (precision mode of the call, error text) in thread-local storage
     and autograd runs every backward on its own thread: two host threads, each on its own stream, one in the three-product mode and
     one in KAGNN_PREC_HALF, 30 forward + backward passes each at different shapes -- every pass gives the bits of the same pass
     run alone"""
@@ -1663,3 +1663,129 @@ def test_second_pass_of_the_persistent_grids_vs_oracle(n, case):
         else:       # the split forward cuts a wide feature loop or a wide set of centres by ROW COUNT (and the FastKAN statistics pass sums over
                     # the row's features in its own order) -- the slice may sum in another order: 2e-6, as test_rccl_c_entry_points_*
             assert_close(ys, y.detach()[lo:hi], 2e-6, what=tag + " y rows across the pass boundary vs the slice alone")
+
+
+def _small_molecule_batch(seed=5):
+    """8 small graphs, about 200 nodes and 400 edges, one atom / bond feature column (the shape of a ZINC mini-batch, in small)"""
+    from types import SimpleNamespace
+    gen = torch.Generator().manual_seed(seed)
+    B = 8
+    sizes = torch.randint(20, 31, (B,), generator=gen)
+    off = torch.cumsum(sizes, 0) - sizes
+    src = torch.cat([torch.randint(0, int(sizes[b]), (2 * int(sizes[b]),), generator=gen) + off[b] for b in range(B)])
+    dst = torch.cat([torch.randint(0, int(sizes[b]), (2 * int(sizes[b]),), generator=gen) + off[b] for b in range(B)])
+    n = int(sizes.sum())
+    return SimpleNamespace(x=torch.randint(0, 21, (n, 1), generator=gen).to(DEV), edge_index=torch.stack([src, dst]).to(DEV),
+                           edge_attr=torch.randint(0, 4, (src.numel(),), generator=gen).to(DEV),
+                           batch=torch.cat([torch.full((int(sizes[b]),), b) for b in range(B)]).to(DEV), num_graphs=B), gen
+
+
+@pytest.mark.parametrize("nconv", [8, 9], ids=["16-layers-one-flush", "18-layers-no-arena"])
+def test_gine_stack_at_the_limit_of_deferred_slab_reductions(nconv):
+    """kagnn_gine_kan_stack_bwd keeps the row slabs of up to 16 KANLinears (kDwDeferMax) in an arena and reduces them in ONE launch
+    at the end of the call; kagnn_gine_kan_stack_fwd packs up to 16 layers in one launch.  8 convolutions x 2 layers is exactly the
+    limit (16 recorded reductions, one flush, one pack launch); 9 x 2 is past it (no arena: every weight gradient reduces its own
+    slabs; every convolution packs for itself) -- the Python stack plan refuses that one, so the tape node is applied directly (its
+    buffers are sized by kagnn_gine_kan_stack_workspace_bytes).  Either way: the per-convolution nodes' kernels in the same order,
+    so output, every parameter gradient, the input gradient and the edge-attribute gradient agree bit for bit.  Hidden 32, grid 4,
+    cubic splines, 8 small graphs."""
+    import copy
+    d, gen = _small_molecule_batch()
+    n, e, H, nl = d.x.size(0), d.edge_index.size(1), 32, 2
+    g = ops.GraphIndex(d.edge_index, n)
+    x0, ea0 = (torch.randn(n, H, generator=gen) * 0.5).to(DEV), (torch.randn(e, H, generator=gen) * 0.5).to(DEV)
+    wgt = torch.randn(n, H, generator=gen).to(DEV)
+    torch.manual_seed(nconv)
+    convs = torch.nn.ModuleList(kagnn_amd.graph_models.GINEKANLayer(kagnn_amd.models.make_kan(H, H, H, nl, 4, 3)) for _ in range(nconv)).to(DEV).train()
+    bns = torch.nn.ModuleList(kagnn_amd.BatchNorm1d(H) for _ in range(nconv)).to(DEV).train()
+    for bn in bns:                              # (not the identity affine: the norm's weight enters every gradient before it)
+        bn.weight.data.uniform_(0.5, 1.5); bn.bias.data.uniform_(-0.5, 0.5)
+    state = copy.deepcopy((convs.state_dict(), bns.state_dict()))
+    res = {}
+    for how in ("stack", "layer"):
+        convs.load_state_dict(state[0]); bns.load_state_dict(state[1])
+        convs.zero_grad(); bns.zero_grad()
+        x, ea = x0.clone().requires_grad_(True), ea0.clone().requires_grad_(True)
+        timer = ops.EntryPointTimer()
+        ops.set_timer(timer)
+        try:
+            if how == "layer":
+                h = x
+                for conv, bn in zip(convs, bns):
+                    h = conv.forward_fused_norm(h, g, ea, bn)
+                    assert h is not None
+            elif nconv * nl <= 16:
+                h = graph_ops.gine_kan_stack(x, ea, g, list(convs), list(bns))
+                assert h is not None
+            else:
+                assert graph_ops._gine_stack_plan(x, list(convs), list(bns)) is None
+                first = convs[0].nn.layers[0]
+                mode = first.precision if first.precision is not None else graph_ops.default_precision()
+                params, scales, running, momentum, eps = graph_ops._gine_stack_args(list(convs), list(bns))
+                h = graph_ops._GineKanStackFn.apply(x, ea, g, scales, first._knots(), first.grid_size, first.spline_order, mode, running,
+                                                    momentum, eps, nconv, nl, *params)
+            (h * wgt).sum().backward()
+        finally:
+            ops.set_timer(None)
+        names = [r[0] for r in timer.records]
+        grads = {f"conv.{k}": p.grad.clone() for k, p in convs.named_parameters()}
+        grads.update({f"bn.{k}": p.grad.clone() for k, p in bns.named_parameters()})
+        res[how] = (h.detach().clone(), grads, x.grad.clone(), ea.grad.clone(), {k: v.clone() for k, v in bns.state_dict().items()}, names)
+    sn, ln = res["stack"][5], res["layer"][5]
+    assert sn.count("kagnn_gine_kan_stack_fwd") == 1 and sn.count("kagnn_gine_kan_stack_bwd") == 1 and "kagnn_gine_kan_layer_fwd" not in sn, sn
+    assert ln.count("kagnn_gine_kan_layer_fwd") == nconv and ln.count("kagnn_gine_kan_layer_bwd") == nconv and "kagnn_gine_kan_stack_fwd" not in ln, ln
+    assert torch.equal(res["stack"][0], res["layer"][0])
+    assert len(res["stack"][1]) == nconv * (2 + 3 * nl) and set(res["stack"][1]) == set(res["layer"][1])
+    for k, gref in res["layer"][1].items():
+        assert torch.equal(res["stack"][1][k], gref), k
+    assert torch.equal(res["stack"][2], res["layer"][2]) and torch.equal(res["stack"][3], res["layer"][3])
+    for k, v in res["layer"][4].items():
+        assert torch.equal(res["stack"][4][k], v), k
+    assert bool(torch.isfinite(res["stack"][0]).all()) and float(res["stack"][2].abs().max()) > 0 and float(res["stack"][3].abs().max()) > 0
+
+
+@pytest.mark.parametrize("nr", [3, 2], ids=["17-layers-two-pack-launches", "16-layers-one-pack-launch"])
+def test_model_call_at_the_limit_of_the_shared_pack_launch(nr, monkeypatch):
+    """kagnn_kagin_model_fwd packs the stack's layers AND the read-out's in one launch while there are at most 16 of them
+    (nconv * nl + nr <= 16) and tells the stack that its packs are made; past that the stack packs for itself and the read-out
+    separately.  7 convolutions x 2 layers with a 3-layer read-out is 17, with a 2-layer read-out 16: either way the whole-model
+    call gives the bits of the model tape node (which runs the stack's and the read-out's entry points one by one).  Hidden 32,
+    grid 4, cubic splines, 8 small graphs."""
+    d, gen = _small_molecule_batch()
+    y = torch.randn(d.num_graphs, generator=gen).to(DEV)
+    torch.manual_seed(nr)
+    m = kagnn_amd.KAGINRegression(1, 1, 7, 32, 2, 4, 3, 1, 0.0, True)
+    m.atom_encoder = kagnn_amd.graph_models.AtomEncoder(32, [21])
+    m.bond_encoder.bond_embedding_list = torch.nn.ModuleList([torch.nn.Embedding(4, 32)])
+    m.kan = kagnn_amd.models.make_kan(32, 32, 1, nr, 4, 3)
+    assert len(m.kan.layers) == nr and len(m.conv) * len(m.conv[0].nn.layers) + nr == 14 + nr
+    m = m.to(DEV).train()
+    state = {k: v.clone() for k, v in m.state_dict().items()}
+    res = {}
+    for how in ("call", "model"):
+        monkeypatch.setattr(graph_ops, "_GINE_MODEL_CALL", how == "call")
+        monkeypatch.setattr(graph_ops, "_GINE_MODEL_NODE", True)
+        m.load_state_dict(state, strict=True)
+        m.zero_grad()
+        timer = ops.EntryPointTimer()
+        ops.set_timer(timer)
+        try:
+            pred = m(d)
+            loss = torch.nn.L1Loss()(pred.squeeze(), y)
+            loss.backward()
+        finally:
+            ops.set_timer(None)
+        res[how] = (pred.detach().clone(), float(loss.detach()), {k: p.grad.clone() for k, p in m.named_parameters()},
+                    {k: v.clone() for k, v in m.state_dict().items() if "running" in k or "num_batches" in k},
+                    [r[0] for r in timer.records], type(pred.grad_fn).__name__)
+    assert res["call"][5] == "_KaginModelCallFnBackward" and res["model"][5] == "_KaginModelFnBackward", (res["call"][5], res["model"][5])
+    cn, mn = res["call"][4], res["model"][4]
+    assert cn.count("kagnn_kagin_model_fwd") == 1 and cn.count("kagnn_kagin_model_bwd") == 1 and "kagnn_gine_kan_stack_fwd" not in cn, cn
+    assert mn.count("kagnn_gine_kan_stack_fwd") == 1 and mn.count("kagnn_gine_kan_stack_bwd") == 1 and "kagnn_kagin_model_fwd" not in mn, mn
+    assert torch.equal(res["call"][0], res["model"][0]) and res["call"][1] == res["model"][1]
+    assert set(res["call"][2]) == set(res["model"][2]) and len(res["model"][2]) == 2 + 7 * 8 + 3 * nr
+    for k, gref in res["model"][2].items():
+        assert torch.equal(res["call"][2][k], gref), k
+    for k, v in res["model"][3].items():
+        assert torch.equal(res["call"][3][k], v), k
+    assert bool(torch.isfinite(res["call"][0]).all()) and all(float(v.abs().max()) > 0 for v in res["call"][2].values())
