@@ -702,10 +702,29 @@ def _segment_pool_raw(x, seg, mean):
     return out
 
 
+_ZERO_ROWS: "dict[tuple, torch.Tensor]" = {}
+
+
 def _segment_broadcast_raw(gout, seg, n, mean):
+    """the gradient of ``_segment_pool_raw``.  The kernel writes the rows of ``[seg[0], seg[B])`` only; nothing pooled depends on
+    rows before ``seg[0]`` or from ``seg[B]`` on (a ``seg_ptr`` that does not span all ``n`` rows: ``segment_ptr`` with fewer graphs
+    than the batch vector names, or any caller-made one), so their gradient is zero: the same kernel broadcasts a zero row over
+    the two ranges ``[0, seg[0])`` and ``[seg[B], n)``, whose ends stay on the device (no host read of ``seg``, no pass over a
+    covered row)."""
     b, f = gout.shape
-    gx = torch.empty((n, f), dtype=torch.float32, device=gout.device)
+    dev = gout.device
+    if b == 0:
+        return torch.zeros((n, f), dtype=torch.float32, device=dev)
+    gx = torch.empty((n, f), dtype=torch.float32, device=dev)
     _call("kagnn_segment_broadcast", _ptr(gout), _ld(gout), _ptr(gx), f, _ptr(seg), b, f, int(mean), _stream())
+    zero = _ZERO_ROWS.get((dev.index, f))
+    if zero is None:
+        zero = _ZERO_ROWS[(dev.index, f)] = torch.zeros((1, f), dtype=torch.float32, device=dev)
+    ends = torch.full((4,), n, dtype=torch.int32, device=dev)          # [0, seg[0]] and [seg[B], n]: two one-segment pointers
+    ends[0:1].zero_()
+    ends[1:3].copy_(seg[::b])
+    _call("kagnn_segment_broadcast", _ptr(zero), f, _ptr(gx), f, _ptr(ends), 1, f, 0, _stream())
+    _call("kagnn_segment_broadcast", _ptr(zero), f, _ptr(gx), f, ctypes.c_void_p(ends.data_ptr() + 8), 1, f, 0, _stream())
     return gx
 
 
