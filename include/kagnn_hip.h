@@ -49,7 +49,7 @@ extern "C" {
 #define KAGNN_DTYPE_F32 0
 #define KAGNN_DTYPE_BF16 1
 
-int kagnn_version(void);          /* 265 = 264 + kagnn_node_eval, kagnn_early_stop_update, kagnn_copy_if; 264 = 263 + kagnn_degree_one_hot, kagnn_nll_loss_fwd / _bwd; 263 = 262 + kagnn_batch_assemble; 262 = 261 - the fields edge_src, edge_dst, csr_flags of kagnn_kagin_model_t; 261 = 260 + kagnn_fastkan_fwd_stats_in_kernel; 260 = round 6: + the feature-sharded FastKAN entry points kagnn_fastkan_row_moments .. _shard_bwd_finish, + kagnn_kagin_model_*; 250 = 240 + KAGNN_PREC_HALF; 240 = 230 + kagnn_gin_kan_layer_bwd_bn_sums; 230 = 220 + the *_affine entry points of a folded BatchNorm1d; 220 = 210 + the stage timer) */
+int kagnn_version(void);          /* 266 = 265 + kagnn_l1_loss_meter_fwd, kagnn_regression_epoch_update; 265 = 264 + kagnn_node_eval, kagnn_early_stop_update, kagnn_copy_if; 264 = 263 + kagnn_degree_one_hot, kagnn_nll_loss_fwd / _bwd; 263 = 262 + kagnn_batch_assemble; 262 = 261 - the fields edge_src, edge_dst, csr_flags of kagnn_kagin_model_t; 261 = 260 + kagnn_fastkan_fwd_stats_in_kernel; 260 = round 6: + the feature-sharded FastKAN entry points kagnn_fastkan_row_moments .. _shard_bwd_finish, + kagnn_kagin_model_*; 250 = 240 + KAGNN_PREC_HALF; 240 = 230 + kagnn_gin_kan_layer_bwd_bn_sums; 230 = 220 + the *_affine entry points of a folded BatchNorm1d; 220 = 210 + the stage timer) */
 const char* kagnn_last_error(void);
 
 /* Stage timer -- a measurement aid, off by default (no reference counterpart: the reference times whole epochs with
@@ -756,6 +756,43 @@ int kagnn_node_eval(const float* logits, int64_t ld, int64_t num_rows, int32_t n
 int kagnn_early_stop_update(const void* eval_records, int32_t num_splits, int32_t val_split, void* state, void* history,
                             int32_t max_epochs, void* stream);
 int kagnn_copy_if(const int32_t* flag, int32_t count, void* const* dst, const void* const* src, const int64_t* bytes, void* stream);
+
+/* What the graph-regression experiment wraps around its models (graph_regression/optuna_zinc.py:56-92, optuna_qm9.py:56-96:
+ * train_model_with_parameters; graph_regression/utils.py:8-16: EarlyStopper), without a read-back.  Both: one launch of one
+ * workgroup, no atomics, no host synchronisation, the same bits every run.
+ *
+ * kagnn_l1_loss_meter_fwd: pred and target are fp32 [rows, targets] with row strides ldp, ldt >= targets;
+ * 1 <= targets <= KAGNN_REGRESSION_MAX_TARGETS (more: KAGNN_ERR_ARG).  The term of an element is fabsf(p - t) with scale == NULL,
+ * else fabsf(t*s - p*s) / s with s = scale[column] (fp32 [targets]; optuna_qm9.py:72) -- every operation rounded to fp32 on its
+ * own, never contracted into a fused multiply-add, so a term has the bits torch's elementwise kernels give it.  Each column's
+ * terms are added in fp64 in a fixed order.  loss_mean (may be NULL) = (float)(sum of all terms / (rows * targets)), the column
+ * sums added in index order, rounded once; rows == 0: NaN.  meter (may be NULL; not both) is an 8-byte aligned device record
+ *   { int64_t graphs; int64_t targets; double abs_sum[KAGNN_REGRESSION_MAX_TARGETS]; }
+ * to which the launch ADDS rows and the column sums with plain loads and stores (launches on one stream are ordered) and whose
+ * `targets` it writes; rows == 0 leaves it untouched.  A NaN reaches its own column's sum and loss_mean only.  The backward of
+ * the unscaled loss is kagnn_l1_loss_bwd with n = rows * targets on contiguous operands.
+ *
+ * kagnn_regression_epoch_update: what the scripts decide once per epoch, from the three splits' meters.  test_meter == NULL: the
+ * validation meter (and n_val) serve as the test split.  n_train / n_val / n_test: the scripts' len(loader.dataset) divisors.
+ * Per split s and target t < the meter's `targets` (clamped to 0..32): mae[s][t] = abs_sum[t] / n_s in fp64; the split's figure
+ * is the mae added over the targets in index order, divided by their number, rounded once to fp32 (no targets: NaN).
+ * history (may be NULL): double [max_epochs][3][KAGNN_REGRESSION_MAX_TARGETS], 8-byte aligned; history[epochs][s][t] = mae[s][t]
+ * (0 for t at or beyond the meter's targets).  state: the 4-byte aligned device record
+ *   { float min_loss (start: +inf), min_delta, best_val (start: +inf), test_at_best (start: NaN);
+ *     int32_t patience, counter, epochs, best_epoch (start: -1), test_epoch (start: -1), improved, stopped, pad; }
+ * advanced with fp32 comparisons, in this order:
+ *   1. best_val >= val (optuna_zinc.py:75; a tie counts): best_val = val, test_at_best = the test figure, test_epoch = epochs;
+ *   2. val < min_loss: min_loss = val, counter = 0, best_epoch = epochs, improved = 1;
+ *      else val >= min_loss + min_delta: ++counter, stopped = 1 once counter >= patience; improved = 0;
+ *      anything else (NaN included): nothing; improved = 0;
+ *   3. ++epochs.
+ * With stopped set, or epochs == max_epochs, the launch writes improved = 0 and nothing else of the record or the history.  In
+ * every case it zeroes graphs and abs_sum of the three meters for the next epoch. */
+#define KAGNN_REGRESSION_MAX_TARGETS 32
+int kagnn_l1_loss_meter_fwd(const float* pred, int64_t ldp, const float* target, int64_t ldt, int64_t rows, int32_t targets,
+                            const float* scale, float* loss_mean, void* meter, void* stream);
+int kagnn_regression_epoch_update(void* train_meter, void* val_meter, void* test_meter, int64_t n_train, int64_t n_val,
+                                  int64_t n_test, void* state, double* history, int32_t max_epochs, void* stream);
 
 /* Optimiser of the same scripts (optuna_zinc.py:49,62: torch.optim.Adam(model.parameters(), lr), optimizer.step() per batch): one
  * update of `count` fp32 tensors in one launch per 32 tensors.  HOST arrays of device pointers / element counts; `step` = 1, 2, ...

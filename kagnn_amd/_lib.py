@@ -157,6 +157,8 @@ _SIGNATURES = {
     "kagnn_node_eval": (c_int32, [_P, c_int64, c_int64, c_int32, _P, _P, c_int32, _P, _P, _P, c_size_t, _P]),
     "kagnn_early_stop_update": (c_int32, [_P, c_int32, c_int32, _P, _P, c_int32, _P]),
     "kagnn_copy_if": (c_int32, [_P, c_int32, _P, _P, _P, _P]),
+    "kagnn_l1_loss_meter_fwd": (c_int32, [_P, c_int64, _P, c_int64, c_int64, c_int32, _P, _P, _P, _P]),
+    "kagnn_regression_epoch_update": (c_int32, [_P, _P, _P, c_int64, c_int64, c_int64, _P, _P, c_int32, _P]),
     "kagnn_adam_step": (c_int32, [c_int32, _P, _P, _P, _P, _P, c_float, c_float, c_float, c_float, c_float, c_int64, _P]),
     "kagnn_gat_logits": (c_int32, [_P, c_int64, c_int64, c_int32, c_int32, _P, _P, _P, _P, _P]),
     "kagnn_gat_fwd": (c_int32, [_P, c_int64, _P, _P, _P, _P, c_int64, c_int32, c_int32, _P, _P, c_int64, _P, _P, _P, c_int64,
@@ -209,6 +211,7 @@ class KaginModel(ctypes.Structure):
 
 
 BATCH_MAX_GRAPHS = 4096      # KAGNN_BATCH_MAX_GRAPHS
+REGRESSION_MAX_TARGETS = 32  # KAGNN_REGRESSION_MAX_TARGETS
 
 
 class BatchAssemble(ctypes.Structure):

@@ -82,7 +82,7 @@ using namespace kagnn;
 #pragma GCC visibility push(default)
 extern "C" {
 
-int kagnn_version(void) { return 265; }
+int kagnn_version(void) { return 266; }
 const char* kagnn_last_error(void) { return g_err; }
 
 int kagnn_stage_timer_enable(const char* only) {
@@ -944,6 +944,27 @@ int kagnn_copy_if(const int32_t* flag, int32_t count, void* const* dst, const vo
         KAGNN_CHECK_ARG((((uintptr_t)dst[k] | (uintptr_t)src[k]) & 3) == 0, "pointers are 4-byte aligned");
     }
     return copy_if(flag, count, dst, src, reinterpret_cast<const long*>(bytes), as_stream(stream));
+}
+
+// the graph-regression experiment's bookkeeping around the models (regress.hip)
+int kagnn_l1_loss_meter_fwd(const float* pred, int64_t ldp, const float* target, int64_t ldt, int64_t rows, int32_t targets,
+                            const float* scale, float* loss_mean, void* meter, void* stream) {
+    KAGNN_STAGE(stream);
+    KAGNN_CHECK_ARG(targets >= 1 && targets <= KAGNN_REGRESSION_MAX_TARGETS, "targets must be 1..KAGNN_REGRESSION_MAX_TARGETS (32)");
+    KAGNN_CHECK_ARG(rows >= 0 && ldp >= targets && ldt >= targets, "bad shape");
+    KAGNN_CHECK_ARG((loss_mean || meter) && (rows == 0 || (pred && target)), "null array");
+    KAGNN_CHECK_ARG(((uintptr_t)meter & 7) == 0, "the record must be 8-byte aligned");
+    return l1_loss_meter_fwd(pred, ldp, target, ldt, rows, targets, scale, loss_mean, meter, as_stream(stream));
+}
+
+int kagnn_regression_epoch_update(void* train_meter, void* val_meter, void* test_meter, int64_t n_train, int64_t n_val, int64_t n_test,
+                                  void* state, double* history, int32_t max_epochs, void* stream) {
+    KAGNN_STAGE(stream);
+    KAGNN_CHECK_ARG(train_meter && val_meter && state && max_epochs >= 0, "null record or negative epoch count");
+    KAGNN_CHECK_ARG((((uintptr_t)train_meter | (uintptr_t)val_meter | (uintptr_t)test_meter | (uintptr_t)history) & 7) == 0 &&
+                    ((uintptr_t)state & 3) == 0, "misaligned record");
+    return regression_epoch_update(train_meter, val_meter, test_meter, n_train, n_val, n_test, state, history, max_epochs,
+                                   as_stream(stream));
 }
 
 // ---------------------------------------------------------------- direct peer-to-peer exchange (p2p.hip)

@@ -208,6 +208,12 @@ int node_eval(const float* z, long ld, long N, int C, const long* y, const unsig
 int early_stop_update(const void* records, int S, int val_split, void* state, void* history, int max_epochs, hipStream_t st);
 int copy_if(const int* flag, int count, void* const* dst, const void* const* src, const long* bytes, hipStream_t st);
 
+// ---- regress.hip
+int l1_loss_meter_fwd(const float* pred, long ldp, const float* target, long ldt, long rows, int T, const float* scale, float*
+                      loss_mean, void* meter, hipStream_t st);
+int regression_epoch_update(void* train_meter, void* val_meter, void* test_meter, long n_train, long n_val, long n_test, void* state,
+                            double* history, int max_epochs, hipStream_t st);
+
 // ---- p2p.hip
 int p2p_reduce_scatter(const float* const* parts, int P, int rank, long N, int out, long ld, float* y, long ldy, hipStream_t st);
 int p2p_all_gather(const float* const* shards, int P, long N, int w, long lds, float* g, long ldg, hipStream_t st);

@@ -56,6 +56,33 @@ def batch_plan(node_ptr: torch.Tensor, edge_ptr: torch.Tensor, ids: torch.Tensor
     return starts.tolist(), (ends - starts).tolist(), (cn[ends] - cn[starts]).tolist(), (ce[ends] - ce[starts]).tolist()
 
 
+def random_split_ids(n: int, fractions_or_lengths, generator: Optional[torch.Generator] = None):
+    """The index tensors of ``torch.utils.data.random_split(range(n), fractions_or_lengths, generator)`` -- its subsets' ``.indices``,
+    int64, CPU -- as the graph-regression scripts draw their train / validation / test sets (``graph_regression/optuna_qm9.py``:
+    ``random_split(dataset, [0.8, 0.1, 0.1], generator)``): ``ds[ids]`` is the reference's subset.  Fractions that sum to 1 become
+    ``floor(n * fraction)`` each, the remainder handed out one by one from the first split on; explicit lengths must sum to ``n``;
+    one ``torch.randperm(n, generator=generator)`` is cut into consecutive runs.  ``generator=None``: torch's default generator, as
+    ``random_split`` uses.  Host only."""
+    import math
+    n, parts = int(n), list(fractions_or_lengths)
+    if n < 0 or not parts:
+        raise ValueError("random_split_ids: n >= 0 and at least one split")
+    if math.isclose(sum(parts), 1) and sum(parts) <= 1:
+        if any(f < 0 or f > 1 for f in parts):
+            raise ValueError("random_split_ids: fractions lie between 0 and 1")
+        lengths = [math.floor(n * f) for f in parts]
+        for k in range(n - sum(lengths)):
+            lengths[k % len(lengths)] += 1
+    else:
+        lengths = [int(v) for v in parts]
+        if any(v != int(v) or v < 0 for v in parts):
+            raise ValueError("random_split_ids: lengths are non-negative integers (or fractions that sum to 1)")
+    if sum(lengths) != n:
+        raise ValueError(f"random_split_ids: the lengths {lengths} do not add up to n = {n}")
+    order = torch.randperm(n, generator=generator) if generator is not None else torch.randperm(n)
+    return list(torch.split(order, lengths))
+
+
 def read_splits(path):
     """The reference's 10-fold split files (``graph_classification/data_splits/<dataset>_splits.json``, read at
     ``graph_classification_utils.py:88-91`` and used at ``:103-124``): ONE line of JSON,
@@ -262,6 +289,32 @@ class DeviceGraphDataset:
     @property
     def device(self) -> torch.device:
         return self._store.device
+
+    def standardize_targets(self, columns=None):
+        """``(dataset, mean, std)``: the targets of the WHOLE storage standardised as the QM9 script does before it splits
+        (``graph_regression/optuna_qm9.py:145-149``): ``y = y[:, columns]`` when ``columns`` (a slice or a list of column indices)
+        is given, ``mean = y.mean(0, keepdim=True)``, ``std = y.std(0, keepdim=True)`` (unbiased), ``y = (y - mean) / std``.  The
+        returned dataset shares every other array with this one (and keeps this view's selection); ``mean`` and ``std`` are
+        ``[1, T]`` device tensors -- ``std`` is what ``l1_loss(scale=...)`` and ``train_graph_regression(target_scale=...)`` take.
+        Plain torch on the device, once per dataset."""
+        st = self._store
+        if st.y is None or not st.y.is_floating_point():
+            raise TypeError("standardize_targets: the dataset needs floating-point targets y [G] or [G, T]")
+        y = st.y if st.y.dim() > 1 else st.y.reshape(-1, 1)
+        if y.dim() != 2:
+            raise TypeError(f"standardize_targets: targets are [G] or [G, T], got {tuple(st.y.shape)}")
+        if columns is not None:
+            y = y[:, columns]
+        mean, std = y.mean(dim=0, keepdim=True), y.std(dim=0, keepdim=True)
+        new = _Storage()
+        for k in _Storage.__slots__:
+            if hasattr(st, k):
+                setattr(new, k, getattr(st, k))
+        new.y = ((y - mean) / std).contiguous()
+        new.y_row_bytes = _row_bytes(new.y)
+        out = object.__new__(type(self))
+        out._store, out._index = new, self._index
+        return out, mean, std
 
     # -- the descriptive attributes the reference's scripts read off a dataset
     @property

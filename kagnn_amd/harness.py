@@ -14,6 +14,7 @@ precomputed index instead of boolean indexing (which would synchronise inside th
 from __future__ import annotations
 
 import time
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -445,6 +446,186 @@ def evaluate_graph_classification(model, loader):
     nll_sum, correct, graphs = meter.read()
     n = max(_dataset_size(loader, graphs), 1)
     return nll_sum / n, correct / n
+
+
+class GraphRegressionResult(NamedTuple):
+    """what ``train_graph_regression`` returns.  ``best_val_loss`` / ``test_loss``: what the reference's
+    ``train_model_with_parameters`` returns -- the lowest validation figure (ties included) and the test figure of the last epoch
+    that reached it (``test_epoch``; without a test loader: that validation figure).  ``epochs_run`` / ``best_epoch`` / ``stopped``
+    as the device record counted them (``best_epoch``: the last STRICT improvement, the epoch ``keep_best`` restores).
+    ``train_losses`` / ``val_losses`` / ``test_losses``: one figure per counted epoch, rounded once to fp32 as the device compared
+    them; ``per_target``: the per-target mean absolute errors behind them, a CPU float64 ``[epochs_run, 3, T]`` tensor (splits in
+    the order train, val, test)"""
+    best_val_loss: float
+    test_loss: float
+    epochs_run: int
+    best_epoch: int
+    test_epoch: int
+    stopped: bool
+    train_losses: list
+    val_losses: list
+    test_losses: list
+    per_target: torch.Tensor
+
+
+def _regression_targets(loader) -> int:
+    """the number of regression targets of a loader's graphs: 1 for ``y [G]``, T for ``y [G, T]``"""
+    ds = getattr(loader, "dataset", None)
+    y = ds.storage.y if ds is not None and hasattr(ds, "storage") else None
+    if y is None and isinstance(loader, (list, tuple)) and loader:
+        y = loader[0].y
+    if y is None:
+        raise TypeError("graph regression needs a kagnn_amd.data.DeviceBatchLoader over a dataset with targets, or a list of batches")
+    return 1 if y.dim() == 1 else int(y.size(1))
+
+
+def _loader_size(loader) -> int:
+    """``len(loader.dataset)``, the divisor of the reference's loops; for a plain list of batches, the graphs it holds"""
+    ds = getattr(loader, "dataset", None)
+    return len(ds) if ds is not None else int(sum(_graphs_in(d) for d in loader))
+
+
+def _regression_output(model, data):
+    """``model(data)`` shaped like ``data.y``: ``[B, 1]`` against ``[B]`` loses its last axis (the scripts' ``.squeeze()``, which would
+    also drop the batch axis of a one-graph batch)"""
+    out = model(data)
+    if out.dim() == 2 and out.size(1) == 1 and data.y.dim() == 1:
+        out = out.squeeze(-1)
+    return out
+
+
+def _figures(per_target: torch.Tensor) -> list:
+    """a split's figure per epoch from its ``[epochs, T]`` per-target means, as ``kagnn_regression_epoch_update`` takes it: added in
+    index order in fp64, divided by T, rounded once to fp32"""
+    out = []
+    for row in per_target.tolist():
+        acc = 0.0
+        for v in row:
+            acc += v
+        out.append(float(np.float32(acc / len(row))) if row else float("nan"))
+    return out
+
+
+def train_graph_regression(model, train_loader, val_loader, test_loader=None, epochs: int = 1000, lr: float = 1e-3, patience: int = 20,
+                           min_delta: float = 0.0, poll_every: int = 8, optimizer=None, loss_fn=None, target_scale=None,
+                           keep_best: bool = False) -> GraphRegressionResult:
+    """The graph-regression experiment of the reference (``graph_regression/optuna_zinc.py:38-92`` and ``optuna_qm9.py:38-96``,
+    ``train_model_with_parameters``): per epoch a training pass with the L1 loss and Adam, a validation pass in ``eval()`` mode, the
+    test pass whenever ``best_val_loss >= val_loss``, and ``EarlyStopper(patience)``; it returns the test figure at the best
+    validation figure.  Here an epoch never reads anything back:
+    * the training pass is ``train_graph_batches``' step (autograd on the calling thread, a cached root gradient,
+      ``kagnn_amd.harness.Adam`` unless an optimiser is passed) with ``ops.l1_loss(pred, data.y, accumulate=train_meter)``: the
+      launch that makes the loss also adds the batch's per-target absolute errors to a device record;
+    * the validation and the test pass run under ``no_grad`` in ``eval()`` mode into meters of their own, with ``target_scale`` (the
+      targets' standard deviation, fp32 ``[T]`` or ``[1, T]``) as ``scale`` -- the QM9 script's ``(y * std - pred * std).abs() / std``;
+      ``None`` is the ZINC script's plain L1 figure.  THE TEST PASS RUNS EVERY EPOCH: skipping it on a miss would need the
+      comparison's outcome on the host, i.e. a read-back per epoch.  The figure reported is still the one of the epochs where the
+      script would have computed it (the device record takes it exactly when ``best_val >= val``);
+    * ``ops.RegressionStop.update`` -- one tiny launch -- turns the three meters into the epoch's figures, applies both of the
+      script's rules, files the figures in the history and zeroes the meters; with ``keep_best=True`` an ``ops.copy_if(improved,
+      snapshot, live)`` over every ``state_dict`` entry follows and the snapshot (the weights of ``best_epoch``; the starting weights
+      if no epoch counted) is loaded back at the end -- the scripts keep the last weights, which is the default here.
+    The deferred graph checks are flushed once per epoch (one wait on the epoch's queue; the composition of
+    ``train_graph_batches`` and two ``evaluate_graph_batches`` waits three times and reads two figures back).  The host reads the
+    48-byte record every ``poll_every`` epochs and once, with the history, at the end; it leaves the loop at the first poll that
+    sees the stop, and epochs run after the stop change neither the record nor the history nor the snapshot (they do train the
+    live weights).  ``poll_every=1`` is the script's one synchronisation per epoch.
+    ``loss_fn`` (e.g. ``torch.nn.L1Loss()``): that function drives the backward and the meter is fed by a second, ``no_grad``
+    metered call on the same prediction; with it and ``optimizer=torch.optim.Adam(..., fused=True)`` the parameter trajectory is
+    the script's, bit for bit.  The loaders: ``kagnn_amd.data.DeviceBatchLoader``s (divisor: ``len(loader.dataset)``) or lists of
+    premade batches.  ``test_loader=None``: the validation figures stand in (the script then returns ``best_val_loss``).  Leaves
+    the model in evaluation mode, as the scripts do."""
+    from . import ops as ops_mod
+    epochs, poll_every = int(epochs), max(1, int(poll_every))
+    params = list(model.parameters())
+    ops_mod._need_cuda(*params, target_scale)
+    if not params:
+        raise ValueError("train_graph_regression: the model has no parameters")
+    dev = params[0].device
+    targets = _regression_targets(train_loader)
+    sizes = (_loader_size(train_loader), _loader_size(val_loader), _loader_size(val_loader if test_loader is None else test_loader))
+    scale = None
+    if target_scale is not None:
+        scale = target_scale.detach().to(torch.float32).reshape(-1).contiguous()
+        if scale.numel() != targets:
+            raise ValueError(f"train_graph_regression: target_scale has {scale.numel()} entries for {targets} targets")
+    if optimizer is None:
+        optimizer = Adam(params, lr=lr)
+    meters = [ops_mod.RegressionMeter(targets, dev) for _ in range(2 if test_loader is None else 3)]
+    train_meter, val_meter, test_meter = meters[0], meters[1], (None if test_loader is None else meters[2])
+    stop = ops_mod.RegressionStop(patience, min_delta, max_epochs=epochs, num_targets=targets, device=dev)
+    live = snapshot = None
+    if keep_best:
+        live = list(model.state_dict().values())
+        if any(not t.is_contiguous() for t in live):
+            raise ValueError("train_graph_regression: every state_dict entry must be contiguous (the snapshot copies them as bytes)")
+        snapshot = [t.detach().clone() for t in live]
+    root = None
+    mt_was = torch.autograd.is_multithreading_enabled()
+    torch.autograd.set_multithreading_enabled(False)              # (a ~1 ms backward of short kernels: see _train_minibatches)
+    try:
+        for epoch in range(epochs):
+            model.train()
+            for data in train_loader:
+                optimizer.zero_grad(set_to_none=True)
+                pred = _regression_output(model, data)
+                if loss_fn is None:
+                    loss = ops_mod.l1_loss(pred, data.y, accumulate=train_meter)
+                else:
+                    loss = loss_fn(pred, data.y)
+                    with torch.no_grad():
+                        ops_mod.l1_loss(pred.detach(), data.y, accumulate=train_meter)
+                if root is None or root.shape != loss.shape or root.dtype != loss.dtype:
+                    root = torch.ones_like(loss)
+                loss.backward(root)
+                optimizer.step()
+            model.eval()
+            with torch.no_grad():
+                for loader, meter in ((val_loader, val_meter), (test_loader, test_meter)):
+                    if loader is not None:
+                        for data in loader:
+                            ops_mod.l1_loss(_regression_output(model, data), data.y, accumulate=meter, scale=scale)
+            stop.update(train_meter, val_meter, test_meter, sizes)
+            if keep_best:
+                ops_mod.copy_if(stop.improved, snapshot, live)
+            ops_mod.flush_graph_checks()       # the epoch's deferred checks (three loaders' batches): one wait per epoch
+            if (epoch + 1) % poll_every == 0 and stop.read(history=False).stopped:
+                break
+    finally:
+        torch.autograd.set_multithreading_enabled(mt_was)
+    ops_mod.flush_graph_checks()
+    st = stop.read()
+    if keep_best:
+        with torch.no_grad():
+            for t, saved in zip(live, snapshot):
+                t.copy_(saved)
+    model.eval()
+    hist = st.history
+    return GraphRegressionResult(best_val_loss=st.best_val, test_loss=st.test_at_best, epochs_run=st.epochs, best_epoch=st.best_epoch,
+                                 test_epoch=st.test_epoch, stopped=st.stopped, train_losses=_figures(hist[:, 0]),
+                                 val_losses=_figures(hist[:, 1]), test_losses=_figures(hist[:, 2]), per_target=hist)
+
+
+def evaluate_graph_regression(model, loader, target_scale=None):
+    """One evaluation pass of the same scripts (``optuna_zinc.py:68-73``, ``optuna_qm9.py:68-75``: ``model.eval()``, no gradients, the
+    absolute errors summed per target over the batches, divided by ``len(loader.dataset)``, averaged over the targets):
+    ``(mean, per-target MAE)`` -- the figure rounded once to fp32 as ``train_graph_regression`` reports it, and a CPU float64
+    ``[T]`` tensor.  ``target_scale`` as there.  One metered ``ops.l1_loss`` launch per batch; the deferred graph checks are flushed
+    and the meter is read back ONCE, at the end.  Leaves the model in evaluation mode."""
+    from . import ops as ops_mod
+    params = list(model.parameters())
+    ops_mod._need_cuda(*params, target_scale)
+    targets = _regression_targets(loader)
+    scale = None if target_scale is None else target_scale.detach().to(torch.float32).reshape(-1).contiguous()
+    meter = ops_mod.RegressionMeter(targets, params[0].device)
+    model.eval()
+    with torch.no_grad():
+        for data in loader:
+            ops_mod.l1_loss(_regression_output(model, data), data.y, accumulate=meter, scale=scale)
+    ops_mod.flush_graph_checks()
+    abs_sum, graphs = meter.read()
+    per_target = abs_sum / float(_dataset_size(loader, graphs))
+    return _figures(per_target[None])[0], per_target
 
 
 class NodeClassificationResult:

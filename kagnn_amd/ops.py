@@ -1898,13 +1898,91 @@ class _L1LossFn(Function):
         return gp, None
 
 
-def l1_loss(pred, target) -> torch.Tensor:
+class RegressionMeter:
+    """The running figures of one pass of the reference's graph-regression loops (``graph_regression/optuna_zinc.py:64,72,81``:
+    ``loss.item() * data.num_graphs`` per batch; ``optuna_qm9.py:69-75``: a ``[1, 12]`` per-target absolute error) as a 272-byte
+    DEVICE record ``{int64 graphs; int64 targets; double abs_sum[32]}`` that ``l1_loss(..., accumulate=meter)`` adds to inside its
+    one launch.  ``reset()`` is two asynchronous fills (the target count stays), ``read()`` ONE read-back: ``(abs_sum[num_targets]`` as a float64
+    CPU tensor, ``graphs)``."""
+
+    def __init__(self, num_targets: int = 1, device="cuda"):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("kagnn_amd.ops.RegressionMeter keeps its record on an MI355X (kagnn_l1_loss_meter_fwd adds to it there); "
+                               f"got device '{device}'. There is no CPU fallback in this package.")
+        if not 1 <= int(num_targets) <= _lib.REGRESSION_MAX_TARGETS:
+            raise ValueError(f"RegressionMeter: num_targets must be 1..{_lib.REGRESSION_MAX_TARGETS}, got {num_targets}")
+        self.num_targets = int(num_targets)
+        host = torch.zeros(2 + _lib.REGRESSION_MAX_TARGETS, dtype=torch.int64)
+        host[1] = self.num_targets
+        self.record = host.to(device)
+
+    def reset(self) -> None:
+        self.record[0].zero_()
+        self.record[2:].zero_()
+
+    def read(self) -> Tuple[torch.Tensor, int]:
+        host = self.record.cpu()
+        return host[2:2 + self.num_targets].view(torch.float64).clone(), int(host[0])
+
+
+class _L1LossMeterFn(Function):
+    @staticmethod
+    @_on_operand_device
+    def forward(ctx, pred, target, meter, scale):
+        p = pred.to(torch.float32)
+        t = target.to(torch.float32)
+        p = _rows(p if p.dim() == 2 else p.reshape(-1, 1))
+        t = _rows(t if t.dim() == 2 else t.reshape(-1, 1))
+        b, c = p.shape
+        out = torch.empty(1, dtype=torch.float32, device=p.device)
+        _call("kagnn_l1_loss_meter_fwd", _ptr(p), _ld(p), _ptr(t), _ld(t), b, c, _ptr(scale), _ptr(out),
+              None if meter is None else _ptr(meter.record), _stream())
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(p.contiguous(), t.contiguous())
+        ctx.pred_shape = pred.shape
+        return out[0]
+
+    @staticmethod
+    @once_differentiable
+    @_on_operand_device
+    def backward(ctx, gloss):
+        p, t = ctx.saved_tensors
+        g = gloss.to(torch.float32).contiguous()
+        gp = torch.empty_like(p)
+        _call("kagnn_l1_loss_bwd", _ptr(p), _ptr(t), p.numel(), _ptr(g), _ptr(gp), _stream())
+        return gp.view(ctx.pred_shape), None, None, None
+
+
+def l1_loss(pred, target, accumulate: Optional[RegressionMeter] = None, scale: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``torch.nn.L1Loss()(pred, target)`` (mean absolute error; the loss of the reference's graph-regression scripts,
     ``graph_regression/optuna_zinc.py:58``) as one kernel each way; same shapes required (no broadcasting -- L1Loss warns about it
-    and the scripts squeeze the prediction for that reason); the target gets no gradient."""
+    and the scripts squeeze the prediction for that reason); the target gets no gradient.
+    ``accumulate``: a ``RegressionMeter`` on the same device to which the same launch adds the batch's per-target sums of absolute
+    errors and its number of rows (``kagnn_l1_loss_meter_fwd``: ``[B]`` or ``[B, T]`` operands, ``T <= 32``; the column sums and the
+    returned mean are taken in fp64 and rounded once; the gradient is the plain path's, bit for bit).  ``scale``: fp32 ``[T]`` -- the
+    QM9 script's de-standardised error ``(y * std - pred * std).abs() / std`` (``optuna_qm9.py:72``) with torch's fp32 roundings;
+    an evaluation figure: refused when ``pred`` requires a gradient.  With neither, the call is what it always was."""
     if pred.shape != target.shape:
         raise ValueError(f"l1_loss: prediction {tuple(pred.shape)} and target {tuple(target.shape)} must have the same shape")
-    return _L1LossFn.apply(pred, target)
+    if accumulate is None and scale is None:
+        return _L1LossFn.apply(pred, target)
+    _need_cuda(pred, target, None if accumulate is None else accumulate.record, scale)
+    if pred.dim() not in (1, 2):
+        raise ValueError(f"l1_loss: with accumulate / scale the operands are [B] or [B, T]; got {tuple(pred.shape)}")
+    targets = 1 if pred.dim() == 1 else int(pred.size(1))
+    if not 1 <= targets <= _lib.REGRESSION_MAX_TARGETS:
+        raise ValueError(f"l1_loss: with accumulate / scale the number of targets must be 1..{_lib.REGRESSION_MAX_TARGETS} "
+                         f"(KAGNN_REGRESSION_MAX_TARGETS), got {targets}")
+    if accumulate is not None and accumulate.num_targets != targets:
+        raise ValueError(f"l1_loss: the meter was made for {accumulate.num_targets} targets, the prediction has {targets}")
+    if scale is not None:
+        if pred.requires_grad:
+            raise ValueError("l1_loss: scale is an evaluation figure (optuna_qm9.py:72); it is refused when pred requires a gradient")
+        if scale.dtype != torch.float32 or scale.numel() != targets:
+            raise ValueError(f"l1_loss: scale is an fp32 tensor of {targets} elements, got {scale.dtype} {tuple(scale.shape)}")
+        scale = scale.detach().reshape(-1).contiguous()
+    return _L1LossMeterFn.apply(pred, target, accumulate, scale)
 
 
 # ======================================================================== graph classification: Degree, nll_loss, the epoch's meter
@@ -2151,6 +2229,70 @@ class EarlyStop:
         f, i = host[:1].view(torch.float32).tolist(), host[:4].view(torch.int32).tolist()
         hist = host[4:].view(self.max_epochs, self.num_splits, 3)[:i[4]] if history else None
         return EarlyStopState(f[0], f[1], i[2], i[3], i[4], i[5], bool(i[6]), bool(i[7]), hist)
+
+
+class RegressionStopState(NamedTuple):
+    """what ``RegressionStop.read()`` returns: the device record's fields and ``history`` -- the per-target mean absolute errors of
+    the counted epochs as a CPU float64 ``[epochs, 3, num_targets]`` tensor, splits in the order train, val, test (``None`` when
+    not asked for)"""
+    min_loss: float
+    min_delta: float
+    best_val: float
+    test_at_best: float
+    patience: int
+    counter: int
+    epochs: int
+    best_epoch: int
+    test_epoch: int
+    improved: bool
+    stopped: bool
+    history: Optional[torch.Tensor]
+
+
+class RegressionStop:
+    """What the reference's graph-regression scripts decide once per epoch (``graph_regression/optuna_zinc.py:75-86``: ``if
+    best_val_loss >= val_loss`` take the test figure; ``EarlyStopper(patience)``, ``graph_regression/utils.py:8-16``) as a 48-byte
+    DEVICE record that ``update(train, val, test, sizes)`` advances with one tiny launch (``kagnn_regression_epoch_update``) from
+    the three splits' ``RegressionMeter``s -- which the launch also zeroes for the next epoch.  Every counted epoch's per-target
+    figures are kept in ``history`` behind the record, in ONE buffer, so ``read()`` is one copy.  ``improved`` is the device word
+    ``copy_if`` takes as its flag.  Once stopped (or after ``max_epochs`` updates) further updates only clear ``improved``."""
+    _HEAD = 6                                                    # the record: 48 bytes = 6 words of 8
+
+    def __init__(self, patience: int, min_delta: float = 0.0, max_epochs: int = 1000, num_targets: int = 1, device="cuda"):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("kagnn_amd.ops.RegressionStop keeps its record on an MI355X (kagnn_regression_epoch_update advances it "
+                               f"there); got device '{device}'. There is no CPU fallback in this package.")
+        if not 1 <= int(num_targets) <= _lib.REGRESSION_MAX_TARGETS or int(max_epochs) < 0:
+            raise ValueError(f"RegressionStop: num_targets 1..{_lib.REGRESSION_MAX_TARGETS} and max_epochs >= 0")
+        self.num_targets, self.max_epochs = int(num_targets), int(max_epochs)
+        host = torch.zeros(self._HEAD + self.max_epochs * 3 * _lib.REGRESSION_MAX_TARGETS, dtype=torch.int64)
+        f, i = host[:2].view(torch.float32), host[:self._HEAD].view(torch.int32)
+        f[0], f[1], f[2], f[3] = float("inf"), float(min_delta), float("inf"), float("nan")
+        i[4], i[7], i[8] = int(patience), -1, -1
+        self._buf = host.to(device)
+        self.state = self._buf[:self._HEAD].view(torch.int32)
+        self.improved = self.state[9:10]
+        self.history = self._buf[self._HEAD:].view(torch.float64).view(self.max_epochs, 3, _lib.REGRESSION_MAX_TARGETS)
+
+    def update(self, train: RegressionMeter, val: RegressionMeter, test: Optional[RegressionMeter], sizes) -> None:
+        """``sizes``: the three ``len(loader.dataset)`` divisors (train, val, test); ``test=None``: the validation meter"""
+        n_train, n_val, n_test = (int(n) for n in sizes)
+        for m in (train, val, test):
+            if m is not None and (not isinstance(m, RegressionMeter) or m.record.device != self._buf.device):
+                raise ValueError(f"RegressionStop.update: the meters are RegressionMeters on {self._buf.device}")
+        with _device_of(self._buf):
+            _call("kagnn_regression_epoch_update", _ptr(train.record), _ptr(val.record), None if test is None else _ptr(test.record),
+                  n_train, n_val, n_test, _ptr(self.state), _ptr(self.history) if self.max_epochs else None, self.max_epochs, _stream())
+
+    def read(self, history: bool = True) -> RegressionStopState:
+        """ONE read-back: the record, and with ``history`` the counted rows of the history (a poll needs the record alone)"""
+        host = (self._buf if history else self._buf[:self._HEAD]).cpu()
+        f, i = host[:2].view(torch.float32).tolist(), host[:self._HEAD].view(torch.int32).tolist()
+        hist = None
+        if history:
+            hist = host[self._HEAD:].view(torch.float64).view(self.max_epochs, 3, _lib.REGRESSION_MAX_TARGETS)[:i[6], :, :self.num_targets]
+        return RegressionStopState(f[0], f[1], f[2], f[3], i[4], i[5], i[6], i[7], i[8], bool(i[9]), bool(i[10]), hist)
 
 
 _COPY_IF_TABLES: dict = {}
