@@ -49,7 +49,7 @@ extern "C" {
 #define KAGNN_DTYPE_F32 0
 #define KAGNN_DTYPE_BF16 1
 
-int kagnn_version(void);          /* 266 = 265 + kagnn_l1_loss_meter_fwd, kagnn_regression_epoch_update; 265 = 264 + kagnn_node_eval, kagnn_early_stop_update, kagnn_copy_if; 264 = 263 + kagnn_degree_one_hot, kagnn_nll_loss_fwd / _bwd; 263 = 262 + kagnn_batch_assemble; 262 = 261 - the fields edge_src, edge_dst, csr_flags of kagnn_kagin_model_t; 261 = 260 + kagnn_fastkan_fwd_stats_in_kernel; 260 = round 6: + the feature-sharded FastKAN entry points kagnn_fastkan_row_moments .. _shard_bwd_finish, + kagnn_kagin_model_*; 250 = 240 + KAGNN_PREC_HALF; 240 = 230 + kagnn_gin_kan_layer_bwd_bn_sums; 230 = 220 + the *_affine entry points of a folded BatchNorm1d; 220 = 210 + the stage timer) */
+int kagnn_version(void);          /* 267 = 266 + kagnn_linear_fwd, kagnn_linear_bwd_input, kagnn_linear_bwd_weight (+ _workspace_bytes); 266 = 265 + kagnn_l1_loss_meter_fwd, kagnn_regression_epoch_update; 265 = 264 + kagnn_node_eval, kagnn_early_stop_update, kagnn_copy_if; 264 = 263 + kagnn_degree_one_hot, kagnn_nll_loss_fwd / _bwd; 263 = 262 + kagnn_batch_assemble; 262 = 261 - the fields edge_src, edge_dst, csr_flags of kagnn_kagin_model_t; 261 = 260 + kagnn_fastkan_fwd_stats_in_kernel; 260 = round 6: + the feature-sharded FastKAN entry points kagnn_fastkan_row_moments .. _shard_bwd_finish, + kagnn_kagin_model_*; 250 = 240 + KAGNN_PREC_HALF; 240 = 230 + kagnn_gin_kan_layer_bwd_bn_sums; 230 = 220 + the *_affine entry points of a folded BatchNorm1d; 220 = 210 + the stage timer) */
 const char* kagnn_last_error(void);
 
 /* Stage timer -- a measurement aid, off by default (no reference counterpart: the reference times whole epochs with
@@ -693,6 +693,31 @@ int kagnn_softmax_xent_bwd(const float* logits, int64_t ld, int64_t num_rows, in
  * loss / g_loss: device scalars; one launch each way, deterministic (fixed summation order), no host sync. */
 int kagnn_l1_loss_fwd(const float* pred, const float* target, int64_t n, float* loss, void* stream);
 int kagnn_l1_loss_bwd(const float* pred, const float* target, int64_t n, const float* g_loss, float* g_pred, void* stream);
+
+/* The dense layer of the MLP baselines (torch.nn.Linear, with the torch.nn.ReLU that follows it inside the reference's make_mlp
+ * chains; the `lin` of torch_geometric's GCNConv / GATConv):
+ *   y[N,out] = x[N,in] @ W[out,in]^T (+ bias[out]) (then max(., 0) when relu = 1)
+ * x, y, gy, gx are row-major with a row stride (ld*, in elements) and unit column stride; W [out,in], gW [out,in], bias and
+ * gb [out] are contiguous.  Any N >= 0, in >= 1, out >= 1; nothing outside [N, width] of an operand is read or written (the
+ * columns between width and ld keep their bytes).
+ * Precision: exact fp32 products on the fp32-input matrix instructions, i.e. an ordered fp32 fma chain per output element, in
+ * EVERY precision mode -- KAGNN_PREC_* / KAGNN_PRECISION do not apply to these entry points.
+ * Mask rule of the gradients: `y` is the SAVED forward output of a relu = 1 call, or NULL for a layer without the fused ReLU.
+ * With y given, gy is read as gy (.) m, m = (y > 0): torch's threshold_backward on the result, so the gradient is 0 where
+ * y == 0.  With y == NULL, m is all ones.
+ *   kagnn_linear_bwd_input :  gx[N,in]  = (gy (.) m) @ W
+ *   kagnn_linear_bwd_weight:  gW[out,in] = (gy (.) m)^T @ x ,  gb[out] = column sums of gy (.) m   (gb may be NULL)
+ * Determinism: no atomics.  The weight gradient sums the rows in slabs held in `workspace`
+ * (kagnn_linear_bwd_weight_workspace_bytes: slabs * out * (in + 1) floats; 16-byte aligned) and adds the slabs in index order,
+ * so the same inputs give bit-identical gW and gb from run to run.  N == 0: y / gx are not touched, gW and gb are set to 0. */
+int kagnn_linear_bwd_weight_workspace_bytes(int64_t num_rows, int32_t in_features, int32_t out_features, size_t* bytes_host);
+int kagnn_linear_fwd(const float* x, int64_t ldx, int64_t num_rows, int32_t in_features, const float* weight, const float* bias,
+                     int32_t out_features, int32_t relu, float* y, int64_t ldy, void* stream);
+int kagnn_linear_bwd_input(const float* gy, int64_t ldgy, const float* y, int64_t ldy, int64_t num_rows, int32_t out_features,
+                           const float* weight, int32_t in_features, float* gx, int64_t ldgx, void* stream);
+int kagnn_linear_bwd_weight(const float* x, int64_t ldx, const float* gy, int64_t ldgy, const float* y, int64_t ldy,
+                            int64_t num_rows, int32_t in_features, int32_t out_features, float* g_weight, float* g_bias,
+                            void* workspace, size_t workspace_bytes, void* stream);
 
 /* What the graph-classification scripts wrap around their models (graph_classification/graph_classification_utils.py).
  *

@@ -14,6 +14,9 @@ from .norm import BatchNorm1d                                                   
 from .graph_models import (AtomEncoder, BondEncoder, FASTKAGAT, FASTKAGCN, FASTKAGCNRegression, FASTKAGIN, GINEKANLayer,   # noqa: F401
                            KAGAT, KAGCN, KAGCNRegression, KAGIN, KAGINRegression, FASTKAGINRegression,
                            KAGCN_Layer, KAGAT_Layer, FASTKAGCN_Layer, FASTKAGAT_Layer)
+from . import baselines                                                          # noqa: F401
+from .baselines import (GAT, GCN, GIN, GATConv, GCNConv, GCNRegression, GINConv, GINEConv, GINRegression, GNN_Nodes,   # noqa: F401
+                        Linear, LinearReLU, make_mlp, make_mlp_nodes)
 from .data import DeviceBatch, DeviceBatchLoader, DeviceGraphDataset             # noqa: F401
 
 __version__ = "0.1.0"

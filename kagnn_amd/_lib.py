@@ -148,6 +148,11 @@ _SIGNATURES = {
     "kagnn_softmax_xent_workspace_bytes": (c_int32, [c_int64, POINTER(c_size_t)]),
     "kagnn_softmax_xent_fwd": (c_int32, [_P, c_int64, c_int64, c_int32, _P, _P, c_int32, _P, _P, _P, _P, c_size_t, _P]),
     "kagnn_softmax_xent_bwd": (c_int32, [_P, c_int64, c_int64, c_int32, _P, _P, c_int32, _P, _P, _P, _P, c_int64, _P]),
+    "kagnn_linear_bwd_weight_workspace_bytes": (c_int32, [c_int64, c_int32, c_int32, POINTER(c_size_t)]),
+    "kagnn_linear_fwd": (c_int32, [_P, c_int64, c_int64, c_int32, _P, _P, c_int32, c_int32, _P, c_int64, _P]),
+    "kagnn_linear_bwd_input": (c_int32, [_P, c_int64, _P, c_int64, c_int64, c_int32, _P, c_int32, _P, c_int64, _P]),
+    "kagnn_linear_bwd_weight": (c_int32, [_P, c_int64, _P, c_int64, _P, c_int64, c_int64, c_int32, c_int32, _P, _P, _P,
+                                          c_size_t, _P]),
     "kagnn_l1_loss_fwd": (c_int32, [_P, _P, c_int64, _P, _P]),
     "kagnn_l1_loss_bwd": (c_int32, [_P, _P, c_int64, _P, _P, _P]),
     "kagnn_degree_one_hot": (c_int32, [_P, c_int64, c_int32, _P, c_int64, _P]),

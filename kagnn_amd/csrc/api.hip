@@ -82,7 +82,7 @@ using namespace kagnn;
 #pragma GCC visibility push(default)
 extern "C" {
 
-int kagnn_version(void) { return 266; }
+int kagnn_version(void) { return 267; }
 const char* kagnn_last_error(void) { return g_err; }
 
 int kagnn_stage_timer_enable(const char* only) {
@@ -965,6 +965,52 @@ int kagnn_regression_epoch_update(void* train_meter, void* val_meter, void* test
                     ((uintptr_t)state & 3) == 0, "misaligned record");
     return regression_epoch_update(train_meter, val_meter, test_meter, n_train, n_val, n_test, state, history, max_epochs,
                                    as_stream(stream));
+}
+
+// ---------------------------------------------------------------- dense layer of the MLP baselines (linear.hip)
+// exact fp32 in every precision mode; the weight gradient is a fixed-order slab reduction (no atomics)
+
+int kagnn_linear_bwd_weight_workspace_bytes(int64_t N, int32_t in, int32_t out, size_t* bytes) {
+    KAGNN_CHECK_ARG(bytes != nullptr && N >= 0 && in >= 1 && out >= 1, "bad argument");
+    *bytes = linear_dw_ws_bytes(N, in, out);
+    return KAGNN_OK;
+}
+
+int kagnn_linear_fwd(const float* x, int64_t ldx, int64_t N, int32_t in, const float* W, const float* bias, int32_t out,
+                     int32_t relu, float* y, int64_t ldy, void* stream) {
+    KAGNN_STAGE(stream);
+    KAGNN_CHECK_ARG(in >= 1 && out >= 1, "in_features/out_features must be >= 1");
+    KAGNN_CHECK_ARG(N >= 0 && ldx >= in && ldy >= out, "bad shape");
+    KAGNN_CHECK_ARG(relu == 0 || relu == 1, "relu must be 0 or 1");
+    if (N == 0) return KAGNN_OK;
+    KAGNN_CHECK_ARG(x && W && y, "null array");
+    return linear_fwd(x, ldx, N, in, W, bias, out, relu, y, ldy, as_stream(stream));
+}
+
+int kagnn_linear_bwd_input(const float* gy, int64_t ldgy, const float* y, int64_t ldy, int64_t N, int32_t out, const float* W,
+                           int32_t in, float* gx, int64_t ldgx, void* stream) {
+    KAGNN_STAGE(stream);
+    KAGNN_CHECK_ARG(in >= 1 && out >= 1, "in_features/out_features must be >= 1");
+    KAGNN_CHECK_ARG(N >= 0 && ldgy >= out && ldgx >= in && (!y || ldy >= out), "bad shape");
+    if (N == 0) return KAGNN_OK;
+    KAGNN_CHECK_ARG(gy && W && gx, "null array");
+    return linear_dx(gy, ldgy, y, ldy, N, out, W, in, gx, ldgx, as_stream(stream));
+}
+
+int kagnn_linear_bwd_weight(const float* x, int64_t ldx, const float* gy, int64_t ldgy, const float* y, int64_t ldy, int64_t N,
+                            int32_t in, int32_t out, float* gW, float* gb, void* ws, size_t ws_bytes, void* stream) {
+    KAGNN_STAGE(stream);
+    KAGNN_CHECK_ARG(in >= 1 && out >= 1, "in_features/out_features must be >= 1");
+    KAGNN_CHECK_ARG(N >= 0 && ldx >= in && ldgy >= out && (!y || ldy >= out), "bad shape");
+    KAGNN_CHECK_ARG(gW != nullptr, "null array");
+    if (N == 0) {                                   // an empty sum: zeros, no kernel
+        KAGNN_HIP(hipMemsetAsync(gW, 0, (size_t)in * out * sizeof(float), as_stream(stream)));
+        if (gb) KAGNN_HIP(hipMemsetAsync(gb, 0, (size_t)out * sizeof(float), as_stream(stream)));
+        return KAGNN_OK;
+    }
+    KAGNN_CHECK_ARG(x && gy && ws, "null array");
+    KAGNN_CHECK_ARG(((uintptr_t)ws & 15) == 0, "the workspace must be 16-byte aligned");
+    return linear_dw(x, ldx, gy, ldgy, y, ldy, N, in, out, gW, gb, (float*)ws, ws_bytes, as_stream(stream));
 }
 
 // ---------------------------------------------------------------- direct peer-to-peer exchange (p2p.hip)

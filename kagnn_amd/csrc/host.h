@@ -214,6 +214,16 @@ int l1_loss_meter_fwd(const float* pred, long ldp, const float* target, long ldt
 int regression_epoch_update(void* train_meter, void* val_meter, void* test_meter, long n_train, long n_val, long n_test, void* state,
                             double* history, int max_epochs, hipStream_t st);
 
+// ---- linear.hip
+int linear_fwd(const float* x, long ldx, long N, int in, const float* W, const float* bias, int out, int relu, float* y, long ldy,
+               hipStream_t st);
+int linear_dx(const float* gy, long ldgy, const float* y, long ldy, long N, int out, const float* W, int in, float* gx, long ldgx,
+              hipStream_t st);
+void linear_dw_plan(long N, int in, int out, long* slabs, long* rows_per_slab);
+size_t linear_dw_ws_bytes(long N, int in, int out);
+int linear_dw(const float* x, long ldx, const float* gy, long ldgy, const float* y, long ldy, long N, int in, int out, float* gW,
+              float* gb, float* ws, size_t ws_bytes, hipStream_t st);
+
 // ---- p2p.hip
 int p2p_reduce_scatter(const float* const* parts, int P, int rank, long N, int out, long ld, float* y, long ldy, hipStream_t st);
 int p2p_all_gather(const float* const* shards, int P, long N, int w, long lds, float* g, long ldg, hipStream_t st);

@@ -763,3 +763,14 @@ def make_model(params: dict):
     if params["architecture"] == "fastkan":
         return GFASTKAN_Nodes(**common)
     raise ValueError("kagnn_amd.harness.make_model builds the 'kan' and 'fastkan' architectures")
+
+
+def make_any_model(params: dict):
+    """``utils.make_model`` of the reference (``node_classification_clean/utils.py:88-123``) for every architecture: ``'mlp'`` builds
+    this package's ``baselines.GNN_Nodes`` from the same ``params`` dictionary, everything else goes to ``make_model``."""
+    if params["architecture"] == "mlp":
+        from .baselines import GNN_Nodes
+        return GNN_Nodes(conv_type=params["conv_type"], mp_layers=params["mp_layers"], num_features=params["num_features"],
+                         hidden_channels=params["hidden_channels"], num_classes=params["num_classes"], skip=params["skip"],
+                         hidden_layers=params["hidden_layers"], dropout=params["dropout"], heads=params.get("heads", 4))
+    return make_model(params)

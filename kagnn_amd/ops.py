@@ -751,6 +751,74 @@ def segment_pool(x, seg_ptr, mean: bool = False) -> torch.Tensor:
     return _SegmentPoolFn.apply(x, seg_ptr, bool(mean))
 
 
+# ======================================================================== dense layer (MLP baselines)
+class _LinearFn(Function):
+    """y = x W^T (+ b) (then ReLU): torch.nn.Linear and the torch.nn.ReLU that follows it in the reference's make_mlp chains,
+    exact fp32 in every precision mode (csrc/linear.hip).  Saves x and, for the fused ReLU only, y (the mask of the backward
+    is y > 0: torch's threshold_backward on the result)."""
+
+    @staticmethod
+    @_on_operand_device
+    def forward(ctx, x, weight, bias, relu):
+        _need_cuda(x, weight, bias)
+        x = _rows(x)
+        w = _rows(weight).contiguous()
+        b = None if bias is None else bias.contiguous()
+        n, fin = x.shape
+        fout = w.size(0)
+        if w.size(1) != fin or (b is not None and (b.dim() != 1 or b.numel() != fout or b.dtype != torch.float32)):
+            raise ValueError(f"linear: x {tuple(x.shape)}, weight {tuple(w.shape)}, bias {None if b is None else tuple(b.shape)} do not fit")
+        y = torch.empty((n, fout), dtype=torch.float32, device=x.device)
+        if n > 0:
+            _call("kagnn_linear_fwd", _ptr(x), _ld(x), n, fin, _ptr(w), _ptr(b), fout, int(relu), _ptr(y), fout, _stream())
+        ctx.save_for_backward(x, w, y if relu else None)
+        ctx.has_bias = b is not None
+        return y
+
+    @staticmethod
+    @once_differentiable
+    @_on_operand_device
+    def backward(ctx, gy):
+        x, w, y = ctx.saved_tensors
+        gy = _rows(gy)
+        n, fin = x.shape
+        fout = w.size(0)
+        dev = x.device
+        gx = gw = gb = None
+        ldy = 0 if y is None else _ld(y)
+        if ctx.needs_input_grad[0]:
+            gx = torch.empty((n, fin), dtype=torch.float32, device=dev)
+            if n > 0:
+                _call("kagnn_linear_bwd_input", _ptr(gy), _ld(gy), _ptr(y), ldy, n, fout, _ptr(w), fin, _ptr(gx), fin, _stream())
+        want_b = ctx.has_bias and ctx.needs_input_grad[2]
+        if ctx.needs_input_grad[1] or want_b:
+            if n == 0:
+                gw = torch.zeros((fout, fin), dtype=torch.float32, device=dev)
+                gb = torch.zeros((fout,), dtype=torch.float32, device=dev) if want_b else None
+            else:
+                gw = torch.empty((fout, fin), dtype=torch.float32, device=dev)
+                gb = torch.empty((fout,), dtype=torch.float32, device=dev) if want_b else None
+                ws = _ws(_sizes("kagnn_linear_bwd_weight_workspace_bytes", n, fin, fout), dev)
+                _call("kagnn_linear_bwd_weight", _ptr(x), _ld(x), _ptr(gy), _ld(gy), _ptr(y), ldy, n, fin, fout, _ptr(gw), _ptr(gb),
+                      _ptr(ws), ws.numel(), _stream())
+            if not ctx.needs_input_grad[1]:
+                gw = None
+        return gx, gw, gb, None
+
+
+def linear(x, weight, bias=None, relu: bool = False) -> torch.Tensor:
+    """``F.linear(x, weight, bias)``, followed by ``F.relu`` when ``relu``, as one library call each way.  x [..., in], weight
+    [out, in], bias [out] or None."""
+    if torch.compiler.is_compiling():
+        y = torch.nn.functional.linear(x, weight, bias)
+        return torch.nn.functional.relu(y) if relu else y
+    if x.dim() == 2:
+        return _LinearFn.apply(x, weight, bias, bool(relu))
+    _need_cuda(x, weight, bias)
+    y = _LinearFn.apply(x.reshape(-1, x.size(-1)), weight, bias, bool(relu))
+    return y.view(*x.shape[:-1], weight.size(0))
+
+
 # ======================================================================== efficient-KAN layer
 def kan_pack_chain(layers, grid_size: int, spline_order: int, mode: int):
     """Pack the weights of all layers of a KAN chain in ONE launch (``kagnn_kan_pack_batch``): ``layers`` is a list of

@@ -14,9 +14,12 @@ Which ``models`` surface is installed follows the script's directory (``--flavou
   node                  ``node_classification_clean/models.py``: GKAN_Nodes, GFASTKAN_Nodes, the conv layers
   graph_classification  ``graph_classification/models.py``: KAGIN, FASTKAGIN, KAGCN, KAGAT, FASTKAGCN, FASTKAGAT
   graph_regression      ``graph_regression/models.py``: the same class NAMES with GINE messages + encoders (``KAGINRegression`` ...)
-The MLP baselines of those files (``GNN_Nodes``, ``GIN``, ``GCN``, ``GAT``: stock torch_geometric models, outside the hot path) pass
-through to the reference's OWN classes when the directory's ``models.py`` imports (i.e. torch_geometric is installed); otherwise
-the name resolves to a class whose constructor says so.
+The MLP baselines of those files (``GNN_Nodes``, ``GIN``, ``GCN``, ``GAT``) follow ``--baselines``:
+  reference (default)   the reference's OWN stock torch_geometric classes when the directory's ``models.py`` imports (i.e.
+                        torch_geometric is installed); otherwise the name resolves to a class whose constructor says so
+  package               this package's ``kagnn_amd.baselines`` classes (``GNN_Nodes``; ``GIN`` / ``GCN`` / ``GAT``; for the regression
+                        flavour ``GINRegression`` / ``GCNRegression`` under the names ``GIN`` / ``GCN``): the MLP rows of the reference's
+                        tables through the same kernels, CSR and loops as the KAN rows
 """
 from __future__ import annotations
 
@@ -54,9 +57,11 @@ def _missing(name: str, why: str):
     return _Unavailable
 
 
-def install(flavour: str, script_dir: str | None = None) -> types.ModuleType:
+def install(flavour: str, script_dir: str | None = None, baselines: str = "reference") -> types.ModuleType:
     """Install the ``ekan`` / ``fastkan`` / ``models`` aliases; returns the ``models`` module object."""
     import kagnn_amd
+    if baselines not in ("reference", "package"):
+        raise ValueError("baselines must be 'reference' or 'package'")
     from kagnn_amd import ekan, fastkan, graph_models, models as node_models
     if flavour not in _BASELINES:
         raise ValueError("flavour must be 'node', 'graph_classification' or 'graph_regression'")
@@ -92,6 +97,11 @@ def install(flavour: str, script_dir: str | None = None) -> types.ModuleType:
             ref_models, why = None, f"{type(ex).__name__}: {ex}"
     for n in _BASELINES[flavour]:
         setattr(mod, n, getattr(ref_models, n) if ref_models is not None and hasattr(ref_models, n) else _missing(n, why))
+    if baselines == "package":
+        from kagnn_amd import baselines as own
+        for n in _BASELINES[flavour]:
+            setattr(mod, n, getattr(own, n + "Regression" if flavour == "graph_regression" else n))
+        mod.make_mlp = own.make_mlp_nodes if flavour == "node" else own.make_mlp
     mod.__kagnn_amd__ = kagnn_amd.__version__
     sys.modules["models"] = mod
     return mod
@@ -99,20 +109,24 @@ def install(flavour: str, script_dir: str | None = None) -> types.ModuleType:
 
 def main(argv=None) -> None:
     argv = list(sys.argv[1:] if argv is None else argv)
-    flavour = None
+    flavour, baselines = None, "reference"
     while argv and argv[0].startswith("--"):
         if argv[0] == "--flavour" and len(argv) > 1:
             flavour, argv = argv[1], argv[2:]
         elif argv[0].startswith("--flavour="):
             flavour, argv = argv[0].split("=", 1)[1], argv[1:]
+        elif argv[0] == "--baselines" and len(argv) > 1:
+            baselines, argv = argv[1], argv[2:]
+        elif argv[0].startswith("--baselines="):
+            baselines, argv = argv[0].split("=", 1)[1], argv[1:]
         else:
             break
     if not argv:
-        raise SystemExit("usage: python -m kagnn_amd.run_reference [--flavour node|graph_classification|graph_regression] "
+        raise SystemExit("usage: python -m kagnn_amd.run_reference [--flavour node|graph_classification|graph_regression] [--baselines reference|package] "
                          "<reference script.py> [script args]")
     script = os.path.abspath(argv[0])
     script_dir = os.path.dirname(script)
-    install(flavour or _flavour_of(script), script_dir)
+    install(flavour or _flavour_of(script), script_dir, baselines)
     sys.argv = [script] + argv[1:]
     sys.path.insert(0, script_dir)                        # what `python script.py` does
     runpy.run_path(script, run_name="__main__")

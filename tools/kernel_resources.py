@@ -43,6 +43,7 @@ HOT = [
     (r"agg16_", 0, 0),
     (r"bn_", 0, 0),
     (r"batch_assemble_kernel", 0, 0),                  # the loader's one launch per mini-batch
+    (r"linear_gemm_kernel<|linear_dw_reduce_kernel", 0, 0),   # the dense layer of the MLP baselines
 ]
 
 
