@@ -45,11 +45,17 @@ extern "C" {
                                  * Cubic layers of <= 8 coefficients; any other shape runs the three-product kernels (more accurate).
                                  * Takes the same packs as KAGNN_PREC_SPLIT.  Never the headline.                              */
 
+/* highest spline_order of the per-operation KANLinear calls (kagnn_kan_pack_bytes, kagnn_kan_pack, kagnn_kan_fwd_workspace_bytes,
+ * kagnn_kan_linear_fwd, kagnn_kan_linear_bwd_input, kagnn_kan_bwd_weight_workspace_bytes, kagnn_kan_linear_bwd_weight,
+ * kagnn_kan_bsplines).  Orders 5..16 run with KAGNN_PREC_FP32 / KAGNN_PREC_FP32_GRID only (KAGNN_PREC_SPLIT / _HALF return
+ * KAGNN_ERR_UNSUPPORTED) and need grid_size + 2 * spline_order + 1 <= 64; every other entry point takes orders 1..4. */
+#define KAGNN_MAX_SPLINE_ORDER 16
+
 /* element type of an activation / gradient matrix where an entry point accepts more than fp32 */
 #define KAGNN_DTYPE_F32 0
 #define KAGNN_DTYPE_BF16 1
 
-int kagnn_version(void);          /* 267 = 266 + kagnn_linear_fwd, kagnn_linear_bwd_input, kagnn_linear_bwd_weight (+ _workspace_bytes); 266 = 265 + kagnn_l1_loss_meter_fwd, kagnn_regression_epoch_update; 265 = 264 + kagnn_node_eval, kagnn_early_stop_update, kagnn_copy_if; 264 = 263 + kagnn_degree_one_hot, kagnn_nll_loss_fwd / _bwd; 263 = 262 + kagnn_batch_assemble; 262 = 261 - the fields edge_src, edge_dst, csr_flags of kagnn_kagin_model_t; 261 = 260 + kagnn_fastkan_fwd_stats_in_kernel; 260 = round 6: + the feature-sharded FastKAN entry points kagnn_fastkan_row_moments .. _shard_bwd_finish, + kagnn_kagin_model_*; 250 = 240 + KAGNN_PREC_HALF; 240 = 230 + kagnn_gin_kan_layer_bwd_bn_sums; 230 = 220 + the *_affine entry points of a folded BatchNorm1d; 220 = 210 + the stage timer) */
+int kagnn_version(void);          /* 268 = 267 + spline orders 5..KAGNN_MAX_SPLINE_ORDER in the per-operation KANLinear calls (no new entry point); 267 = 266 + kagnn_linear_fwd, kagnn_linear_bwd_input, kagnn_linear_bwd_weight (+ _workspace_bytes); 266 = 265 + kagnn_l1_loss_meter_fwd, kagnn_regression_epoch_update; 265 = 264 + kagnn_node_eval, kagnn_early_stop_update, kagnn_copy_if; 264 = 263 + kagnn_degree_one_hot, kagnn_nll_loss_fwd / _bwd; 263 = 262 + kagnn_batch_assemble; 262 = 261 - the fields edge_src, edge_dst, csr_flags of kagnn_kagin_model_t; 261 = 260 + kagnn_fastkan_fwd_stats_in_kernel; 260 = round 6: + the feature-sharded FastKAN entry points kagnn_fastkan_row_moments .. _shard_bwd_finish, + kagnn_kagin_model_*; 250 = 240 + KAGNN_PREC_HALF; 240 = 230 + kagnn_gin_kan_layer_bwd_bn_sums; 230 = 220 + the *_affine entry points of a folded BatchNorm1d; 220 = 210 + the stage timer) */
 const char* kagnn_last_error(void);
 
 /* Stage timer -- a measurement aid, off by default (no reference counterpart: the reference times whole epochs with
@@ -197,6 +203,9 @@ int kagnn_segment_broadcast(const float* gout, int64_t ldg, float* gx, int64_t l
  * kagnn_kan_pack rearranges (base_weight | spline_weight*scaler) into the MFMA fragment order
  * used by fwd (`pack_fwd`) and by the input-gradient kernel (`pack_dx`); call it whenever the
  * parameters change.  Sizes from kagnn_kan_pack_bytes.
+ *
+ * spline_order 1..4 in every mode; 5..KAGNN_MAX_SPLINE_ORDER with KAGNN_PREC_FP32 / KAGNN_PREC_FP32_GRID (the pack, the
+ * forward, both gradients and their workspace queries below; the same fp32 packs and the same ordered fp32 fma chain).
  * ------------------------------------------------------------------------------------------ */
 int kagnn_kan_pack_bytes(int32_t in_features, int32_t out_features, int32_t grid_size,
                          int32_t spline_order, int32_t mode, size_t* fwd_bytes_host,
@@ -259,7 +268,7 @@ int kagnn_kan_linear_fwd_moments(const float* x, int64_t ldx, int64_t num_rows, 
                                  void* workspace, size_t workspace_bytes, void* stream);
 
 /* gx[N,in] = d loss / d x given gy[N,out] (x is the saved layer input; bases' derivatives are
- * recomputed, nothing but x was saved).  gx_dtype = KAGNN_DTYPE_F32, or KAGNN_DTYPE_BF16 (split-precision
+ * recomputed, nothing but x was saved).  spline_order as kagnn_kan_linear_fwd (5..16: exact-fp32 modes, fp32 rows).  gx_dtype = KAGNN_DTYPE_F32, or KAGNN_DTYPE_BF16 (split-precision
  * B-spline layers with <= 128 outputs: the rows the transposed aggregation gathers next, rounded once) with
  * ldgx in bf16 elements.                                                                    */
 int kagnn_kan_linear_bwd_input(const float* x, int64_t ldx, const float* gy, int64_t ldgy,
@@ -270,7 +279,8 @@ int kagnn_kan_linear_bwd_input(const float* x, int64_t ldx, const float* gy, int
 
 /* parameter gradients: g_base_weight[out,in] (NULL when not wanted), g_spline_weight[out,in,G+k],
  * g_spline_scaler[out,in] (NULL when the layer has no scaler).  `workspace` holds the per-wave
- * partial sums (size from kagnn_kan_bwd_weight_workspace_bytes); deterministic reduction.   */
+ * partial sums (size from kagnn_kan_bwd_weight_workspace_bytes); deterministic reduction.
+ * spline_order as kagnn_kan_linear_fwd (5..16: exact-fp32 modes).                           */
 int kagnn_kan_bwd_weight_workspace_bytes(int64_t num_rows, int32_t in_features,
                                          int32_t out_features, int32_t grid_size,
                                          int32_t spline_order, int32_t mode, size_t* bytes_host);
@@ -490,7 +500,8 @@ int kagnn_kan_linear_bwd_input_affine_sums(const float* x, int64_t ldx, const fl
  * Adaptive grids.  Replaces the device work of KANLinear.update_grid (ekan.py:164-211) and the dense
  * b_splines (:79-112).  `grid*` are whole grid buffers [in, G+2k+1] with increasing rows.
  * ------------------------------------------------------------------------------------------ */
-/* bases[N, in, G+k] = b_splines(x) on per-feature knot rows (ekan.py:79-112).                  */
+/* bases[N, in, G+k] = b_splines(x) on per-feature knot rows (ekan.py:79-112).  spline_order 1..KAGNN_MAX_SPLINE_ORDER
+ * (above 4: grid_size + 2 * spline_order + 1 <= 64); a non-finite x gives NaN in every basis at orders above 4.  */
 int kagnn_kan_bsplines(const float* x, int64_t ldx, int64_t num_rows, const float* grid,
                        int32_t in_features, int32_t grid_size, int32_t spline_order, float* bases,
                        void* stream);

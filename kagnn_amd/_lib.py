@@ -19,6 +19,9 @@ PREC_SPLIT = 1
 PREC_FP32_GRID = 2      # exact fp32 on per-feature, non-uniform knot rows (after update_grid)
 PREC_HALF = 3           # build-defined reduced precision: the split kernels with ONE fp16 product per fp32 product (kagnn_hip.h)
 DTYPE_F32, DTYPE_BF16 = 0, 1
+MAX_SPLINE_ORDER = 16   # KAGNN_MAX_SPLINE_ORDER: the per-operation KANLinear calls; above FUSED_MAX_SPLINE_ORDER exact fp32 only
+FUSED_MAX_SPLINE_ORDER = 4   # every other entry point (fused layer / stack / model calls, parts, moments, refit, sharded)
+HIGH_ORDER_MAX_KNOTS = 64    # grid_size + 2 * spline_order + 1 at orders above FUSED_MAX_SPLINE_ORDER
 
 _P = c_void_p
 _SIGNATURES = {

@@ -61,7 +61,7 @@ int kan_linear_bwd_weight(const float* x, int64_t ldx, const float* x_affine, co
     static const char fn[] = "kagnn_kan_linear_bwd_weight_affine";
     ModeScope mode_scope_(mode);
     KAGNN_STAGE_AS("kagnn_kan_linear_bwd_weight", stream);
-    int rc = check_kan_dims(fn, in, out, G, K, mode);
+    int rc = check_kan_dims_wide(fn, in, out, G, K, mode);
     if (rc) return rc;
     KAGNN_CHECK_ARG_AS(fn, N >= 0 && ldx >= in && ldgy >= out, "bad shape");
     KAGNN_CHECK_ARG_AS(fn, knots && sw && g_sw && ws, "null array");          // g_base_weight NULL: not wanted
@@ -72,6 +72,8 @@ int kan_linear_bwd_weight(const float* x, int64_t ldx, const float* x_affine, co
         return kan_split_dw(x, ldx, gy, ldgy, N, knots, in, out, G, K, sw, sc, g_bw, g_sw, g_sc, (float*)ws, ws_bytes, as_stream(stream), x_affine, defer);
     }
     if (x_affine) return fail(KAGNN_ERR_UNSUPPORTED, "%s: an input affine is applied by the split-precision kernels only", fn);
+    if (high_order(K))
+        return kan_ho_dw(x, ldx, gy, ldgy, N, knots, in, out, G, K, sw, sc, g_bw, g_sw, g_sc, (float*)ws, ws_bytes, mode == KAGNN_PREC_FP32_GRID, as_stream(stream));
     return kan_f32_dw(x, ldx, gy, ldgy, N, knots, in, out, G, K, sw, sc, g_bw, g_sw, g_sc, (float*)ws, ws_bytes, mode == KAGNN_PREC_FP32_GRID, as_stream(stream));
 }
 }  // namespace kagnn
@@ -82,7 +84,7 @@ using namespace kagnn;
 #pragma GCC visibility push(default)
 extern "C" {
 
-int kagnn_version(void) { return 267; }
+int kagnn_version(void) { return 268; }
 const char* kagnn_last_error(void) { return g_err; }
 
 int kagnn_stage_timer_enable(const char* only) {
@@ -296,7 +298,7 @@ int kagnn_embedding_bwd(const int64_t* index, int64_t index_stride, int64_t N, c
 int kagnn_kan_pack_bytes(int32_t in, int32_t out, int32_t G, int32_t K, int32_t mode,
                          size_t* fwd_bytes, size_t* dx_bytes) {
     ModeScope mode_scope_(mode);
-    int rc = check_kan_dims(__func__, in, out, G, K, mode);
+    int rc = check_kan_dims_wide(__func__, in, out, G, K, mode);
     if (rc) return rc;
     KAGNN_CHECK_ARG(fwd_bytes && dx_bytes, "null output");
     *fwd_bytes = use_sparse_fwd(in, out, G, K, mode) ? kan_sparse_pack_fwd_bytes(in, out, G + K)
@@ -309,7 +311,7 @@ int kagnn_kan_pack(const float* bw, const float* sw, const float* sc, int32_t in
                    int32_t G, int32_t K, int32_t mode, void* pack_fwd, void* pack_dx, void* stream) {
     ModeScope mode_scope_(mode);
     KAGNN_STAGE(stream);
-    int rc = check_kan_dims(__func__, in, out, G, K, mode);
+    int rc = check_kan_dims_wide(__func__, in, out, G, K, mode);
     if (rc) return rc;
     KAGNN_CHECK_ARG(sw && pack_fwd && pack_dx, "null array");          // base_weight NULL = no SiLU branch
     const bool sf = use_split_fwd(in, out, G, K, mode), sd = use_split_dx(in, out, G, K, mode);
@@ -346,7 +348,7 @@ int kagnn_kan_pack_batch(int32_t n_layers, const float* const* bw, const float* 
 int kagnn_kan_fwd_workspace_bytes(int64_t N, int32_t in, int32_t out, int32_t G, int32_t K, int32_t mode,
                                   size_t* bytes) {
     ModeScope mode_scope_(mode);
-    int rc = check_kan_dims(__func__, in, out, G, K, mode);
+    int rc = check_kan_dims_wide(__func__, in, out, G, K, mode);
     if (rc) return rc;
     KAGNN_CHECK_ARG(bytes && N >= 0, "bad argument");
     *bytes = use_sparse_fwd(in, out, G, K, mode) ? kan_sparse_fwd_ws_bytes(N, in, out, G + K)
@@ -359,7 +361,7 @@ int kagnn_kan_linear_fwd(const float* x, int64_t ldx, int64_t N, const float* kn
                          float* y, int64_t ldy, void* ws, size_t ws_bytes, void* stream) {
     ModeScope mode_scope_(mode);
     KAGNN_STAGE(stream);
-    int rc = check_kan_dims(__func__, in, out, G, K, mode);
+    int rc = check_kan_dims_wide(__func__, in, out, G, K, mode);
     if (rc) return rc;
     KAGNN_CHECK_ARG(N >= 0 && ldx >= in && ldy >= out, "bad shape");
     if (N == 0) return KAGNN_OK;
@@ -370,6 +372,8 @@ int kagnn_kan_linear_fwd(const float* x, int64_t ldx, int64_t N, const float* kn
             return kan_sparse_fwd(x, ldx, N, knots, in, out, G, K, pack_fwd, y, ldy, ws, ws_bytes, nullptr, nullptr, as_stream(stream));
         return kan_split_fwd(x, ldx, N, knots, in, out, G, K, pack_fwd, y, ldy, ws, ws_bytes, as_stream(stream));
     }
+    if (high_order(K))
+        return kan_ho_fwd(x, ldx, N, knots, in, out, G, K, (const float*)pack_fwd, y, ldy, mode == KAGNN_PREC_FP32_GRID, as_stream(stream));
     return kan_f32_fwd(x, ldx, N, knots, in, out, G, K, (const float*)pack_fwd, y, ldy, mode == KAGNN_PREC_FP32_GRID, as_stream(stream));
 }
 
@@ -421,7 +425,9 @@ int kagnn_kan_fwd_moments_workspace_bytes(int64_t N, int32_t in, int32_t out, in
                                           size_t* bytes) {
     ModeScope mode_scope_(mode);
     size_t b = 0;
-    int rc = kagnn_kan_fwd_workspace_bytes(N, in, out, G, K, mode, &b);
+    int rc = check_kan_dims(__func__, in, out, G, K, mode);
+    if (rc) return rc;
+    rc = kagnn_kan_fwd_workspace_bytes(N, in, out, G, K, mode, &b);
     if (rc) return rc;
     const size_t m = fused_moments(N, in, out, G, K, mode) ? kan_sparse_fwd_moments_ws_bytes(N, out) : bn_ws_bytes(N, out);
     *bytes = b > m ? b : m;
@@ -466,7 +472,7 @@ int kagnn_kan_linear_bwd_input_affine(const float* x, int64_t ldx, const float* 
                                       int32_t mode, const void* pack_dx, void* gx, int64_t ldgx, int32_t gx_dtype, void* stream) {
     ModeScope mode_scope_(mode);
     KAGNN_STAGE_AS("kagnn_kan_linear_bwd_input", stream);
-    int rc = check_kan_dims(__func__, in, out, G, K, mode);
+    int rc = check_kan_dims_wide(__func__, in, out, G, K, mode);
     if (rc) return rc;
     KAGNN_CHECK_ARG(N >= 0 && ldx >= in && ldgy >= out && ldgx >= in, "bad shape");
     KAGNN_CHECK_ARG(gx_dtype == KAGNN_DTYPE_F32 || gx_dtype == KAGNN_DTYPE_BF16, "gx_dtype must be KAGNN_DTYPE_F32 or KAGNN_DTYPE_BF16");
@@ -480,6 +486,8 @@ int kagnn_kan_linear_bwd_input_affine(const float* x, int64_t ldx, const float* 
     if (x_affine) return fail(KAGNN_ERR_UNSUPPORTED, "%s: an input affine is applied by the split-precision kernels only", __func__);
     if (gx_dtype != KAGNN_DTYPE_F32) return fail(KAGNN_ERR_UNSUPPORTED, "%s: bf16 gradient rows are produced by the split-precision kernels only", __func__);
     float* gxf = static_cast<float*>(gx);
+    if (high_order(K))
+        return kan_ho_dx(x, ldx, gy, ldgy, N, knots, in, out, G, K, (const float*)pack_dx, gxf, ldgx, mode == KAGNN_PREC_FP32_GRID, as_stream(stream));
     return kan_f32_dx(x, ldx, gy, ldgy, N, knots, in, out, G, K, (const float*)pack_dx, gxf, ldgx, mode == KAGNN_PREC_FP32_GRID, as_stream(stream));
 }
 
@@ -523,7 +531,7 @@ int kagnn_kan_linear_bwd_input_affine_sums(const float* x, int64_t ldx, const fl
 int kagnn_kan_bwd_weight_workspace_bytes(int64_t N, int32_t in, int32_t out, int32_t G, int32_t K,
                                          int32_t mode, size_t* bytes) {
     ModeScope mode_scope_(mode);
-    int rc = check_kan_dims(__func__, in, out, G, K, mode);
+    int rc = check_kan_dims_wide(__func__, in, out, G, K, mode);
     if (rc) return rc;
     KAGNN_CHECK_ARG(bytes && N >= 0, "bad argument");
     *bytes = use_split_dw(in, out, G, K, mode) ? kan_split_dw_ws_bytes(N, in, out, G + K, K)
@@ -557,10 +565,11 @@ static int check_fk(const char* fn, int in, int out, int ng, int mode) {
 // ---------------------------------------------------------------- adaptive grids (update_grid)
 int kagnn_kan_bsplines(const float* x, int64_t ldx, int64_t N, const float* grid, int32_t in, int32_t G,
                        int32_t K, float* bases, void* stream) {
-    int rc = check_kan_dims(__func__, in, 1, G, K, KAGNN_PREC_FP32_GRID);
+    int rc = check_kan_dims_wide(__func__, in, 1, G, K, KAGNN_PREC_FP32_GRID);
     if (rc) return rc;
     KAGNN_CHECK_ARG(N >= 0 && ldx >= in, "bad shape");
     KAGNN_CHECK_ARG(N == 0 || (x && grid && bases), "null array");
+    if (high_order(K)) return kan_ho_bsplines(x, ldx, N, grid, in, G, K, bases, as_stream(stream));
     return kan_bsplines(x, ldx, N, grid, in, G, K, bases, as_stream(stream));
 }
 

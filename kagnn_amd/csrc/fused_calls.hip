@@ -752,6 +752,9 @@ int km_check(const kagnn_kagin_model_t* m, const char* fn) {
                     m->num_convs * m->num_layers <= KAGNN_MODEL_MAX_LAYERS && m->num_readout >= 1 && m->num_readout <= KAGNN_MODEL_MAX_READOUT &&
                     m->readout_widths[0] == m->hidden;
     if (!ok) return fail(KAGNN_ERR_ARG, "%s: sizes outside the limits of kagnn_kagin_model_t (include/kagnn_hip.h)", fn);
+    // the per-operation calls the layout is sized with take orders up to KAGNN_MAX_SPLINE_ORDER; the model calls do not
+    if (m->spline_order < 1 || m->spline_order > kMaxOrder || m->readout_spline_order < 1 || m->readout_spline_order > kMaxOrder)
+        return fail(KAGNN_ERR_UNSUPPORTED, "%s: spline_order and readout_spline_order must be 1..4", fn);
     return KAGNN_OK;
 }
 

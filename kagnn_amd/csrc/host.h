@@ -111,6 +111,16 @@ int kan_dw_unpack(const float* gcat, int in, int out, int C, long inP, long outP
 int kan_dw_reduce(const float* slab, long NS, long per_slab, float* gcat, hipStream_t st);
 void dw_plan(long N, int in, int out, int* NBx, long* rpw);
 
+// ---- kan_high_order.hip (spline orders 5..KAGNN_MAX_SPLINE_ORDER, exact fp32; the packs, slab reduction and unpack are kan_fp32.hip's)
+int kan_ho_fwd(const float* x, long ldx, long N, const float* knots, int in, int out, int G, int K, const float* pack, float* y,
+               long ldy, bool pf, hipStream_t st);
+int kan_ho_dx(const float* x, long ldx, const float* gy, long ldgy, long N, const float* knots, int in, int out, int G, int K,
+              const float* pack, float* gx, long ldgx, bool pf, hipStream_t st);
+int kan_ho_dw(const float* x, long ldx, const float* gy, long ldgy, long N, const float* knots, int in, int out, int G, int K,
+              const float* sw, const float* sc, float* g_bw, float* g_sw, float* g_sc, float* ws, size_t ws_bytes, bool pf,
+              hipStream_t st);
+int kan_ho_bsplines(const float* x, long ldx, long N, const float* grid, int in, int G, int K, float* bases, hipStream_t st);
+
 // ---- kan_split.hip
 size_t kan_split_pack_fwd_bytes(int in, int out, int C);
 int kan_split_pack_fwd_noscale(const float* bw, const float* sw, const float* sc, int in, int out, int C, void* pack_fwd,
@@ -267,6 +277,20 @@ inline int check_kan_dims(const char* fn, int in, int out, int G, int K, int mod
     if (K < 1 || K > kMaxOrder) return fail(KAGNN_ERR_UNSUPPORTED, "%s: spline_order must be 1..4", fn);
     if (G < 1 || G + 2 * K + 1 > kMaxKnots) return fail(KAGNN_ERR_UNSUPPORTED, "%s: grid_size out of range", fn);
     if (mode != KAGNN_PREC_FP32 && mode != KAGNN_PREC_SPLIT && mode != KAGNN_PREC_FP32_GRID) return fail(KAGNN_ERR_ARG, "%s: unknown precision mode", fn);
+    return KAGNN_OK;
+}
+// The per-operation KANLinear calls (pack, forward, both gradients, their workspace queries, the dense bases) also take orders
+// kMaxOrder+1 .. KAGNN_MAX_SPLINE_ORDER, in the exact-fp32 modes only and with their own knot bound (kan_high_order.hip).  Every
+// other entry point keeps check_kan_dims and so refuses those orders before it launches anything.
+constexpr int kHighOrderMaxKnots = 64;
+inline bool high_order(int K) { return K > kMaxOrder; }
+inline int check_kan_dims_wide(const char* fn, int in, int out, int G, int K, int mode) {
+    if (K <= kMaxOrder) return check_kan_dims(fn, in, out, G, K, mode);
+    if (in < 1 || out < 1) return fail(KAGNN_ERR_ARG, "%s: in_features/out_features must be >= 1", fn);
+    if (K > KAGNN_MAX_SPLINE_ORDER) return fail(KAGNN_ERR_UNSUPPORTED, "%s: spline_order must be 1..16", fn);
+    if (mode == KAGNN_PREC_SPLIT) return fail(KAGNN_ERR_UNSUPPORTED, "%s: spline_order above 4 runs with KAGNN_PREC_FP32 or KAGNN_PREC_FP32_GRID only", fn);
+    if (mode != KAGNN_PREC_FP32 && mode != KAGNN_PREC_FP32_GRID) return fail(KAGNN_ERR_ARG, "%s: unknown precision mode", fn);
+    if (G < 1 || G + 2 * K + 1 > kHighOrderMaxKnots) return fail(KAGNN_ERR_UNSUPPORTED, "%s: grid_size + 2 * spline_order + 1 must be <= 64 at spline_order above 4", fn);
     return KAGNN_OK;
 }
 // the split path covers the hot shapes; everything else runs the exact-fp32 kernels (still HIP)

@@ -120,6 +120,7 @@ struct FwdLayout { size_t part, blocks, ws, total, ws_bytes; };
 struct BwdLayout { size_t gath, gfull, ws, total, ws_bytes; };
 
 int layouts(long n, int in_local, int out, int G, int K, int mode, int row_chunks, FwdLayout* f, BwdLayout* b) {
+    if (K > 4) return fail(KAGNN_ERR_UNSUPPORTED, "%s: spline_order must be 1..4", "kagnn_rccl_sharded_kan_*");
     const size_t mat = align256((size_t)(n > 0 ? n : 0) * out * sizeof(float));
     size_t fws = 0, dws = 0;
     // the forward kernel's own scratch (non-zero only for few rows x many features): every chunk size that will occur

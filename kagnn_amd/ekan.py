@@ -50,8 +50,11 @@ class KANLinear(nn.Module):
         if base_activation is not torch.nn.SiLU:
             raise NotImplementedError("the fused kernel implements the SiLU base branch only "
                                       "(the only activation KAGNN uses)")
-        if not 1 <= spline_order <= 4:
-            raise NotImplementedError("spline_order must be in 1..4 (KAGNN's search space)")
+        if not 1 <= spline_order <= ops.MAX_SPLINE_ORDER:
+            raise NotImplementedError(f"spline_order must be in 1..{ops.MAX_SPLINE_ORDER}")
+        if ops.high_order(spline_order) and grid_size + 2 * spline_order + 1 > ops.HIGH_ORDER_MAX_KNOTS:
+            raise NotImplementedError(f"grid_size + 2 * spline_order + 1 must be <= {ops.HIGH_ORDER_MAX_KNOTS} at spline_order above 4 "
+                                      f"(got {grid_size + 2 * spline_order + 1})")
         self.in_features = in_features
         self.out_features = out_features
         self.grid_size = grid_size
@@ -136,13 +139,13 @@ class KANLinear(nn.Module):
     def read_out_blocks_in_one_launch(self, widths) -> bool:
         """would ``forward_parts`` over fp32 blocks of these widths run as one forward launch (``kagnn_kan_fwd_parts_ok``)?"""
         mode = self.precision if self.precision is not None else ops.default_precision()
-        return (self._knots().dim() == 1 and ops.split_like(mode) and sum(widths) == self.in_features
+        return (not ops.high_order(self.spline_order) and self._knots().dim() == 1 and ops.split_like(mode) and sum(widths) == self.in_features
                 and ops.parts_one_launch_widths_ok(tuple(int(w) for w in widths), self.out_features, self.grid_size, self.spline_order, mode))
 
     def forward_parts(self, parts, skip_gradients=None) -> torch.Tensor:
         """``forward(torch.cat(parts, dim=1))`` without the concatenation (``ops.kan_linear_parts``)."""
         knots = self._knots()
-        if knots.dim() != 1:                             # adaptive grid: per-feature knot rows, keep it simple
+        if knots.dim() != 1 or ops.high_order(self.spline_order):    # adaptive grid (per-feature knot rows) / orders above 4: keep it simple
             return self.forward(ops.concat_columns([t.materialise() if isinstance(t, ops.AffineRows) else t for t in parts]))
         scaler = self.spline_scaler if self.enable_standalone_scale_spline else None
         return ops.kan_linear_parts(parts, self.base_weight, self.spline_weight, scaler, knots, self.grid_size,
@@ -161,6 +164,13 @@ class KANLinear(nn.Module):
         handful of [G+1, in] torch ops in the reference's order; the refit is
         ``kagnn_kan_grid_refit`` -- no [N, in, out] intermediate.  The layer then runs on per-feature knots."""
         assert x.dim() == 2 and x.size(1) == self.in_features
+        if ops.high_order(self.spline_order):
+            # a decision, not an omission: the reference's own refit (fp64 least squares) breaks down from order 12 -- fitted
+            # coefficients of 1e7..1e10, a function residual above the function at (G, k) = (16, 16) and (2, 16), and its fp64 solve
+            # and the normal equations disagreeing by 100 % -- so there is nothing to hold a device refit to (DESIGN.md section 7)
+            raise NotImplementedError("update_grid is not implemented at spline_order above 4: the least-squares refit of the "
+                                      "coefficients is ill-conditioned at these orders (the reference's own fp64 refit loses the "
+                                      "function from order 12). A layer whose grid buffer already holds per-feature knot rows runs.")
         n, g, k, dev = x.size(0), self.grid_size, self.spline_order, x.device
         ranked = torch.sort(x, dim=0).values
         quantiles = ranked[torch.linspace(0, n - 1, g + 1, dtype=torch.int64, device=dev)]       # [G+1, in]
@@ -242,7 +252,7 @@ class KAN(nn.Module):
         """all layers' weight packs in one launch when the chain runs on the sparse-forward / split kernels"""
         first = self.layers[0]
         mode = first.precision if first.precision is not None else ops.default_precision()
-        if not ops.split_like(mode) or any(l.precision != first.precision or l._knots().dim() != 1 for l in self.layers):
+        if ops.high_order(self.spline_order) or not ops.split_like(mode) or any(l.precision != first.precision or l._knots().dim() != 1 for l in self.layers):
             return None
         if x.size(0) == 0 or not ops._fits32(x, 1):
             return None

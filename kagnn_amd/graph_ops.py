@@ -614,7 +614,7 @@ def kagin_regression_forward(model, data):
     ro_knots, ro_modes = [], []
     for l in ro:
         k = l._knots()
-        if k.dim() != 1 or l.grid_size != G_r or l.spline_order != K_r or G_r + K_r > 16:
+        if k.dim() != 1 or l.grid_size != G_r or l.spline_order != K_r or G_r + K_r > 16 or K_r > 4:
             return None
         m = l.precision if l.precision is not None else default_precision()
         if split_like(m) and max(l.in_features, l.out_features) > 7680:

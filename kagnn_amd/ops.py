@@ -20,7 +20,7 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from ._lib import PREC_FP32, PREC_FP32_GRID, PREC_HALF, PREC_SPLIT
+from ._lib import FUSED_MAX_SPLINE_ORDER, HIGH_ORDER_MAX_KNOTS, MAX_SPLINE_ORDER, PREC_FP32, PREC_FP32_GRID, PREC_HALF, PREC_SPLIT
 
 HUB_THRESHOLD = int(os.environ.get("KAGNN_HUB_THRESHOLD", "96"))       # rows above this many edges are split into segments
 _LAYER_ABI = os.environ.get("KAGNN_LAYER_ABI", "1") != "0"     # 1: kagnn_gin_kan_layer_fwd / _bwd (one library call each way)
@@ -38,6 +38,12 @@ def default_precision() -> int:
     if v in ("half", "fp16", "3"):
         return PREC_HALF
     raise ValueError(f"KAGNN_PRECISION={v!r}: expected 'fp32', 'split' or 'half'")
+
+
+def high_order(spline_order) -> bool:
+    """orders 5..16: the exact-fp32 per-operation kernels only (kan_high_order.hip) -- no split / reduced precision, no fused
+    layer / stack / model call, no parts or moments forward, no refit, no sharding"""
+    return int(spline_order) > FUSED_MAX_SPLINE_ORDER
 
 
 def split_like(mode) -> bool:
@@ -1412,6 +1418,8 @@ def _chain_plan(layers):
     grid_range, update_grid with grid_eps = 1) must not be folded onto the first layer's."""
     first = layers[0]
     mode = first.precision if first.precision is not None else default_precision()
+    if any(high_order(l.spline_order) for l in layers):
+        return None                                      # the fused calls take orders 1..4: the caller composes the operations
     if any(l.precision != first.precision or l.grid_size != first.grid_size or l.spline_order != first.spline_order
            or l.grid_size + l.spline_order > 16 or not l.enable_standalone_scale_spline for l in layers):
         return None
@@ -1471,6 +1479,13 @@ def kan_linear(x, base_weight, spline_weight, spline_scaler, knots, grid_size: i
         mode = PREC_FP32_GRID
     if mode is None:
         mode = default_precision()
+    if high_order(spline_order):
+        # orders 5..16: the exact-fp32 kernels whatever precision was asked for (the rule of every other uncovered shape: the more
+        # accurate kernels, never less), so every mode gives the same bits; never the coefficient-group split below
+        if packed is not None or out is not None:
+            raise ValueError("packed= and out= are not supported at spline_order above 4")
+        if mode != PREC_FP32_GRID:
+            mode = PREC_FP32
     if split_like(mode) and not _fits32(x, base_weight.size(0)):
         mode = PREC_FP32
     if not split_like(mode):
@@ -1651,6 +1666,9 @@ def kan_linear_parts(parts, base_weight, spline_weight, spline_scaler, knots, gr
     if sum(int(t.size(1)) for t in parts) != base_weight.size(1):
         raise AssertionError("parts do not add up to in_features")
     m = default_precision() if mode is None else int(mode)
+    if high_order(spline_order):                         # no parts forward at these orders: write lazy blocks out and concatenate
+        rows = concat_columns([t.materialise() if isinstance(t, AffineRows) else t for t in parts])
+        return kan_linear(rows, base_weight, spline_weight, spline_scaler, knots, grid_size, spline_order, mode)
     lazy = [isinstance(t, AffineRows) for t in parts]
     raw = [t.y if z else t for t, z in zip(parts, lazy)]
     if (_PARTS_ONE_LAUNCH and split_like(m) and knots.dim() == 1 and len(parts) > 1 and not torch.compiler.is_compiling()

@@ -261,6 +261,9 @@ class ShardedKANLinear(nn.Module):
             raise ValueError("in_features and out_features must be divisible by the world size")
         if scatter_out and full.out_features % world:
             raise ValueError("in_features and out_features must be divisible by the world size")
+        if full.spline_order > 4:
+            raise ValueError("sharded KANLinear layers are not supported at spline_order above 4 (the exact-fp32 kernels of these "
+                             "orders take neither packed= nor out=)")
         self.grid_size, self.spline_order = full.grid_size, full.spline_order
         self.out_features = full.out_features
         if columns is None:

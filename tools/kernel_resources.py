@@ -38,6 +38,7 @@ HOT = [
     (r"kan_split_dw_shared_kernel<", 0, 0),            # wide layers (round 4)
     (r"kan_split_fwd_kernel<", 0, 0),
     (r"kan_dx_f32_kernel<|kan_dw_f32_kernel<|kan_fwd_f32_kernel<", 0, 0),   # exact-fp32 mode: the documented fallback (round 4: was up to 53 spilled)
+    (r"kan_ho_", 0, 0),                                # spline orders 5..16 (order a kernel argument: a run-time index into a private array would be scratch)
     (r"agg_rows_v4_kernel<", 0, 0),
     (r"agg_hub", 0, 0),
     (r"agg16_", 0, 0),
