@@ -55,7 +55,7 @@ extern "C" {
 #define KAGNN_DTYPE_F32 0
 #define KAGNN_DTYPE_BF16 1
 
-int kagnn_version(void);          /* 268 = 267 + spline orders 5..KAGNN_MAX_SPLINE_ORDER in the per-operation KANLinear calls (no new entry point); 267 = 266 + kagnn_linear_fwd, kagnn_linear_bwd_input, kagnn_linear_bwd_weight (+ _workspace_bytes); 266 = 265 + kagnn_l1_loss_meter_fwd, kagnn_regression_epoch_update; 265 = 264 + kagnn_node_eval, kagnn_early_stop_update, kagnn_copy_if; 264 = 263 + kagnn_degree_one_hot, kagnn_nll_loss_fwd / _bwd; 263 = 262 + kagnn_batch_assemble; 262 = 261 - the fields edge_src, edge_dst, csr_flags of kagnn_kagin_model_t; 261 = 260 + kagnn_fastkan_fwd_stats_in_kernel; 260 = round 6: + the feature-sharded FastKAN entry points kagnn_fastkan_row_moments .. _shard_bwd_finish, + kagnn_kagin_model_*; 250 = 240 + KAGNN_PREC_HALF; 240 = 230 + kagnn_gin_kan_layer_bwd_bn_sums; 230 = 220 + the *_affine entry points of a folded BatchNorm1d; 220 = 210 + the stage timer) */
+int kagnn_version(void);          /* 269 = 268 + kagnn_kan_edge_abs_sum, kagnn_kan_edge_abs_sum_bwd (+ _workspace_bytes), kagnn_kan_edge_curves; 268 = 267 + spline orders 5..KAGNN_MAX_SPLINE_ORDER in the per-operation KANLinear calls (no new entry point); 267 = 266 + kagnn_linear_fwd, kagnn_linear_bwd_input, kagnn_linear_bwd_weight (+ _workspace_bytes); 266 = 265 + kagnn_l1_loss_meter_fwd, kagnn_regression_epoch_update; 265 = 264 + kagnn_node_eval, kagnn_early_stop_update, kagnn_copy_if; 264 = 263 + kagnn_degree_one_hot, kagnn_nll_loss_fwd / _bwd; 263 = 262 + kagnn_batch_assemble; 262 = 261 - the fields edge_src, edge_dst, csr_flags of kagnn_kagin_model_t; 261 = 260 + kagnn_fastkan_fwd_stats_in_kernel; 260 = round 6: + the feature-sharded FastKAN entry points kagnn_fastkan_row_moments .. _shard_bwd_finish, + kagnn_kagin_model_*; 250 = 240 + KAGNN_PREC_HALF; 240 = 230 + kagnn_gin_kan_layer_bwd_bn_sums; 230 = 220 + the *_affine entry points of a folded BatchNorm1d; 220 = 210 + the stage timer) */
 const char* kagnn_last_error(void);
 
 /* Stage timer -- a measurement aid, off by default (no reference counterpart: the reference times whole epochs with
@@ -517,6 +517,42 @@ int kagnn_kan_grid_refit(const float* x, int64_t ldx, int64_t num_rows, const fl
                          int32_t grid_size, int32_t spline_order, const float* spline_weight,
                          const float* spline_scaler, float* new_spline_weight, void* workspace,
                          size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Per-edge activations of a KANLinear: the edge functions
+ *   phi_{o,i}(t) = base_weight[o,i] silu(t) + spline_scaler[o,i] sum_c spline_weight[o,i,c] B_c(t)
+ * which the layer's forward only sums over i.  Exact fp32 whatever precision the layer runs in (there is no `precision`
+ * argument), spline_order 1..4 (above: KAGNN_ERR_UNSUPPORTED).  `knots` is the shared uniform row [G+2k+1]
+ * (per_feature_knots 0) or the whole grid buffer [in, G+2k+1] (per_feature_knots 1).  base_weight and spline_scaler may be NULL
+ * (a layer without them).  Nothing of size num_rows * out_features is ever stored: the workspaces hold row-slab partials,
+ * which are added in index order (no atomics: the same inputs give the same bits).
+ * ------------------------------------------------------------------------------------------ */
+/* abs_sum[o*ld_abs_sum + i] = sum_n |phi_{o,i}(x[n,i])|  -- a sum, not a mean: results over a partition of the rows add.  A
+ * non-finite x[n,i] makes column i NaN.  num_rows 0: zeros.                                                                  */
+int kagnn_kan_edge_abs_sum_workspace_bytes(int64_t num_rows, int32_t in_features, int32_t out_features, int32_t grid_size,
+                                           int32_t spline_order, size_t* bytes_host);
+int kagnn_kan_edge_abs_sum(const float* x, int64_t ldx, int64_t num_rows, const float* knots, int32_t per_feature_knots,
+                           int32_t in_features, int32_t out_features, int32_t grid_size, int32_t spline_order,
+                           const float* base_weight, const float* spline_weight, const float* spline_scaler, float* abs_sum,
+                           int64_t ld_abs_sum, void* workspace, size_t workspace_bytes, void* stream);
+/* its backward under the upstream gradient g_abs_sum[out, in], s = sign(phi_{o,i}(x[n,i])) with sign(0) = 0:
+ *   g_base_weight[o,i]     = g sum_n s silu(x)            g_spline_weight[o,i,c] = g scaler sum_n s B_c(x)
+ *   g_spline_scaler[o,i]   = g sum_n s sum_c w B_c(x)     gx[n,i]                = sum_o g s phi'_{o,i}(x[n,i])
+ * Every output may be NULL (not wanted); the workspace is needed for the three parameter gradients only.                      */
+int kagnn_kan_edge_abs_sum_bwd_workspace_bytes(int64_t num_rows, int32_t in_features, int32_t out_features, int32_t grid_size,
+                                               int32_t spline_order, size_t* bytes_host);
+int kagnn_kan_edge_abs_sum_bwd(const float* x, int64_t ldx, int64_t num_rows, const float* knots, int32_t per_feature_knots,
+                               int32_t in_features, int32_t out_features, int32_t grid_size, int32_t spline_order,
+                               const float* base_weight, const float* spline_weight, const float* spline_scaler,
+                               const float* g_abs_sum, int64_t ld_g_abs_sum, float* g_base_weight, float* g_spline_weight,
+                               float* g_spline_scaler, float* gx, int64_t ldgx, void* workspace, size_t workspace_bytes,
+                               void* stream);
+/* phi[p, o, i] (contiguous [num_points, out, in]) at the sample points t[p] (ldt 0: one column shared by every feature) or
+ * t[p*ldt + i].                                                                                                                */
+int kagnn_kan_edge_curves(const float* t, int64_t ldt, int64_t num_points, const float* knots, int32_t per_feature_knots,
+                          int32_t in_features, int32_t out_features, int32_t grid_size, int32_t spline_order,
+                          const float* base_weight, const float* spline_weight, const float* spline_scaler, float* phi,
+                          void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * FastKAN layer.  Replaces FastKANLayer.forward (node_classification_clean/fastkan.py:76-85:

@@ -120,6 +120,17 @@ _SIGNATURES = {
     "kagnn_kan_linear_bwd_input_affine_sums": (c_int32, [_P, c_int64, _P, _P, _P, _P, c_int64, c_int64, _P, c_int32, c_int32,
                                                          c_int32, c_int32, c_int32, _P, _P, c_int64, _P, _P, c_size_t, _P]),
     "kagnn_kan_bsplines": (c_int32, [_P, c_int64, c_int64, _P, c_int32, c_int32, c_int32, _P, _P]),
+    "kagnn_kan_edge_abs_sum_workspace_bytes": (c_int32, [c_int64, c_int32, c_int32, c_int32, c_int32, POINTER(c_size_t)]),
+    # x ldx N knots per_feature in out G K bw sw sc S ldS ws bytes stream
+    "kagnn_kan_edge_abs_sum": (c_int32, [_P, c_int64, c_int64, _P, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, _P,
+                                         c_int64, _P, c_size_t, _P]),
+    "kagnn_kan_edge_abs_sum_bwd_workspace_bytes": (c_int32, [c_int64, c_int32, c_int32, c_int32, c_int32, POINTER(c_size_t)]),
+    # x ldx N knots per_feature in out G K bw sw sc gS ldgS g_bw g_sw g_sc gx ldgx ws bytes stream
+    "kagnn_kan_edge_abs_sum_bwd": (c_int32, [_P, c_int64, c_int64, _P, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P, _P,
+                                             _P, c_int64, _P, _P, _P, _P, c_int64, _P, c_size_t, _P]),
+    # t ldt P knots per_feature in out G K bw sw sc phi stream
+    "kagnn_kan_edge_curves": (c_int32, [_P, c_int64, c_int64, _P, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, _P,
+                                        _P]),
     "kagnn_kan_grid_refit_workspace_bytes": (c_int32, [c_int64, c_int32, c_int32, c_int32, POINTER(c_size_t)]),
     "kagnn_kan_grid_refit": (c_int32, [_P, c_int64, c_int64, _P, _P, c_int32, c_int32, c_int32, c_int32, _P, _P, _P,
                                        _P, c_size_t, _P]),

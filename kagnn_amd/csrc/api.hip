@@ -84,7 +84,7 @@ using namespace kagnn;
 #pragma GCC visibility push(default)
 extern "C" {
 
-int kagnn_version(void) { return 268; }
+int kagnn_version(void) { return 269; }
 const char* kagnn_last_error(void) { return g_err; }
 
 int kagnn_stage_timer_enable(const char* only) {
@@ -1020,6 +1020,80 @@ int kagnn_linear_bwd_weight(const float* x, int64_t ldx, const float* gy, int64_
     KAGNN_CHECK_ARG(x && gy && ws, "null array");
     KAGNN_CHECK_ARG(((uintptr_t)ws & 15) == 0, "the workspace must be 16-byte aligned");
     return linear_dw(x, ldx, gy, ldgy, y, ldy, N, in, out, gW, gb, (float*)ws, ws_bytes, as_stream(stream));
+}
+
+// ---------------------------------------------------------------- per-edge activations of a KANLinear (kan_edge.hip)
+// exact fp32 in every precision mode (no `mode` argument); spline orders 1..4; fixed-order slab reductions (no atomics)
+
+int kagnn_kan_edge_abs_sum_workspace_bytes(int64_t N, int32_t in, int32_t out, int32_t G, int32_t K, size_t* bytes) {
+    int rc = check_kan_dims(__func__, in, out, G, K, KAGNN_PREC_FP32);
+    if (rc) return rc;
+    KAGNN_CHECK_ARG(bytes != nullptr && N >= 0, "null output or negative row count");
+    *bytes = kan_edge_abs_sum_ws_bytes(N, in, out);
+    return KAGNN_OK;
+}
+
+int kagnn_kan_edge_abs_sum(const float* x, int64_t ldx, int64_t N, const float* knots, int32_t per_feature_knots, int32_t in,
+                           int32_t out, int32_t G, int32_t K, const float* bw, const float* sw, const float* sc, float* S,
+                           int64_t ldS, void* ws, size_t ws_bytes, void* stream) {
+    KAGNN_STAGE(stream);
+    int rc = check_kan_dims(__func__, in, out, G, K, KAGNN_PREC_FP32);
+    if (rc) return rc;
+    KAGNN_CHECK_ARG(N >= 0 && ldx >= in && ldS >= in, "bad shape");
+    KAGNN_CHECK_ARG(per_feature_knots == 0 || per_feature_knots == 1, "per_feature_knots must be 0 or 1");
+    KAGNN_CHECK_ARG(S != nullptr, "null array");
+    if (N == 0) {                                   // an empty sum: zeros, no kernel
+        KAGNN_HIP(hipMemset2DAsync(S, (size_t)ldS * sizeof(float), 0, (size_t)in * sizeof(float), (size_t)out, as_stream(stream)));
+        return KAGNN_OK;
+    }
+    KAGNN_CHECK_ARG(x && knots && sw && ws, "null array");          // base_weight / spline_scaler NULL: the layer has none
+    return kan_edge_abs_sum(x, ldx, N, knots, per_feature_knots != 0, in, out, G, K, bw, sw, sc, S, ldS, (float*)ws, ws_bytes,
+                            as_stream(stream));
+}
+
+int kagnn_kan_edge_abs_sum_bwd_workspace_bytes(int64_t N, int32_t in, int32_t out, int32_t G, int32_t K, size_t* bytes) {
+    int rc = check_kan_dims(__func__, in, out, G, K, KAGNN_PREC_FP32);
+    if (rc) return rc;
+    KAGNN_CHECK_ARG(bytes != nullptr && N >= 0, "null output or negative row count");
+    *bytes = kan_edge_abs_sum_bwd_ws_bytes(N, in, out, G + K);
+    return KAGNN_OK;
+}
+
+int kagnn_kan_edge_abs_sum_bwd(const float* x, int64_t ldx, int64_t N, const float* knots, int32_t per_feature_knots, int32_t in,
+                               int32_t out, int32_t G, int32_t K, const float* bw, const float* sw, const float* sc,
+                               const float* gS, int64_t ldgS, float* g_bw, float* g_sw, float* g_sc, float* gx, int64_t ldgx,
+                               void* ws, size_t ws_bytes, void* stream) {
+    KAGNN_STAGE(stream);
+    int rc = check_kan_dims(__func__, in, out, G, K, KAGNN_PREC_FP32);
+    if (rc) return rc;
+    KAGNN_CHECK_ARG(N >= 0 && ldx >= in && ldgS >= in && (!gx || ldgx >= in), "bad shape");
+    KAGNN_CHECK_ARG(per_feature_knots == 0 || per_feature_knots == 1, "per_feature_knots must be 0 or 1");
+    KAGNN_CHECK_ARG(!g_bw || bw, "a base_weight gradient needs base_weight");
+    KAGNN_CHECK_ARG(!g_sc || sc, "a spline_scaler gradient needs spline_scaler");
+    if (N == 0) {                                   // empty sums: zeros, no kernel (gx has no rows)
+        const size_t e = (size_t)in * out * sizeof(float);
+        if (g_bw) KAGNN_HIP(hipMemsetAsync(g_bw, 0, e, as_stream(stream)));
+        if (g_sw) KAGNN_HIP(hipMemsetAsync(g_sw, 0, e * (G + K), as_stream(stream)));
+        if (g_sc) KAGNN_HIP(hipMemsetAsync(g_sc, 0, e, as_stream(stream)));
+        return KAGNN_OK;
+    }
+    KAGNN_CHECK_ARG(x && knots && sw && gS, "null array");
+    KAGNN_CHECK_ARG(!(g_bw || g_sw || g_sc) || ws, "the parameter gradients need the workspace");
+    return kan_edge_abs_sum_bwd(x, ldx, N, knots, per_feature_knots != 0, in, out, G, K, bw, sw, sc, gS, ldgS, g_bw, g_sw, g_sc, gx,
+                                ldgx, (float*)ws, ws_bytes, as_stream(stream));
+}
+
+int kagnn_kan_edge_curves(const float* t, int64_t ldt, int64_t P, const float* knots, int32_t per_feature_knots, int32_t in,
+                          int32_t out, int32_t G, int32_t K, const float* bw, const float* sw, const float* sc, float* phi,
+                          void* stream) {
+    KAGNN_STAGE(stream);
+    int rc = check_kan_dims(__func__, in, out, G, K, KAGNN_PREC_FP32);
+    if (rc) return rc;
+    KAGNN_CHECK_ARG(P >= 0 && (ldt == 0 || ldt >= in), "bad shape");
+    KAGNN_CHECK_ARG(per_feature_knots == 0 || per_feature_knots == 1, "per_feature_knots must be 0 or 1");
+    if (P == 0) return KAGNN_OK;
+    KAGNN_CHECK_ARG(t && knots && sw && phi, "null array");
+    return kan_edge_curves(t, ldt, P, knots, per_feature_knots != 0, in, out, G, K, bw, sw, sc, phi, as_stream(stream));
 }
 
 // ---------------------------------------------------------------- direct peer-to-peer exchange (p2p.hip)

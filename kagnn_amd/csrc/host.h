@@ -234,6 +234,17 @@ size_t linear_dw_ws_bytes(long N, int in, int out);
 int linear_dw(const float* x, long ldx, const float* gy, long ldgy, const float* y, long ldy, long N, int in, int out, float* gW,
               float* gb, float* ws, size_t ws_bytes, hipStream_t st);
 
+// ---- kan_edge.hip (per-edge activations phi_{o,i}: abs sum over the rows, its backward, sampled curves; exact fp32, orders 1..4)
+size_t kan_edge_abs_sum_ws_bytes(long N, int in, int out);
+size_t kan_edge_abs_sum_bwd_ws_bytes(long N, int in, int out, int C);
+int kan_edge_abs_sum(const float* x, long ldx, long N, const float* knots, bool pf, int in, int out, int G, int K, const float* bw,
+                     const float* sw, const float* sc, float* S, long ldS, float* ws, size_t ws_bytes, hipStream_t st);
+int kan_edge_abs_sum_bwd(const float* x, long ldx, long N, const float* knots, bool pf, int in, int out, int G, int K, const float*
+                         bw, const float* sw, const float* sc, const float* gS, long ldgS, float* g_bw, float* g_sw, float* g_sc,
+                         float* gx, long ldgx, float* ws, size_t ws_bytes, hipStream_t st);
+int kan_edge_curves(const float* t, long ldt, long P, const float* knots, bool pf, int in, int out, int G, int K, const float* bw,
+                    const float* sw, const float* sc, float* phi, hipStream_t st);
+
 // ---- p2p.hip
 int p2p_reduce_scatter(const float* const* parts, int P, int rank, long N, int out, long ld, float* y, long ldy, hipStream_t st);
 int p2p_all_gather(const float* const* shards, int P, long N, int w, long lds, float* g, long ldg, hipStream_t st);

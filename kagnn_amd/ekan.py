@@ -11,9 +11,10 @@ reference's ``reset_parameters`` :57-77); it is not on the hot path.
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import os
-from typing import List, Optional, Sequence
+from typing import Dict, List, Optional, Sequence
 
 import torch
 from torch import nn
@@ -132,6 +133,13 @@ class KANLinear(nn.Module):
 
     def forward(self, x: torch.Tensor, _packed=None) -> torch.Tensor:
         assert x.dim() == 2 and x.size(1) == self.in_features
+        if ops.layer_inputs_visible():
+            _collect(self, x)
+        return self._forward(x, _packed)
+
+    def _forward(self, x: torch.Tensor, _packed=None) -> torch.Tensor:
+        """the layer itself, without the statistics of a ``collect_edge_l1`` block (the chain walks of ``KAN.edge_l1`` /
+        ``KAN.regularization_loss(x=)`` are not the model's forward)"""
         scaler = self.spline_scaler if self.enable_standalone_scale_spline else None
         return ops.kan_linear(x, self.base_weight, self.spline_weight, scaler, self._knots(),
                               self.grid_size, self.spline_order, self.precision, _packed)
@@ -145,7 +153,8 @@ class KANLinear(nn.Module):
     def forward_parts(self, parts, skip_gradients=None) -> torch.Tensor:
         """``forward(torch.cat(parts, dim=1))`` without the concatenation (``ops.kan_linear_parts``)."""
         knots = self._knots()
-        if knots.dim() != 1 or ops.high_order(self.spline_order):    # adaptive grid (per-feature knot rows) / orders above 4: keep it simple
+        if knots.dim() != 1 or ops.high_order(self.spline_order) or ops.layer_inputs_visible():
+            # adaptive grid (per-feature knot rows) / orders above 4: keep it simple; a collect_edge_l1 block: forward() must see the input
             return self.forward(ops.concat_columns([t.materialise() if isinstance(t, ops.AffineRows) else t for t in parts]))
         scaler = self.spline_scaler if self.enable_standalone_scale_spline else None
         return ops.kan_linear_parts(parts, self.base_weight, self.spline_weight, scaler, knots, self.grid_size,
@@ -216,8 +225,28 @@ class KANLinear(nn.Module):
         sol = torch.linalg.lstsq(g1.cpu(), rhs.cpu(), driver="gelsd").solution     # [in, C, out], minimum norm per feature
         return sol.permute(2, 0, 1).to(dtype=self.spline_weight.dtype, device=dev).contiguous()
 
-    def regularization_loss(self, regularize_activation=1.0, regularize_entropy=1.0):
-        mag = self.spline_weight.abs().mean(-1)
+    # ------------------------------------------------------------------ the edge functions phi_{o,i}
+    def _edge_args(self):
+        scaler = self.spline_scaler if self.enable_standalone_scale_spline else None
+        return self.base_weight, self.spline_weight, scaler, self._knots(), self.grid_size, self.spline_order
+
+    def edge_l1(self, x: torch.Tensor) -> torch.Tensor:
+        """``[out, in]``: the mean magnitude ``mean_n |phi_{o,i}(x[n,i])|`` of every edge's activation over the rows of ``x`` --
+        what the KAN paper's regulariser is defined on, and what tells which inputs / edges a trained layer uses.  One fused
+        kernel (``ops.kan_edge_abs_sum``): no [N, out, in] tensor.  Differentiable.  Spline orders 1..4."""
+        assert x.dim() == 2 and x.size(1) == self.in_features
+        return ops.kan_edge_abs_sum(x, *self._edge_args()) / max(x.size(0), 1)
+
+    @torch.no_grad()
+    def edge_curves(self, points: torch.Tensor) -> torch.Tensor:
+        """``[P, out, in]``: every edge function sampled at ``points`` (``[P]``, shared by all inputs, or ``[P, in]``) -- the
+        reference's ``plot_curve`` (``fastkan.py``) for all edges at once."""
+        return ops.kan_edge_curves(points, *self._edge_args())
+
+    def regularization_loss(self, regularize_activation=1.0, regularize_entropy=1.0, x: Optional[torch.Tensor] = None):
+        """``x=None``: efficient-KAN's stand-in on ``|spline_weight|`` (``ekan.py:213-233``).  With the layer's input ``x``: the
+        KAN paper's L1 + entropy regulariser on the edge activations, ``mag = edge_l1(x)`` in the same formula."""
+        mag = self.spline_weight.abs().mean(-1) if x is None else self.edge_l1(x)
         total = mag.sum()
         share = mag / total
         return regularize_activation * total - regularize_entropy * torch.sum(share * share.log())
@@ -252,7 +281,7 @@ class KAN(nn.Module):
         """all layers' weight packs in one launch when the chain runs on the sparse-forward / split kernels"""
         first = self.layers[0]
         mode = first.precision if first.precision is not None else ops.default_precision()
-        if ops.high_order(self.spline_order) or not ops.split_like(mode) or any(l.precision != first.precision or l._knots().dim() != 1 for l in self.layers):
+        if ops.layer_inputs_visible() or ops.high_order(self.spline_order) or not ops.split_like(mode) or any(l.precision != first.precision or l._knots().dim() != 1 for l in self.layers):
             return None
         if x.size(0) == 0 or not ops._fits32(x, 1):
             return None
@@ -260,5 +289,51 @@ class KAN(nn.Module):
                                     l.spline_scaler if l.enable_standalone_scale_spline else None) for l in self.layers],
                                   self.grid_size, self.spline_order, mode)
 
-    def regularization_loss(self, regularize_activation=1.0, regularize_entropy=1.0):
-        return sum(l.regularization_loss(regularize_activation, regularize_entropy) for l in self.layers)
+    def regularization_loss(self, regularize_activation=1.0, regularize_entropy=1.0, x: Optional[torch.Tensor] = None):
+        """``x``: the chain's input -- every layer is then regularised on the activations of ITS input (the chain is walked)"""
+        if x is None:
+            return sum(l.regularization_loss(regularize_activation, regularize_entropy) for l in self.layers)
+        total = 0.0
+        for i, layer in enumerate(self.layers):
+            total = total + layer.regularization_loss(regularize_activation, regularize_entropy, x=x)
+            if i + 1 < len(self.layers):
+                x = layer._forward(x)             # (not a forward of the model: a collect_edge_l1 block does not record it)
+        return total
+
+    def edge_l1(self, x: torch.Tensor) -> List[torch.Tensor]:
+        """``KANLinear.edge_l1`` of every layer on its own input, ``x`` being the chain's"""
+        out = []
+        for i, layer in enumerate(self.layers):
+            out.append(layer.edge_l1(x))
+            if i + 1 < len(self.layers):
+                x = layer._forward(x)
+        return out
+
+
+def _collect(layer: KANLinear, x: torch.Tensor) -> None:
+    for names, stats in ops._edge_collectors():
+        name = names.get(id(layer))
+        if name is not None:
+            stats[name] = layer.edge_l1(x if x.dtype == torch.float32 else x.float())
+
+
+@contextlib.contextmanager
+def collect_edge_l1(model: nn.Module):
+    """``with collect_edge_l1(model) as stats: out = model(...)`` fills ``stats`` with ``{qualified module name: edge_l1 [out, in]}``
+    for every ``KANLinear`` of spline order <= 4 under ``model``, taken on the input each layer sees during the forwards inside
+    the block (a layer called again overwrites its entry).  The statistics are differentiable: add a regulariser built from them
+    to the loss.  While a block is active the fused layer / stack / model routes, which never expose a layer's input, take their
+    composed per-layer form (``ops.layer_inputs_visible``); outside it nothing changes.
+
+    EVERY ``KANLinear.forward`` inside the block records -- also under ``torch.no_grad()`` or in eval mode -- and the latest call
+    wins, so run inside the block only the forward whose statistics are wanted.  The chain walks of ``KAN.edge_l1`` and
+    ``KAN.regularization_loss(x=)`` do not record.  The block belongs to the thread that opened it: forwards on other threads
+    (data-parallel replicas, a loader thread) keep their fused routes and are not recorded."""
+    names = {id(m): n for n, m in model.named_modules() if isinstance(m, KANLinear) and not ops.high_order(m.spline_order)}
+    entry = (names, {})
+    active = ops._edge_collectors()
+    active.append(entry)
+    try:
+        yield entry[1]
+    finally:
+        active.remove(entry)

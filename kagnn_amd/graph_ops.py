@@ -15,7 +15,7 @@ from .ops import (PREC_FP32, GraphIndex, _batchnorm_fwd_raw, _call, _chain_bwd_b
                   _chain_layers, _chain_plan, _chain_saved, _chain_unsaved, _fits32, _fixed_args, _kan_bwd_input_raw,
                   _kan_bwd_weight_raw, _kan_fwd_raw, _ld, _need_cuda, _on_operand_device, _ptr, _ptr_array, _rows, _same_knots,
                   _segment_broadcast_raw, _segment_pool_raw, _sizes, _stream, _weights_key, _ws, batch_graph_index, default_precision,
-                  kan_pack_chain, split_like)
+                  kan_pack_chain, layer_inputs_visible, split_like)
 
 
 class _GineKanLayerFn(Function):
@@ -272,7 +272,7 @@ def gine_kan_stack(x, edge_attr, g: "GraphIndex", convs, bns):
     stack is outside what the node covers (the caller then runs the loop): GINE convolutions around KAN chains of identical
     hidden -> ... -> hidden widths (<= 64: one pack launch for the stack), one uniform grid and precision for all of them, a
     split-like mode, training-mode affine BatchNorm1d modules, fp32 CUDA rows, at most 16 KANLinears in all, not under torch.compile."""
-    plan = _gine_stack_plan(x, convs, bns)
+    plan = None if layer_inputs_visible() else _gine_stack_plan(x, convs, bns)
     if plan is None:
         return None
     first, nl, mode = plan
@@ -289,7 +289,7 @@ def gine_kan_layer(x, edge_attr, g: "GraphIndex", self_scale: float, net, batch_
     with affine parameters) is given -- as one tape node (``_GineKanLayerFn``), or ``None`` when the chain is outside what the
     node covers (the caller then composes the operations): a KAN chain of uniform grids, one precision, split-like mode, <= 8
     layers, fp32 CUDA rows, not under torch.compile."""
-    if not _GINE_LAYER_ABI or torch.compiler.is_compiling() or not x.is_cuda or x.dtype != torch.float32 or x.size(0) < 2:
+    if not _GINE_LAYER_ABI or layer_inputs_visible() or torch.compiler.is_compiling() or not x.is_cuda or x.dtype != torch.float32 or x.size(0) < 2:
         return None
     layers = list(getattr(net, "layers", []))
     if not (1 <= len(layers) <= 8) or any(type(l).__name__ != "KANLinear" for l in layers):
@@ -581,7 +581,7 @@ def kagin_regression_forward(model, data):
     what the node covers (the caller then runs its modules one by one): training mode, no dropout, embedding-table encoders on
     int64 features, a GINE stack that ``_GineKanStackFn`` takes, a read-out ``KAN`` of uniform-grid ``KANLinear`` layers with at
     most 16 coefficients, no hooks anywhere, not under torch.compile."""
-    if not _GINE_MODEL_NODE or not model.training or model.dropout.p > 0.0 or torch.compiler.is_compiling():
+    if not _GINE_MODEL_NODE or layer_inputs_visible() or not model.training or model.dropout.p > 0.0 or torch.compiler.is_compiling():
         return None
     x, e = data.x, data.edge_attr
     if e.dim() == 1:

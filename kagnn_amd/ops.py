@@ -11,6 +11,7 @@ import ctypes
 import functools
 import inspect
 import os
+import threading
 import weakref
 from ctypes import byref, c_int64, c_size_t
 from typing import NamedTuple, Optional, Tuple
@@ -1445,6 +1446,8 @@ def gin_kan_layer(x, g: GraphIndex, self_scale: float, chain, act_dtype: Optiona
     ``batch_norm=(weight, bias, running_mean, running_var, momentum, eps)``: the training-mode BatchNorm1d that follows the
     convolution joins the node (``_GinKanBnLayerFn``: its element-wise backward runs inside the last input-gradient kernel)
     and the normalised rows are returned."""
+    if layer_inputs_visible():        # a collect_edge_l1 block: the composed form, every KANLinear.forward sees its input
+        return None
     layers = list(chain.layers)
     act = default_activation_dtype() if act_dtype is None else act_dtype
     plan = _chain_plan(layers)
@@ -1723,6 +1726,132 @@ def kan_grid_refit(x, grid_old, grid_new, spline_weight, spline_scaler, grid_siz
     with _device_of(x):
         _call("kagnn_kan_grid_refit", _ptr(x), _ld(x), n, _ptr(go), _ptr(gn), fin, fout, int(grid_size),
               int(spline_order), _ptr(sw), _ptr(sc), _ptr(out), _ptr(ws), ws.numel(), _stream())
+    return out
+
+
+# ======================================================================== per-edge activations (kan_edge.hip)
+# phi_{o,i}(t) = base_weight[o,i] silu(t) + spline_scaler[o,i] sum_c spline_weight[o,i,c] B_c(t): what a KAN user inspects and
+# regularises.  Exact fp32 in every precision mode; spline orders 1..FUSED_MAX_SPLINE_ORDER.
+
+_EDGE_STATE = threading.local()      # .collectors: the calling thread's active kagnn_amd.collect_edge_l1 blocks, innermost last
+
+
+def _edge_collectors() -> list:
+    """the collect_edge_l1 blocks open on THIS thread (a block opened by another thread -- a replica, a loader thread running a
+    model -- neither changes this thread's routing nor receives its statistics)"""
+    got = getattr(_EDGE_STATE, "collectors", None)
+    if got is None:
+        got = _EDGE_STATE.collectors = []
+    return got
+
+
+def layer_inputs_visible() -> bool:
+    """True inside a ``kagnn_amd.collect_edge_l1`` block of the calling thread: every route that hides a KANLinear's input from ``KANLinear.forward``
+    (the fused layer / stack / model nodes, the chain pack, the concatenation-free read-out) then takes its composed
+    per-layer form, so each layer sees -- and can take statistics of -- its own input."""
+    return bool(getattr(_EDGE_STATE, "collectors", None))
+
+
+def _edge_operands(what, rows, base_weight, spline_weight, spline_scaler, knots, grid_size, spline_order):
+    if high_order(spline_order) or int(spline_order) < 1:
+        raise NotImplementedError(f"{what}: spline_order must be in 1..{FUSED_MAX_SPLINE_ORDER} (got {spline_order}); the per-edge "
+                                  "activation kernels do not cover the orders above")
+    _need_cuda(rows, base_weight, spline_weight, spline_scaler, knots)
+    fout, fin, coef = spline_weight.shape
+    if coef != int(grid_size) + int(spline_order):
+        raise AssertionError("spline_weight must be [out_features, in_features, G+k]")
+    kn = knots.detach().to(torch.float32).contiguous()
+    if kn.dim() == 2 and kn.size(0) != fin or kn.size(-1) != int(grid_size) + 2 * int(spline_order) + 1:
+        raise AssertionError("knots must be [G+2k+1] or [in_features, G+2k+1]")
+    bw = None if base_weight is None else base_weight.detach().contiguous()
+    sw = spline_weight.detach().contiguous()
+    sc = None if spline_scaler is None else spline_scaler.detach().contiguous()
+    for t in (bw, sw, sc):
+        if t is not None and t.dtype != torch.float32:
+            raise TypeError(f"kagnn_amd kernels are fp32; got {t.dtype}")
+    if (bw is not None and bw.shape != (fout, fin)) or (sc is not None and sc.shape != (fout, fin)):
+        raise AssertionError("base_weight / spline_scaler must be [out_features, in_features]")
+    return bw, sw, sc, kn, int(kn.dim() == 2), fin, fout
+
+
+def _kan_edge_abs_sum_raw(x, bw, sw, sc, kn, pf, fin, fout, G, K, out=None):
+    n = x.size(0)
+    S = torch.empty((fout, fin), dtype=torch.float32, device=x.device) if out is None else out
+    ws = _ws(_sizes("kagnn_kan_edge_abs_sum_workspace_bytes", n, fin, fout, G, K), x.device)
+    _call("kagnn_kan_edge_abs_sum", _ptr(x), _ld(x), n, _ptr(kn), pf, fin, fout, G, K, _ptr(bw), _ptr(sw), _ptr(sc), _ptr(S),
+          _ld(S) if out is not None else fin, _ptr(ws), ws.numel(), _stream())
+    return S
+
+
+def _kan_edge_abs_sum_bwd_raw(x, bw, sw, sc, kn, pf, fin, fout, G, K, gS, want_bw, want_sw, want_sc, want_x):
+    n = x.size(0)
+    dev = x.device
+    gbw = torch.empty((fout, fin), dtype=torch.float32, device=dev) if want_bw and bw is not None else None
+    gsw = torch.empty((fout, fin, G + K), dtype=torch.float32, device=dev) if want_sw else None
+    gsc = torch.empty((fout, fin), dtype=torch.float32, device=dev) if want_sc and sc is not None else None
+    gx = torch.empty((n, fin), dtype=torch.float32, device=dev) if want_x else None
+    ws = None
+    if gbw is not None or gsw is not None or gsc is not None:
+        ws = _ws(_sizes("kagnn_kan_edge_abs_sum_bwd_workspace_bytes", n, fin, fout, G, K), dev)
+    _call("kagnn_kan_edge_abs_sum_bwd", _ptr(x), _ld(x), n, _ptr(kn), pf, fin, fout, G, K, _ptr(bw), _ptr(sw), _ptr(sc), _ptr(gS),
+          _ld(gS), _ptr(gbw), _ptr(gsw), _ptr(gsc), _ptr(gx), fin, _ptr(ws), 0 if ws is None else ws.numel(), _stream())
+    return gbw, gsw, gsc, gx
+
+
+class _KanEdgeAbsSumFn(Function):
+    """``S[o,i] = sum_n |phi_{o,i}(x[n,i])|``.  Saves the rows and the parameters, not phi: the backward evaluates it again."""
+
+    @staticmethod
+    @_on_operand_device
+    def forward(ctx, x, base_weight, spline_weight, spline_scaler, knots, grid_size, spline_order):
+        bw, sw, sc, kn, pf, fin, fout = _edge_operands("kan_edge_abs_sum", x, base_weight, spline_weight, spline_scaler, knots,
+                                                       grid_size, spline_order)
+        x = _rows(x.detach())
+        if x.size(1) != fin:
+            raise AssertionError("x must be [rows, in_features]")
+        ctx.save_for_backward(x, bw, sw, sc, kn)
+        ctx.dims = (pf, fin, fout, int(grid_size), int(spline_order))
+        return _kan_edge_abs_sum_raw(x, bw, sw, sc, kn, pf, fin, fout, int(grid_size), int(spline_order))
+
+    @staticmethod
+    @once_differentiable
+    @_on_operand_device
+    def backward(ctx, gS):
+        x, bw, sw, sc, kn = ctx.saved_tensors
+        pf, fin, fout, G, K = ctx.dims
+        need = ctx.needs_input_grad
+        gbw, gsw, gsc, gx = _kan_edge_abs_sum_bwd_raw(x, bw, sw, sc, kn, pf, fin, fout, G, K, _rows(gS), need[1], need[2], need[3],
+                                                      need[0])
+        return gx, gbw, gsw, gsc, None, None, None
+
+
+def kan_edge_abs_sum(x, base_weight, spline_weight, spline_scaler, knots, grid_size: int, spline_order: int) -> torch.Tensor:
+    """``S[out, in] = sum_n |phi_{o,i}(x[n,i])|`` -- the per-edge activation magnitude the KAN regulariser is defined on, as a
+    SUM over the rows (sums over a partition of the rows add; ``KANLinear.edge_l1`` divides by the row count).  ``knots`` as
+    for ``kan_linear``: one row [G+2k+1] or the whole grid buffer [in, G+2k+1].  ``base_weight`` / ``spline_scaler`` may be
+    ``None``.  Differentiable in the three parameters and ``x``; nothing of size [N, out, in] (or [N, out]) is stored."""
+    return _KanEdgeAbsSumFn.apply(x, base_weight, spline_weight, spline_scaler, knots, int(grid_size), int(spline_order))
+
+
+def kan_edge_curves(points, base_weight, spline_weight, spline_scaler, knots, grid_size: int, spline_order: int) -> torch.Tensor:
+    """``phi[P, out, in]``: every edge function sampled at ``points`` -- ``[P]`` (the same abscissae for every input feature)
+    or ``[P, in]``.  Not differentiable."""
+    bw, sw, sc, kn, pf, fin, fout = _edge_operands("kan_edge_curves", points, base_weight, spline_weight, spline_scaler, knots,
+                                                   grid_size, spline_order)
+    t = points.detach()
+    if t.dtype != torch.float32:
+        raise TypeError(f"kagnn_amd kernels are fp32; got {t.dtype}")
+    if t.dim() == 1:
+        t, ldt = t.contiguous(), 0
+    elif t.dim() == 2 and t.size(1) == fin:
+        t = _rows(t)
+        ldt = _ld(t)
+    else:
+        raise AssertionError("points must be [P] or [P, in_features]")
+    out = torch.empty((t.size(0), fout, fin), dtype=torch.float32, device=t.device)
+    with _device_of(t):
+        _call("kagnn_kan_edge_curves", _ptr(t), ldt, t.size(0), _ptr(kn), pf, fin, fout, int(grid_size), int(spline_order), _ptr(bw),
+              _ptr(sw), _ptr(sc), _ptr(out), _stream())
     return out
 
 
