@@ -13,6 +13,9 @@ precomputed index instead of boolean indexing (which would synchronise inside th
 """
 from __future__ import annotations
 
+import contextlib
+import ctypes
+import os
 import time
 from typing import NamedTuple
 
@@ -61,6 +64,22 @@ def _time_model_graphed(model, x, edge_index, y, mask, nb_epochs: int, warmup: i
     return float(np.round(dt, 6)), [float(l) for l in losses]
 
 
+@contextlib.contextmanager
+def _autograd_threads(enabled: bool):
+    """Run the backward passes inside on autograd's per-device worker threads (``True``) or on the calling thread (``False``).
+    The backward of a ~1 ms step is ~80 kernel launches from ~10 library calls: handing every tape node to the engine's worker
+    thread costs more than running it (host issue time of the ZINC-shaped step on the round-6 boxes: 1.41-1.50 ms per step with
+    the engine's threads, 0.85-0.90 ms on the calling thread -- tools/host_profile_cfg4.py, profiles/r06_experiments.md).  One
+    device, one stream: nothing runs concurrently in that backward anyway.  The timed loops pass ``KAGNN_CFG4_MT == "1"``, the
+    switch that keeps the engine's threads for the A/B; the experiment loops always pass ``False``."""
+    was = torch.autograd.is_multithreading_enabled()
+    torch.autograd.set_multithreading_enabled(enabled)
+    try:
+        yield
+    finally:
+        torch.autograd.set_multithreading_enabled(was)
+
+
 def time_model(model, x, edge_index, y, mask, nb_epochs: int = 20, warmup: int = 2, graphed: bool = False):
     if graphed:
         return _time_model_graphed(model, x, edge_index, y, mask, nb_epochs, warmup)
@@ -68,7 +87,6 @@ def time_model(model, x, edge_index, y, mask, nb_epochs: int = 20, warmup: int =
     # (the reference's optimiser, time_model.py:36; on the device its update runs as ONE fused launch over all parameter tensors
     # instead of ~10 multi-tensor launches: same update rule)
     try:
-        import os
         optimizer = torch.optim.Adam(model.parameters(), lr=0.001, fused=bool(x.is_cuda) and os.environ.get("KAGNN_FUSED_ADAM", "1") != "0")
     except (TypeError, RuntimeError):
         optimizer = torch.optim.Adam(model.parameters(), lr=0.001)
@@ -84,12 +102,7 @@ def time_model(model, x, edge_index, y, mask, nb_epochs: int = 20, warmup: int =
         optimizer.step()
         return loss
 
-    # (round 6) the backward on the calling thread: on small graphs an epoch is ~1 ms of ~100 short kernels and handing its tape nodes
-    # to autograd's per-device worker thread costs more than running them (see train_graph_batches; KAGNN_CFG4_MT=1 for the A/B)
-    import os
-    mt_was = torch.autograd.is_multithreading_enabled()
-    torch.autograd.set_multithreading_enabled(os.environ.get("KAGNN_CFG4_MT", "0") == "1")
-    try:
+    with _autograd_threads(os.environ.get("KAGNN_CFG4_MT", "0") == "1"):     # (round 6: on small graphs an epoch is such a ~1 ms step)
         for _ in range(warmup):
             epoch()
         if x.is_cuda:
@@ -100,8 +113,6 @@ def time_model(model, x, edge_index, y, mask, nb_epochs: int = 20, warmup: int =
         if x.is_cuda:
             torch.cuda.synchronize()
         dt = (time.perf_counter() - t0) / nb_epochs
-    finally:
-        torch.autograd.set_multithreading_enabled(mt_was)
     return float(np.round(dt, 6)), [float(l.detach()) for l in losses]
 
 
@@ -118,7 +129,6 @@ class Adam:
 
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0, amsgrad: bool = False,
                  maximize: bool = False):
-        import ctypes
         if amsgrad or maximize:
             raise NotImplementedError("kagnn_amd.harness.Adam implements torch.optim.Adam's default rule only (no amsgrad / maximize); "
                                       "pass a torch.optim.Adam to train_graph_batches(optimizer=...) for those")
@@ -154,13 +164,13 @@ class Adam:
 
     @torch.no_grad()
     def step(self):
-        from . import ops
         self.steps += 1
         f32 = torch.float32
         ptrs = [p.data_ptr() for p in self.params]
         if ptrs != self._p_ptr:                                       # a parameter's storage was replaced (p.data = ...): follow it
             self._p_ptr, self._p_tab = ptrs, self._VP(*ptrs)
         gs = [p.grad for p in self.params]
+        keep = None                                                   # the indices of the tensors that step; None: all
         if not all(g is not None and g.dtype is f32 and g.is_contiguous() for g in gs):     # rare: a subset, or gradients to convert
             # (`None in gs` would compare every TENSOR with None through torch's dispatcher: 10 us each)
             keep = [k for k, g in enumerate(gs) if g is not None]
@@ -169,46 +179,30 @@ class Adam:
                 return
             if len(keep) < len(gs) and self._tensor_steps is None:    # first time a tensor sits a step out: counts diverge from here
                 self._tensor_steps = [self.steps - 1] * len(gs)
-            gs = {k: (gs[k] if gs[k].dtype is f32 and gs[k].is_contiguous() else gs[k].to(f32).contiguous()) for k in keep}
-            groups = {}
-            if self._tensor_steps is None:
-                groups[self.steps] = keep
-            else:
-                for k in keep:
-                    self._tensor_steps[k] += 1
-                    groups.setdefault(self._tensor_steps[k], []).append(k)
-            for t, ks in groups.items():                              # one library call per distinct step count (normally one)
-                VP, I64 = _ctypes_arrays(len(ks))
-                with ops._device_of(self.params[0]):
-                    ops._call("kagnn_adam_step", len(ks), VP(*[self._p_ptr[k] for k in ks]), VP(*[gs[k].data_ptr() for k in ks]),
-                              VP(*[self._m_ptr[k] for k in ks]), VP(*[self._v_ptr[k] for k in ks]), I64(*[self._numel[k] for k in ks]),
-                              self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay, t, ops._stream())
-            return
-        if self._tensor_steps is not None:                            # all tensors present, but their counts differ
-            groups = {}
-            for k in range(len(gs)):
-                self._tensor_steps[k] += 1
-                groups.setdefault(self._tensor_steps[k], []).append(k)
-            if len(groups) > 1:
-                for t, ks in groups.items():
-                    VP, I64 = _ctypes_arrays(len(ks))
-                    with ops._device_of(self.params[0]):
-                        ops._call("kagnn_adam_step", len(ks), VP(*[self._p_ptr[k] for k in ks]), VP(*[gs[k].data_ptr() for k in ks]),
-                                  VP(*[self._m_ptr[k] for k in ks]), VP(*[self._v_ptr[k] for k in ks]), I64(*[self._numel[k] for k in ks]),
-                                  self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay, t, ops._stream())
-                return
-            step_t = next(iter(groups))
+            gs = [g if g is None or (g.dtype is f32 and g.is_contiguous()) else g.to(f32).contiguous() for g in gs]
+        if self._tensor_steps is None:
+            return self._launch(keep, gs, self.steps)
+        groups = {}
+        for k in range(len(gs)) if keep is None else keep:
+            self._tensor_steps[k] += 1
+            groups.setdefault(self._tensor_steps[k], []).append(k)
+        for t, ks in groups.items():                                  # one library call per distinct step count (normally one)
+            self._launch(ks, gs, t)
+
+    def _launch(self, ks, gs, t: int):
+        """one ``kagnn_adam_step`` at step count ``t`` over the tensors with the indices ``ks`` (None: all) and the gradients
+        ``gs[k]``; for all of them, the pointer tables cached at construction and one fresh table of gradient pointers"""
+        from . import ops
+        n = len(gs if ks is None else ks)
+        if n == len(gs):
+            tables = (self._p_tab, self._VP(*[g.data_ptr() for g in gs]), self._m_tab, self._v_tab, self._n_tab)
         else:
-            step_t = self.steps
-        tables = (self._p_tab, self._VP(*[g.data_ptr() for g in gs]), self._m_tab, self._v_tab, self._n_tab)
+            VP, I64 = ctypes.c_void_p * n, ctypes.c_int64 * n
+            tables = (VP(*[self._p_ptr[k] for k in ks]), VP(*[gs[k].data_ptr() for k in ks]), VP(*[self._m_ptr[k] for k in ks]),
+                      VP(*[self._v_ptr[k] for k in ks]), I64(*[self._numel[k] for k in ks]))
         with ops._device_of(self.params[0]):
-            ops._call("kagnn_adam_step", len(gs), *tables, self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay, step_t,
+            ops._call("kagnn_adam_step", n, *tables, self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay, t,
                       ops._stream())
-
-
-def _ctypes_arrays(n: int):
-    import ctypes
-    return ctypes.c_void_p * n, ctypes.c_int64 * n
 
 
 class GradientReplicas:
@@ -285,13 +279,8 @@ def train_graph_batches(model, batches, nb_epochs: int = 1, warmup: int = 0, lr:
     def batch_loss(data):
         return loss_fn(model(data).squeeze(), data.y.squeeze())
 
-    def end():
-        if not losses:
-            return torch.zeros(())
-        # the epoch's mean training loss, weighted by graphs per batch: three small launches per EPOCH, still no read-back
-        # (the caller converts after the final synchronisation)
-        w = torch.tensor(weights, dtype=losses[0].dtype).to(losses[0].device, non_blocking=True)
-        return (torch.stack(losses) * w).sum() / max(sum(weights), 1.0)
+    def end():             # (still no read-back: the caller converts after the final synchronisation)
+        return _weighted_mean(losses, weights) if losses else torch.zeros(())
 
     dt, means = _train_minibatches(model, batches, nb_epochs, warmup, lr, optimizer, replicas, begin, batch_loss,
                                    lambda loss, data: (losses.append(loss), weights.append(_graphs_in(data))), end)
@@ -300,6 +289,35 @@ def train_graph_batches(model, batches, nb_epochs: int = 1, warmup: int = 0, lr:
 
 def _graphs_in(data) -> float:
     return float(int(getattr(data, "num_graphs", 0) or data.y.size(0)))
+
+
+def _weighted_mean(losses, weights) -> torch.Tensor:
+    """the mean of the per-batch device losses weighted by graphs per batch: three small launches per EPOCH, no read-back"""
+    w = torch.tensor(weights, dtype=losses[0].dtype).to(losses[0].device, non_blocking=True)
+    return (torch.stack(losses) * w).sum() / max(sum(weights), 1.0)
+
+
+def _training_step(optimizer, replicas=None):
+    """the training step every loop here takes: ``step(loss_of, *args)`` does ``{zero_grad(set_to_none=True), loss = loss_of(*args),
+    backward, [the replicas' gradient all-reduce], optimizer.step()}`` and returns the loss.  The root gradient of the backward is
+    cached (the implicit one would be a ``torch.ones_like``: one fill launch per step) and made again only when the loss changes
+    device, dtype or shape; with replicas it is their ``scale()``."""
+    root = None
+
+    def step(loss_of, *args):
+        nonlocal root
+        optimizer.zero_grad(set_to_none=True)
+        loss = loss_of(*args)
+        if replicas is None:
+            if root is None or root.device != loss.device or root.dtype != loss.dtype or root.shape != loss.shape:
+                root = torch.ones(loss.shape, dtype=loss.dtype, device=loss.device)
+            loss.backward(root)
+        else:
+            loss.backward(replicas.scale(loss))
+            replicas.sync()
+        optimizer.step()
+        return loss
+    return step
 
 
 def _train_minibatches(model, batches, nb_epochs, warmup, lr, optimizer, replicas, begin, batch_loss, record, end):
@@ -311,38 +329,17 @@ def _train_minibatches(model, batches, nb_epochs, warmup, lr, optimizer, replica
     from . import ops as ops_mod
     model.train()
     on_gpu = any(p.is_cuda for p in model.parameters())
-
-    root = []
-
-    def one(like):
-        if not root or root[0].device != like.device or root[0].dtype != like.dtype or root[0].shape != like.shape:
-            root[:] = [torch.ones(like.shape, dtype=like.dtype, device=like.device)]
-        return root[0]
+    step = _training_step(optimizer, replicas)
 
     def epoch():
         begin()
         for data in batches:
-            optimizer.zero_grad(set_to_none=True)
-            loss = batch_loss(data)
-            if replicas is None:
-                loss.backward(one(loss))           # (the implicit root gradient would be a torch.ones_like: one fill launch per step)
-            else:
-                loss.backward(replicas.scale(loss))
-                replicas.sync()
-            optimizer.step()
-            record(loss.detach(), data)            # (kept on the device: no kernel and no read-back per step)
+            record(step(batch_loss, data).detach(), data)      # (kept on the device: no kernel and no read-back per step)
         if on_gpu:
             ops_mod.flush_graph_checks()       # the epoch's deferred node-id range checks (incl. the LAST batch's): one wait per epoch
         return end()
 
-    # The backward of a ~1 ms step is ~80 kernel launches from ~10 library calls: handing every tape node to autograd's per-device
-    # worker thread costs more than running it (host issue time of the ZINC-shaped step on the round-6 boxes: 1.41-1.50 ms per
-    # step with the engine's threads, 0.85-0.90 ms on the calling thread -- tools/host_profile_cfg4.py, profiles/r06_experiments.md).
-    # One device, one stream: nothing runs concurrently in that backward anyway.
-    import os
-    mt_was = torch.autograd.is_multithreading_enabled()
-    torch.autograd.set_multithreading_enabled(os.environ.get("KAGNN_CFG4_MT", "0") == "1")     # (=1: the engine's worker threads, for A/B)
-    try:
+    with _autograd_threads(os.environ.get("KAGNN_CFG4_MT", "0") == "1"):     # (=1: the engine's worker threads, for A/B)
         for _ in range(warmup):
             epoch()
         if on_gpu:
@@ -352,8 +349,6 @@ def _train_minibatches(model, batches, nb_epochs, warmup, lr, optimizer, replica
         if on_gpu:
             torch.cuda.synchronize()
         dt = (time.perf_counter() - t0) / max(1, nb_epochs * len(batches))
-    finally:
-        torch.autograd.set_multithreading_enabled(mt_was)
     return float(dt), means
 
 
@@ -370,19 +365,19 @@ def evaluate_graph_batches(model, batches, loss_fn=None) -> float:
     with torch.no_grad():
         for data in batches:
             losses.append(loss_fn(model(data).squeeze(), data.y.squeeze()).detach())
-            weights.append(float(int(getattr(data, "num_graphs", 0) or data.y.size(0))))
+            weights.append(_graphs_in(data))
     if any(p.is_cuda for p in model.parameters()):
         ops_mod.flush_graph_checks()
-    if not losses:
-        return 0.0
-    w = torch.tensor(weights, dtype=losses[0].dtype).to(losses[0].device, non_blocking=True)
-    return float((torch.stack(losses) * w).sum() / max(sum(weights), 1.0))
+    return float(_weighted_mean(losses, weights)) if losses else 0.0
 
 
-def _dataset_size(loader, seen: int) -> int:
-    """``len(loader.dataset)``, the divisor of the reference's loops; for a plain list of batches, the graphs it holds"""
+def _dataset_size(loader, seen=None) -> int:
+    """``len(loader.dataset)``, the divisor of the reference's loops; for a plain list of batches, the graphs it holds (``seen``,
+    where a pass over them has counted these already)"""
     ds = getattr(loader, "dataset", None)
-    return len(ds) if ds is not None else seen
+    if ds is not None:
+        return len(ds)
+    return int(sum(_graphs_in(d) for d in loader)) if seen is None else seen
 
 
 def train_graph_classification(model, loader, nb_epochs: int = 1, warmup: int = 0, lr: float = 1e-3, optimizer=None, loss_fn=None):
@@ -448,6 +443,37 @@ def evaluate_graph_classification(model, loader):
     return nll_sum / n, correct / n
 
 
+class _BestWeights:
+    """the best-weights copy of the two early-stopping experiments: the live ``state_dict`` entries of ``model`` and clones of them
+    (``saved``: the starting weights, until ``_run_until_stopped`` copies an improved epoch's over them); ``restore()`` loads the
+    clones back.  ``who``: the calling function, for the error message."""
+
+    def __init__(self, model, who: str):
+        self.live = list(model.state_dict().values())
+        if any(not t.is_contiguous() for t in self.live):
+            raise ValueError(f"{who}: every state_dict entry must be contiguous (the snapshot copies them as bytes)")
+        self.saved = [t.detach().clone() for t in self.live]
+
+    def restore(self) -> None:
+        with torch.no_grad():
+            for t, saved in zip(self.live, self.saved):
+                t.copy_(saved)
+
+
+def _run_until_stopped(one_epoch, epochs: int, poll_every: int, stop, best=None) -> None:
+    """the polled loop of the two early-stopping experiments: up to ``epochs`` times ``one_epoch()`` (which ends in ``stop.update``),
+    then ``ops.copy_if(stop.improved, ...)`` into ``best``, a ``_BestWeights``, when there is one; the host reads the stopper's
+    record every ``poll_every`` epochs and leaves at the first poll that sees the stop.  The backward passes run on the calling thread."""
+    from . import ops as ops_mod
+    with _autograd_threads(False):
+        for epoch in range(epochs):
+            one_epoch()
+            if best is not None:
+                ops_mod.copy_if(stop.improved, best.saved, best.live)
+            if (epoch + 1) % poll_every == 0 and stop.read(history=False).stopped:
+                break
+
+
 class GraphRegressionResult(NamedTuple):
     """what ``train_graph_regression`` returns.  ``best_val_loss`` / ``test_loss``: what the reference's
     ``train_model_with_parameters`` returns -- the lowest validation figure (ties included) and the test figure of the last epoch
@@ -477,12 +503,6 @@ def _regression_targets(loader) -> int:
     if y is None:
         raise TypeError("graph regression needs a kagnn_amd.data.DeviceBatchLoader over a dataset with targets, or a list of batches")
     return 1 if y.dim() == 1 else int(y.size(1))
-
-
-def _loader_size(loader) -> int:
-    """``len(loader.dataset)``, the divisor of the reference's loops; for a plain list of batches, the graphs it holds"""
-    ds = getattr(loader, "dataset", None)
-    return len(ds) if ds is not None else int(sum(_graphs_in(d) for d in loader))
 
 
 def _regression_output(model, data):
@@ -543,7 +563,7 @@ def train_graph_regression(model, train_loader, val_loader, test_loader=None, ep
         raise ValueError("train_graph_regression: the model has no parameters")
     dev = params[0].device
     targets = _regression_targets(train_loader)
-    sizes = (_loader_size(train_loader), _loader_size(val_loader), _loader_size(val_loader if test_loader is None else test_loader))
+    sizes = (_dataset_size(train_loader), _dataset_size(val_loader), _dataset_size(val_loader if test_loader is None else test_loader))
     scale = None
     if target_scale is not None:
         scale = target_scale.detach().to(torch.float32).reshape(-1).contiguous()
@@ -554,51 +574,36 @@ def train_graph_regression(model, train_loader, val_loader, test_loader=None, ep
     meters = [ops_mod.RegressionMeter(targets, dev) for _ in range(2 if test_loader is None else 3)]
     train_meter, val_meter, test_meter = meters[0], meters[1], (None if test_loader is None else meters[2])
     stop = ops_mod.RegressionStop(patience, min_delta, max_epochs=epochs, num_targets=targets, device=dev)
-    live = snapshot = None
-    if keep_best:
-        live = list(model.state_dict().values())
-        if any(not t.is_contiguous() for t in live):
-            raise ValueError("train_graph_regression: every state_dict entry must be contiguous (the snapshot copies them as bytes)")
-        snapshot = [t.detach().clone() for t in live]
-    root = None
-    mt_was = torch.autograd.is_multithreading_enabled()
-    torch.autograd.set_multithreading_enabled(False)              # (a ~1 ms backward of short kernels: see _train_minibatches)
-    try:
-        for epoch in range(epochs):
-            model.train()
-            for data in train_loader:
-                optimizer.zero_grad(set_to_none=True)
-                pred = _regression_output(model, data)
-                if loss_fn is None:
-                    loss = ops_mod.l1_loss(pred, data.y, accumulate=train_meter)
-                else:
-                    loss = loss_fn(pred, data.y)
-                    with torch.no_grad():
-                        ops_mod.l1_loss(pred.detach(), data.y, accumulate=train_meter)
-                if root is None or root.shape != loss.shape or root.dtype != loss.dtype:
-                    root = torch.ones_like(loss)
-                loss.backward(root)
-                optimizer.step()
-            model.eval()
-            with torch.no_grad():
-                for loader, meter in ((val_loader, val_meter), (test_loader, test_meter)):
-                    if loader is not None:
-                        for data in loader:
-                            ops_mod.l1_loss(_regression_output(model, data), data.y, accumulate=meter, scale=scale)
-            stop.update(train_meter, val_meter, test_meter, sizes)
-            if keep_best:
-                ops_mod.copy_if(stop.improved, snapshot, live)
-            ops_mod.flush_graph_checks()       # the epoch's deferred checks (three loaders' batches): one wait per epoch
-            if (epoch + 1) % poll_every == 0 and stop.read(history=False).stopped:
-                break
-    finally:
-        torch.autograd.set_multithreading_enabled(mt_was)
+    best = _BestWeights(model, "train_graph_regression") if keep_best else None
+    step = _training_step(optimizer)
+
+    def train_loss(data):
+        pred = _regression_output(model, data)
+        if loss_fn is None:
+            return ops_mod.l1_loss(pred, data.y, accumulate=train_meter)
+        loss = loss_fn(pred, data.y)
+        with torch.no_grad():
+            ops_mod.l1_loss(pred.detach(), data.y, accumulate=train_meter)
+        return loss
+
+    def one_epoch():
+        model.train()
+        for data in train_loader:
+            step(train_loss, data)
+        model.eval()
+        with torch.no_grad():
+            for loader, meter in ((val_loader, val_meter), (test_loader, test_meter)):
+                if loader is not None:
+                    for data in loader:
+                        ops_mod.l1_loss(_regression_output(model, data), data.y, accumulate=meter, scale=scale)
+        stop.update(train_meter, val_meter, test_meter, sizes)
+        ops_mod.flush_graph_checks()           # the epoch's deferred checks (three loaders' batches): one wait per epoch
+
+    _run_until_stopped(one_epoch, epochs, poll_every, stop, best)
     ops_mod.flush_graph_checks()
     st = stop.read()
     if keep_best:
-        with torch.no_grad():
-            for t, saved in zip(live, snapshot):
-                t.copy_(saved)
+        best.restore()
     model.eval()
     hist = st.history
     return GraphRegressionResult(best_val_loss=st.best_val, test_loss=st.test_at_best, epochs_run=st.epochs, best_epoch=st.best_epoch,
@@ -680,39 +685,27 @@ def train_node_classification(model, x, edge_index, y, train_mask, val_mask, tes
     bits = ops_mod.split_bits(train_mask, val_mask, test_mask, out=_bits)
     if optimizer is None:
         optimizer = Adam(model.parameters(), lr=lr)
-    live = list(model.state_dict().values())
-    if any(not t.is_contiguous() for t in live):
-        raise ValueError("train_node_classification: every state_dict entry must be contiguous (the snapshot copies them as bytes)")
-    snapshot = [t.detach().clone() for t in live]                 # the script saves the starting weights before the first epoch
+    best = _BestWeights(model, "train_node_classification")       # the script saves the starting weights before the first epoch
     stop = ops_mod.EarlyStop(patience, min_delta, max_epochs=epochs, num_splits=3, device=x.device)
     records = torch.empty((3, 3), dtype=torch.int64, device=x.device)
-    root = None
+    step = _training_step(optimizer)
     model.train()
-    mt_was = torch.autograd.is_multithreading_enabled()
-    torch.autograd.set_multithreading_enabled(False)              # (a ~1 ms backward of short kernels: see _train_minibatches)
-    try:
-        for epoch in range(epochs):
-            optimizer.zero_grad(set_to_none=True)
+
+    def train_loss():
+        out = model(x, g)
+        return ops_mod.softmax_cross_entropy(out, y, train_mask) if loss_fn is None else loss_fn(out[train_mask], y[train_mask])
+
+    def one_epoch():
+        step(train_loss)
+        with torch.no_grad():
             out = model(x, g)
-            loss = ops_mod.softmax_cross_entropy(out, y, train_mask) if loss_fn is None else loss_fn(out[train_mask], y[train_mask])
-            if root is None:
-                root = torch.ones_like(loss)
-            loss.backward(root)
-            optimizer.step()
-            with torch.no_grad():
-                out = model(x, g)
-            ops_mod.node_eval(out, y, bits, 3, out=records)
-            stop.update(records, 1)
-            ops_mod.copy_if(stop.improved, snapshot, live)
-            if (epoch + 1) % poll_every == 0 and stop.read(history=False).stopped:
-                break
-    finally:
-        torch.autograd.set_multithreading_enabled(mt_was)
+        ops_mod.node_eval(out, y, bits, 3, out=records)
+        stop.update(records, 1)
+
+    _run_until_stopped(one_epoch, epochs, poll_every, stop, best)
     ops_mod.flush_graph_checks(x.device)
     st = stop.read()
-    with torch.no_grad():
-        for t, saved in zip(live, snapshot):
-            t.copy_(saved)
+    best.restore()
     at = st.epochs - 1 if metrics_at == "last" else st.best_epoch
     nan = float("nan")
     (_, train_acc), (val_loss, val_acc), (_, test_acc) = [_split_figures(st.history[at, s]) for s in range(3)] if at >= 0 else [(nan, nan)] * 3
@@ -754,10 +747,7 @@ def make_model(params: dict):
     architectures: the same ``params`` dictionary builds the same model classes.  The MLP baselines
     (``architecture == 'mlp'``) are stock torch_geometric models and outside this package."""
     from .models import GFASTKAN_Nodes, GKAN_Nodes
-    common = dict(conv_type=params["conv_type"], mp_layers=params["mp_layers"], num_features=params["num_features"],
-                  hidden_channels=params["hidden_channels"], num_classes=params["num_classes"], skip=params["skip"],
-                  hidden_layers=params["hidden_layers"], dropout=params["dropout"], grid_size=params["grid_size"],
-                  heads=params.get("heads", 4))
+    common = dict(_model_kwargs(params), grid_size=params["grid_size"])
     if params["architecture"] == "kan":
         return GKAN_Nodes(spline_order=params["spline_order"], **common)
     if params["architecture"] == "fastkan":
@@ -765,12 +755,17 @@ def make_model(params: dict):
     raise ValueError("kagnn_amd.harness.make_model builds the 'kan' and 'fastkan' architectures")
 
 
+def _model_kwargs(params: dict) -> dict:
+    """the keyword arguments every node-model class takes, from the reference's ``params`` dictionary"""
+    return dict(conv_type=params["conv_type"], mp_layers=params["mp_layers"], num_features=params["num_features"],
+                hidden_channels=params["hidden_channels"], num_classes=params["num_classes"], skip=params["skip"],
+                hidden_layers=params["hidden_layers"], dropout=params["dropout"], heads=params.get("heads", 4))
+
+
 def make_any_model(params: dict):
     """``utils.make_model`` of the reference (``node_classification_clean/utils.py:88-123``) for every architecture: ``'mlp'`` builds
     this package's ``baselines.GNN_Nodes`` from the same ``params`` dictionary, everything else goes to ``make_model``."""
     if params["architecture"] == "mlp":
         from .baselines import GNN_Nodes
-        return GNN_Nodes(conv_type=params["conv_type"], mp_layers=params["mp_layers"], num_features=params["num_features"],
-                         hidden_channels=params["hidden_channels"], num_classes=params["num_classes"], skip=params["skip"],
-                         hidden_layers=params["hidden_layers"], dropout=params["dropout"], heads=params.get("heads", 4))
+        return GNN_Nodes(**_model_kwargs(params))
     return make_model(params)

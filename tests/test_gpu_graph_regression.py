@@ -505,6 +505,21 @@ def test_lists_of_premade_batches_serve_as_loaders():
     assert mean == r2.val_losses[-1] and torch.equal(per_target, r2.per_target[-1, 1])
 
 
+def test_the_training_pass_is_train_graph_batches_step_bit_for_bit():
+    """default loss, default harness.Adam: the experiment's training pass and ``train_graph_batches`` take the same step, so the same
+    batches leave the same weights (the metered loss gives the plain loss's gradient bits; the evaluation passes between the epochs
+    run in ``eval()`` mode and the model has no dropout, so they change no state)"""
+    ds, _ = _setup("KAGCN", 1)
+    lists = [list(loader) for loader in _loaders(ds)]                   # (unshuffled: 16 + 16 + 8, the same batches every epoch)
+    ops.flush_graph_checks()
+    ma = _model("KAGCN", 1)
+    mb = copy.deepcopy(ma)
+    res = harness.train_graph_regression(ma, *lists, epochs=2, lr=LR, patience=100, poll_every=1)
+    harness.train_graph_batches(mb, lists[0], nb_epochs=2, warmup=0, lr=LR)
+    assert res.epochs_run == 2 and not res.stopped
+    _same_state(ma, mb, "train_graph_regression against train_graph_batches")
+
+
 class _Stub(torch.nn.Module):
     """one parameter; with lr = 0 every epoch repeats the first one's figures exactly"""
 
