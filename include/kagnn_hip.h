@@ -55,7 +55,7 @@ extern "C" {
 #define KAGNN_DTYPE_F32 0
 #define KAGNN_DTYPE_BF16 1
 
-int kagnn_version(void);          /* 269 = 268 + kagnn_kan_edge_abs_sum, kagnn_kan_edge_abs_sum_bwd (+ _workspace_bytes), kagnn_kan_edge_curves; 268 = 267 + spline orders 5..KAGNN_MAX_SPLINE_ORDER in the per-operation KANLinear calls (no new entry point); 267 = 266 + kagnn_linear_fwd, kagnn_linear_bwd_input, kagnn_linear_bwd_weight (+ _workspace_bytes); 266 = 265 + kagnn_l1_loss_meter_fwd, kagnn_regression_epoch_update; 265 = 264 + kagnn_node_eval, kagnn_early_stop_update, kagnn_copy_if; 264 = 263 + kagnn_degree_one_hot, kagnn_nll_loss_fwd / _bwd; 263 = 262 + kagnn_batch_assemble; 262 = 261 - the fields edge_src, edge_dst, csr_flags of kagnn_kagin_model_t; 261 = 260 + kagnn_fastkan_fwd_stats_in_kernel; 260 = round 6: + the feature-sharded FastKAN entry points kagnn_fastkan_row_moments .. _shard_bwd_finish, + kagnn_kagin_model_*; 250 = 240 + KAGNN_PREC_HALF; 240 = 230 + kagnn_gin_kan_layer_bwd_bn_sums; 230 = 220 + the *_affine entry points of a folded BatchNorm1d; 220 = 210 + the stage timer) */
+int kagnn_version(void);          /* 270 = 269 + kagnn_fastkan_edge_abs_sum, kagnn_fastkan_edge_abs_sum_bwd (+ _workspace_bytes), kagnn_fastkan_edge_curves; 269 = 268 + kagnn_kan_edge_abs_sum, kagnn_kan_edge_abs_sum_bwd (+ _workspace_bytes), kagnn_kan_edge_curves; 268 = 267 + spline orders 5..KAGNN_MAX_SPLINE_ORDER in the per-operation KANLinear calls (no new entry point); 267 = 266 + kagnn_linear_fwd, kagnn_linear_bwd_input, kagnn_linear_bwd_weight (+ _workspace_bytes); 266 = 265 + kagnn_l1_loss_meter_fwd, kagnn_regression_epoch_update; 265 = 264 + kagnn_node_eval, kagnn_early_stop_update, kagnn_copy_if; 264 = 263 + kagnn_degree_one_hot, kagnn_nll_loss_fwd / _bwd; 263 = 262 + kagnn_batch_assemble; 262 = 261 - the fields edge_src, edge_dst, csr_flags of kagnn_kagin_model_t; 261 = 260 + kagnn_fastkan_fwd_stats_in_kernel; 260 = round 6: + the feature-sharded FastKAN entry points kagnn_fastkan_row_moments .. _shard_bwd_finish, + kagnn_kagin_model_*; 250 = 240 + KAGNN_PREC_HALF; 240 = 230 + kagnn_gin_kan_layer_bwd_bn_sums; 230 = 220 + the *_affine entry points of a folded BatchNorm1d; 220 = 210 + the stage timer) */
 const char* kagnn_last_error(void);
 
 /* Stage timer -- a measurement aid, off by default (no reference counterpart: the reference times whole epochs with
@@ -593,6 +593,44 @@ int kagnn_fastkan_bwd(const float* x, int64_t ldx, const float* gy, int64_t ldgy
                       float* g_ln_bias, float* g_spline_weight, float* g_base_weight,
                       float* g_base_bias, int32_t precision, void* workspace,
                       size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Per-edge activations of a FastKAN layer: the edge functions
+ *   phi_{o,i}(n) = sum_g spline_weight[o, i*num_grids+g] exp(-((u[n,i] - centers[g]) / denominator)^2) + base_weight[o,i] silu(x[n,i])
+ * with u = LayerNorm(x) (ln_weight / ln_bias given) or x, which the layer's forward only sums over i (base_bias is per output and
+ * no part of phi: y[n,o] = sum_i phi_{o,i}(n) + base_bias[o]).  Exact fp32 whatever precision the layer runs in (there is no
+ * `precision` argument), every num_grids kagnn_fastkan_fwd takes.  base_weight NULL: no base branch.  Nothing of size
+ * num_rows * out_features is ever stored: the workspaces hold row-slab partials, which are added in index order (no atomics: the
+ * same inputs give the same bits), and with a layernorm the row statistics [N, 2] and, in the backward, d / du [N, in].
+ * `layernorm` of the workspace queries: 1 when ln_weight will be given.
+ * ------------------------------------------------------------------------------------------ */
+/* abs_sum[o*ld_abs_sum + i] = sum_n |phi_{o,i}(n)|  -- a sum, not a mean: results over a partition of the rows add.  num_rows 0:
+ * zeros.                                                                                                                        */
+int kagnn_fastkan_edge_abs_sum_workspace_bytes(int64_t num_rows, int32_t in_features, int32_t out_features, int32_t num_grids,
+                                               int32_t layernorm, size_t* bytes_host);
+int kagnn_fastkan_edge_abs_sum(const float* x, int64_t ldx, int64_t num_rows, int32_t in_features, int32_t out_features,
+                               int32_t num_grids, const float* centers, float denominator, const float* ln_weight,
+                               const float* ln_bias, float ln_eps, const float* spline_weight, const float* base_weight,
+                               float* abs_sum, int64_t ld_abs_sum, void* workspace, size_t workspace_bytes, void* stream);
+/* its backward under the upstream gradient g_abs_sum[out, in], s = sign(phi_{o,i}(n)) with sign(0) = 0:
+ *   g_spline_weight[o, i*G+g] = g sum_n s rbf_g(u[n,i])       g_base_weight[o,i] = g sum_n s silu(x[n,i])
+ *   gx, g_ln_weight, g_ln_bias: sum_o g s dphi/du goes back through the layer's LayerNorm backward, sum_o g s base_weight silu'(x)
+ *   is added to gx directly.  g_spline_weight, g_base_weight and gx may be NULL (not wanted); with a layernorm gx and the two
+ *   layernorm gradients come from one pass: all three or none.                                                                 */
+int kagnn_fastkan_edge_abs_sum_bwd_workspace_bytes(int64_t num_rows, int32_t in_features, int32_t out_features, int32_t num_grids,
+                                                   int32_t layernorm, size_t* bytes_host);
+int kagnn_fastkan_edge_abs_sum_bwd(const float* x, int64_t ldx, int64_t num_rows, int32_t in_features, int32_t out_features,
+                                   int32_t num_grids, const float* centers, float denominator, const float* ln_weight,
+                                   const float* ln_bias, float ln_eps, const float* spline_weight, const float* base_weight,
+                                   const float* g_abs_sum, int64_t ld_g_abs_sum, float* g_spline_weight, float* g_base_weight,
+                                   float* gx, int64_t ldgx, float* g_ln_weight, float* g_ln_bias, void* workspace,
+                                   size_t workspace_bytes, void* stream);
+/* phi[p, o, i] (contiguous [num_points, out, in]): the spline branch at t[p] (ldt 0: one column shared by every feature) or
+ * t[p*ldt + i] -- the argument AFTER any layernorm --, the base branch at t_base likewise (t_base NULL: at t).  spline_weight NULL
+ * or base_weight NULL leaves that branch out (not both).                                                                        */
+int kagnn_fastkan_edge_curves(const float* t, int64_t ldt, const float* t_base, int64_t ldt_base, int64_t num_points,
+                              int32_t in_features, int32_t out_features, int32_t num_grids, const float* centers,
+                              float denominator, const float* spline_weight, const float* base_weight, float* phi, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Feature-sharded FastKAN layer (no counterpart in the reference, which is single-device: this is

@@ -142,6 +142,17 @@ _SIGNATURES = {
     "kagnn_fastkan_bwd": (c_int32, [_P, c_int64, _P, c_int64, c_int64, c_int32, c_int32, c_int32, _P,
                                     c_float, _P, _P, c_float, _P, _P, _P, _P, c_int64, _P, _P, _P, _P,
                                     _P, c_int32, _P, c_size_t, _P]),
+    "kagnn_fastkan_edge_abs_sum_workspace_bytes": (c_int32, [c_int64, c_int32, c_int32, c_int32, c_int32, POINTER(c_size_t)]),
+    # x ldx N in out ng centers den ln_w ln_b eps sw bw S ldS ws bytes stream
+    "kagnn_fastkan_edge_abs_sum": (c_int32, [_P, c_int64, c_int64, c_int32, c_int32, c_int32, _P, c_float, _P, _P, c_float, _P, _P,
+                                             _P, c_int64, _P, c_size_t, _P]),
+    "kagnn_fastkan_edge_abs_sum_bwd_workspace_bytes": (c_int32, [c_int64, c_int32, c_int32, c_int32, c_int32, POINTER(c_size_t)]),
+    # x ldx N in out ng centers den ln_w ln_b eps sw bw gS ldgS g_sw g_bw gx ldgx g_ln_w g_ln_b ws bytes stream
+    "kagnn_fastkan_edge_abs_sum_bwd": (c_int32, [_P, c_int64, c_int64, c_int32, c_int32, c_int32, _P, c_float, _P, _P, c_float, _P,
+                                                 _P, _P, c_int64, _P, _P, _P, c_int64, _P, _P, _P, c_size_t, _P]),
+    # t ldt t_base ldt_base P in out ng centers den sw bw phi stream
+    "kagnn_fastkan_edge_curves": (c_int32, [_P, c_int64, _P, c_int64, c_int64, c_int32, c_int32, c_int32, _P, c_float, _P, _P, _P,
+                                            _P]),
     "kagnn_fastkan_row_moments": (c_int32, [_P, c_int64, c_int64, c_int32, _P, _P]),
     "kagnn_fastkan_merge_moments": (c_int32, [_P, c_int32, c_int64, c_int32, c_float, _P, _P]),
     "kagnn_fastkan_shard_fwd": (c_int32, [_P, c_int64, c_int64, c_int32, c_int32, c_int32, _P, c_float, _P, _P,

@@ -84,7 +84,7 @@ using namespace kagnn;
 #pragma GCC visibility push(default)
 extern "C" {
 
-int kagnn_version(void) { return 269; }
+int kagnn_version(void) { return 270; }
 const char* kagnn_last_error(void) { return g_err; }
 
 int kagnn_stage_timer_enable(const char* only) {
@@ -655,6 +655,87 @@ int kagnn_fastkan_bwd(const float* x, int64_t ldx, const float* gy, int64_t ldgy
     return fastkan_bwd(x, ldx, gy, ldgy, N, in, out, ng, centers, denominator, ln_w, ln_b, ln_eps, spline_w,
                        base_w, row_stats, gx, ldgx, g_ln_w, g_ln_b, g_spline_w, g_base_w, g_base_b, ws,
                        ws_bytes, mode, as_stream(stream));
+}
+
+// ---------------------------------------------------------------- per-edge activations of a FastKANLayer (fastkan_edge.hip)
+// exact fp32 in every precision mode (no `mode` argument); every num_grids the layer takes; fixed-order slab reductions (no atomics)
+
+int kagnn_fastkan_edge_abs_sum_workspace_bytes(int64_t N, int32_t in, int32_t out, int32_t ng, int32_t layernorm, size_t* bytes) {
+    int rc = check_fk(__func__, in, out, ng, KAGNN_PREC_FP32);
+    if (rc) return rc;
+    KAGNN_CHECK_ARG(bytes != nullptr && N >= 0, "null output or negative row count");
+    *bytes = fastkan_edge_abs_sum_ws_bytes(N, in, out, layernorm != 0);
+    return KAGNN_OK;
+}
+
+int kagnn_fastkan_edge_abs_sum(const float* x, int64_t ldx, int64_t N, int32_t in, int32_t out, int32_t ng, const float* centers,
+                               float denominator, const float* ln_w, const float* ln_b, float ln_eps, const float* spline_w,
+                               const float* base_w, float* S, int64_t ldS, void* ws, size_t ws_bytes, void* stream) {
+    KAGNN_STAGE(stream);
+    int rc = check_fk(__func__, in, out, ng, KAGNN_PREC_FP32);
+    if (rc) return rc;
+    KAGNN_CHECK_ARG(N >= 0 && ldx >= in && ldS >= in, "bad shape");
+    KAGNN_CHECK_ARG(S != nullptr, "null array");
+    KAGNN_CHECK_ARG((ln_w == nullptr) == (ln_b == nullptr), "layernorm weight and bias must both be given or both be null");
+    if (N == 0) {                                   // an empty sum: zeros, no kernel
+        KAGNN_HIP(hipMemset2DAsync(S, (size_t)ldS * sizeof(float), 0, (size_t)in * sizeof(float), (size_t)out, as_stream(stream)));
+        return KAGNN_OK;
+    }
+    KAGNN_CHECK_ARG(x && centers && spline_w && ws, "null array");          // base_weight NULL: the layer has no base branch
+    KAGNN_CHECK_ARG(denominator != 0.0f, "denominator is zero");
+    return fastkan_edge_abs_sum(x, ldx, N, in, out, ng, centers, denominator, ln_w, ln_b, ln_eps, spline_w, base_w, S, ldS, ws,
+                                ws_bytes, as_stream(stream));
+}
+
+int kagnn_fastkan_edge_abs_sum_bwd_workspace_bytes(int64_t N, int32_t in, int32_t out, int32_t ng, int32_t layernorm, size_t* bytes) {
+    int rc = check_fk(__func__, in, out, ng, KAGNN_PREC_FP32);
+    if (rc) return rc;
+    KAGNN_CHECK_ARG(bytes != nullptr && N >= 0, "null output or negative row count");
+    *bytes = fastkan_edge_abs_sum_bwd_ws_bytes(N, in, out, ng, layernorm != 0);
+    return KAGNN_OK;
+}
+
+int kagnn_fastkan_edge_abs_sum_bwd(const float* x, int64_t ldx, int64_t N, int32_t in, int32_t out, int32_t ng, const float* centers,
+                                   float denominator, const float* ln_w, const float* ln_b, float ln_eps, const float* spline_w,
+                                   const float* base_w, const float* gS, int64_t ldgS, float* g_spline_w, float* g_base_w, float* gx,
+                                   int64_t ldgx, float* g_ln_w, float* g_ln_b, void* ws, size_t ws_bytes, void* stream) {
+    KAGNN_STAGE(stream);
+    int rc = check_fk(__func__, in, out, ng, KAGNN_PREC_FP32);
+    if (rc) return rc;
+    KAGNN_CHECK_ARG(N >= 0 && ldx >= in && ldgS >= in && (!gx || ldgx >= in), "bad shape");
+    KAGNN_CHECK_ARG((ln_w == nullptr) == (ln_b == nullptr), "layernorm weight and bias must both be given or both be null");
+    KAGNN_CHECK_ARG(!g_base_w || base_w, "a base_weight gradient needs base_weight");
+    KAGNN_CHECK_ARG((g_ln_w == nullptr) == (g_ln_b == nullptr) && (!g_ln_w || ln_w), "the layernorm gradients come as a pair and need layernorm");
+    if (N == 0) {                                   // empty sums: zeros, no kernel (gx has no rows)
+        const size_t e = (size_t)in * out * sizeof(float);
+        if (g_base_w) KAGNN_HIP(hipMemsetAsync(g_base_w, 0, e, as_stream(stream)));
+        if (g_spline_w) KAGNN_HIP(hipMemsetAsync(g_spline_w, 0, e * ng, as_stream(stream)));
+        if (g_ln_w) KAGNN_HIP(hipMemsetAsync(g_ln_w, 0, (size_t)in * sizeof(float), as_stream(stream)));
+        if (g_ln_b) KAGNN_HIP(hipMemsetAsync(g_ln_b, 0, (size_t)in * sizeof(float), as_stream(stream)));
+        return KAGNN_OK;
+    }
+    KAGNN_CHECK_ARG(x && centers && spline_w && gS, "null array");
+    KAGNN_CHECK_ARG(!ln_w || (gx == nullptr) == (g_ln_w == nullptr), "with layernorm, gx and the layernorm gradients come from one pass: all three or none");
+    KAGNN_CHECK_ARG(denominator != 0.0f, "denominator is zero");
+    KAGNN_CHECK_ARG(ws != nullptr, "the workspace is missing");
+    return fastkan_edge_abs_sum_bwd(x, ldx, N, in, out, ng, centers, denominator, ln_w, ln_b, ln_eps, spline_w, base_w, gS, ldgS,
+                                    g_spline_w, g_base_w, gx, ldgx, g_ln_w, g_ln_b, ws, ws_bytes, as_stream(stream));
+}
+
+int kagnn_fastkan_edge_curves(const float* t, int64_t ldt, const float* t_base, int64_t ldt_base, int64_t P, int32_t in, int32_t out,
+                              int32_t ng, const float* centers, float denominator, const float* spline_w, const float* base_w,
+                              float* phi, void* stream) {
+    KAGNN_STAGE(stream);
+    int rc = check_fk(__func__, in, out, ng, KAGNN_PREC_FP32);
+    if (rc) return rc;
+    KAGNN_CHECK_ARG(P >= 0 && (ldt == 0 || ldt >= in) && (ldt_base == 0 || ldt_base >= in), "bad shape");
+    KAGNN_CHECK_ARG(spline_w || base_w, "neither branch is given");
+    KAGNN_CHECK_ARG(phi != nullptr || P == 0, "null array");
+    if (P == 0) return KAGNN_OK;
+    KAGNN_CHECK_ARG(centers && (!spline_w || t) && (!base_w || t || t_base), "null array");
+    KAGNN_CHECK_ARG(denominator != 0.0f, "denominator is zero");
+    return fastkan_edge_curves(spline_w ? t : nullptr, ldt, base_w ? (t_base ? t_base : t) : nullptr, t_base ? ldt_base : ldt, P, in, out,
+                               ng, centers, denominator, spline_w, base_w, phi, as_stream(stream));
 }
 
 // ---------------------------------------------------------------- feature-sharded FastKAN layer

@@ -95,6 +95,13 @@ __device__ __forceinline__ float silu_gradf(float x) {
     return s * (1.0f + x * (1.0f - s));
 }
 
+// Gaussian RBF of the FastKAN layer, exp(-((z - c) / denominator)^2): the one form its layer kernels (fastkan.hip) and its edge
+// kernels (fastkan_edge.hip) evaluate, so that the layer's output is the sum of its edge functions to rounding
+__device__ __forceinline__ float rbf_val(float z, float c, float inv_den) {
+    const float d = (z - c) * inv_den;
+    return __expf(-d * d);
+}
+
 // ---------------------------------------------------------------- local uniform B-spline
 // For x in knot span m (knots[m] <= x < knots[m+1], the half-open test of ekan.py:95) the only
 // non-zero order-K bases are j = m-K .. m; N[r] = B_{m-K+r,K}(x), r = 0..K, via the Cox-de Boor

@@ -21,11 +21,6 @@ struct LnArgs {
     const float* row_sums = nullptr; float inv_total = 0.0f;
 };
 
-__device__ __forceinline__ float rbf_val(float z, float c, float inv_den) {
-    const float d = (z - c) * inv_den;
-    return __expf(-d * d);
-}
-
 // LayerNorm row statistics (mean, 1/sqrt(biased var + eps)), two-pass like torch; 16 lanes per row
 __global__ __launch_bounds__(256) void fastkan_stats_kernel(const float* __restrict__ x, long ldx, long N,
                                                             int in, float eps, float* __restrict__ stats) {
@@ -84,7 +79,7 @@ __global__ __launch_bounds__(256) void fastkan_stats_v4_kernel(const float* __re
     if (l == 0 && row < N) { stats[2 * row] = mean; stats[2 * row + 1] = rsqrtf(q / (float)in + eps); }
 }
 
-static int launch_stats(const float* x, long ldx, long N, int in, float eps, float* stats, hipStream_t st) {
+int launch_stats(const float* x, long ldx, long N, int in, float eps, float* stats, hipStream_t st) {
     const bool vec = (in & 3) == 0 && (ldx & 3) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
     const int grid = cdiv(N, 16);
 #define L(NV) do { if (vec) fastkan_stats_v4_kernel<NV, true><<<grid, 256, 0, st>>>(x, ldx, N, in, eps, stats); \
@@ -709,6 +704,24 @@ __global__ void fastkan_dw_unpack_kernel(const float* __restrict__ gcat, int in,
 // ------------------------------------------------------------------ host launchers
 static size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 
+// The LayerNorm backward as one call (also the edge kernels', fastkan_edge.hip):  gx += d loss / dx through the normalisation of
+// gz = d loss / d LayerNorm(x) [N, in] (contiguous),  g_lnw / g_lnb = its two parameter gradients.  `lnpart` holds one partial row
+// pair per workgroup (fastkan_ln_bwd_ws_bytes), added in a fixed order.
+static int fk_ln_blocks(long N) { return (int)max(1L, min(2048L, (N + 15) / 16)); }       // >= 4 rows per wave, up to 8192 waves
+
+size_t fastkan_ln_bwd_ws_bytes(long N, int in) { return al256((size_t)fk_ln_blocks(N) * 2 * in * 4); }
+
+int fastkan_ln_bwd(const float* x, long ldx, const float* gz, long N, int in, const float* lnw, const float* lnb, float eps,
+                   const float* stats, float* gx, long ldgx, float* g_lnw, float* g_lnb, float* lnpart, hipStream_t st) {
+    if (in > 64 * kLnMaxT) return fail(KAGNN_ERR_UNSUPPORTED, "%s: layernorm backward supports input_dim <= 4096", "fastkan_ln_bwd");
+    LnArgs ln{lnw, lnb, eps};
+    const int blocks = fk_ln_blocks(N);
+    { int rc = launch_ln_bwd(blocks, x, ldx, gz, N, in, ln, stats, gx, ldgx, lnpart, st); if (rc) return rc; }
+    sum_partials_kernel<<<cdiv(2L * in, 32), 32 * kSumGroups, 0, st>>>(lnpart, blocks, 2L * in, 2L * in, g_lnw, g_lnb, in);
+    KAGNN_LAUNCH_CHECK();
+    return KAGNN_OK;
+}
+
 // the forward takes the LayerNorm row statistics from the rows it loads (no statistics pass before it): the exact-fp32 kernel
 // always; the split kernels for one-chunk layers (<= 8 centres, in <= 64 with <= 64 outputs / in <= 32 with <= 128, one output block)
 bool fastkan_fwd_stats_in_kernel(long N, int in, int out, int ng, int mode) {
@@ -783,7 +796,7 @@ static FkBwdPlan fk_plan(long N, int in, int out, int ng, int mode) {
         p.gcat = al256((size_t)p.per * 4);
         p.slab = al256((size_t)p.NS * p.per * 4);
     }
-    p.ln_blocks = (int)max(1L, min(2048L, (N + 15) / 16));       // >= 4 rows per wave, up to 8192 waves
+    p.ln_blocks = fk_ln_blocks(N);
     p.lnpart = al256((size_t)p.ln_blocks * 2 * in * 4);
     p.col_blocks = (int)max(1L, min(512L, N / 256 + 1));
     p.col_rpb = (N + p.col_blocks - 1) / p.col_blocks;
@@ -844,10 +857,8 @@ int fastkan_bwd(const float* x, long ldx, const float* gy, long ldgy, long N, in
         if (lnw && shard) {
             if (N > 0 && do_dx) { fastkan_ln_row_sums_kernel<<<cdiv(N, 16), 256, 0, st>>>(x, ldx, gz, N, in, lnw, stats, row_sums); KAGNN_LAUNCH_CHECK(); }
         } else if (lnw) {
-            LnArgs ln{lnw, lnb, eps};
-            { int rc = launch_ln_bwd(p.ln_blocks, x, ldx, gz, N, in, ln, stats, gx, ldgx, lnpart, st); if (rc) return rc; }
-            sum_partials_kernel<<<cdiv(2L * in, 32), 32 * kSumGroups, 0, st>>>(lnpart, p.ln_blocks, 2L * in, 2L * in, g_lnw, g_lnb, in);
-            KAGNN_LAUNCH_CHECK();
+            int rc = fastkan_ln_bwd(x, ldx, gz, N, in, lnw, lnb, eps, stats, gx, ldgx, g_lnw, g_lnb, lnpart, st);
+            if (rc) return rc;
         }
         if (!do_dw) return KAGNN_OK;
         // the base bias gradient (column sums of gy) rides in the weight-gradient kernel, which reads gy anyway: one row of
@@ -886,9 +897,8 @@ int fastkan_bwd(const float* x, long ldx, const float* gy, long ldgy, long N, in
     if (lnw && shard) {
         if (N > 0 && do_dx) { fastkan_ln_row_sums_kernel<<<cdiv(N, 16), 256, 0, st>>>(x, ldx, gz, N, in, lnw, stats, row_sums); KAGNN_LAUNCH_CHECK(); }
     } else if (lnw) {
-        { int rc = launch_ln_bwd(p.ln_blocks, x, ldx, gz, N, in, ln, stats, gx, ldgx, lnpart, st); if (rc) return rc; }
-        sum_partials_kernel<<<cdiv(2L * in, 32), 32 * kSumGroups, 0, st>>>(lnpart, p.ln_blocks, 2L * in, 2L * in, g_lnw, g_lnb, in);
-        KAGNN_LAUNCH_CHECK();
+        int rc = fastkan_ln_bwd(x, ldx, gz, N, in, lnw, lnb, eps, stats, gx, ldgx, g_lnw, g_lnb, lnpart, st);
+        if (rc) return rc;
     }
     if (!do_dw) return KAGNN_OK;
     dim3 grid(p.nb, FT * OTt);

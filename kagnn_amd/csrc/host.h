@@ -173,6 +173,26 @@ int fastkan_bwd(const float* x, long ldx, const float* gy, long ldgy, long N, in
                 long ldgx, float* g_lnw, float* g_lnb, float* g_sw, float* g_bw, float* g_bb, void* ws, size_t ws_bytes, int mode,
                 hipStream_t st, int phase = 0, float* row_sums = nullptr, int in_total = 0);
 
+// the LayerNorm pieces of the layer that its edge kernels (fastkan_edge.hip) run as they are: row statistics (mean, rstd) [N, 2],
+// and the backward through the normalisation (gx += ..., both parameter gradients; lnpart: fastkan_ln_bwd_ws_bytes)
+int launch_stats(const float* x, long ldx, long N, int in, float eps, float* stats, hipStream_t st);
+size_t fastkan_ln_bwd_ws_bytes(long N, int in);
+int fastkan_ln_bwd(const float* x, long ldx, const float* gz, long N, int in, const float* lnw, const float* lnb, float eps,
+                   const float* stats, float* gx, long ldgx, float* g_lnw, float* g_lnb, float* lnpart, hipStream_t st);
+
+// ---- fastkan_edge.hip (per-edge activations of a FastKANLayer: abs sum over the rows, its backward, sampled curves; exact fp32)
+size_t fastkan_edge_abs_sum_ws_bytes(long N, int in, int out, bool layernorm);
+size_t fastkan_edge_abs_sum_bwd_ws_bytes(long N, int in, int out, int ng, bool layernorm);
+int fastkan_edge_abs_sum(const float* x, long ldx, long N, int in, int out, int ng, const float* centers, float den, const float* lnw,
+                         const float* lnb, float eps, const float* sw, const float* bw, float* S, long ldS, void* ws, size_t ws_bytes,
+                         hipStream_t st);
+int fastkan_edge_abs_sum_bwd(const float* x, long ldx, long N, int in, int out, int ng, const float* centers, float den, const float*
+                             lnw, const float* lnb, float eps, const float* sw, const float* bw, const float* gS, long ldgS, float*
+                             g_sw, float* g_bw, float* gx, long ldgx, float* g_lnw, float* g_lnb, void* ws, size_t ws_bytes,
+                             hipStream_t st);
+int fastkan_edge_curves(const float* t, long ldt, const float* tb, long ldtb, long P, int in, int out, int ng, const float* centers,
+                        float den, const float* sw, const float* bw, float* phi, hipStream_t st);
+
 // ---- gat.hip
 int gat_logits(const float* xh, long ld, long N, int H, int C, const float* att_src, const float* att_dst, float* a_s, float* a_d,
                hipStream_t st);

@@ -21,14 +21,12 @@
 // scaler's gradient  g_sc = gS sum_c w_c T_c.
 //
 // No atomics anywhere: the same inputs give the same bits.
-#include "common.h"
+#include "edge_common.h"
 #include "host.h"
 
 namespace kagnn {
 
-constexpr int kEdgeThreads = 256;      // four waves
-constexpr int kEdgeFT = 4;             // features per workgroup (one per wave)
-constexpr int kEdgeOB = 64;            // outputs per tile
+// (workgroup shape, edge_sign, edge_plan and the declarations of the two slab reductions: edge_common.h, shared with fastkan_edge.hip)
 constexpr int kEdgeMaxNQ = 12;         // widest parameter-gradient kernel: NQ * 4 = 48 dense columns
 // check_kan_dims: G + 2K + 1 <= kMaxKnots, so C = G + K <= kMaxKnots - 1 - K, largest at K = 1
 static_assert(kEdgeMaxNQ * 4 >= (kMaxKnots - 2) + 1, "the widest parameter kernel must hold C + 1 columns at the knot limit");
@@ -64,9 +62,6 @@ __device__ __forceinline__ int edge_basis(float x, const float* kn /* LDS: this 
     }
     return m;
 }
-
-// torch's sgn for the backward of abs: 0 at 0, NaN stays NaN
-__device__ __forceinline__ float edge_sign(float v) { return v > 0.0f ? 1.0f : (v < 0.0f ? -1.0f : v); }
 
 template <int K, bool PF, int MODE>
 __global__ __launch_bounds__(kEdgeThreads) void kan_edge_rows_kernel(EdgeArgs a) {
@@ -306,13 +301,17 @@ __global__ void kan_edge_param_reduce_kernel(const float* __restrict__ partial, 
     if (g_sc) g_sc[e] = g * dot;
 }
 
-// about `want_blocks` workgroups in all, a slab a multiple of 64 rows and never shorter than 256
-static void edge_plan(long N, long tiles, long want_blocks, long* slabs, long* rows_per_slab) {
-    const long want = max(1L, want_blocks / max(1L, tiles));
-    long r = (N + want - 1) / want;
-    r = max(256L, (r + 63) / 64 * 64);
-    *rows_per_slab = r;
-    *slabs = max(1L, (N + r - 1) / r);
+int edge_sum_reduce(const float* partial, long slabs, int in, int out, float* dst, long ld, hipStream_t st) {
+    kan_edge_sum_reduce_kernel<<<cdiv((long)out * in, 256), 256, 0, st>>>(partial, slabs, in, out, dst, ld);
+    KAGNN_LAUNCH_CHECK();
+    return KAGNN_OK;
+}
+
+int edge_param_reduce(const float* partial, long slabs, int in, int out, int C, const float* gS, long ldgS, const float* sw,
+                      const float* sc, float* g_bw, float* g_sw, float* g_sc, hipStream_t st) {
+    kan_edge_param_reduce_kernel<<<cdiv((long)out * in, 256), 256, 0, st>>>(partial, slabs, in, out, C, gS, ldgS, sw, sc, g_bw, g_sw, g_sc);
+    KAGNN_LAUNCH_CHECK();
+    return KAGNN_OK;
 }
 
 static size_t edge_rows_lds_bytes(int nknots, int C, int K, bool pf) {
@@ -353,10 +352,6 @@ static int edge_launch_param(const EdgeArgs& a, int K, bool pf, dim3 grid, hipSt
     return KAGNN_OK;
 }
 
-static bool edge_grid_ok(long gx, long gy, long gz) { return gx <= 0x7fffffffL && gy <= 65535 && gz <= 65535; }
-
-static long edge_tiles(int in, int out) { return (long)cdiv(in, kEdgeFT) * cdiv(out, kEdgeOB); }
-
 size_t kan_edge_abs_sum_ws_bytes(long N, int in, int out) {
     long S, r;
     edge_plan(N, edge_tiles(in, out), 2048, &S, &r);
@@ -380,9 +375,7 @@ int kan_edge_abs_sum(const float* x, long ldx, long N, const float* knots, bool 
     if (!edge_grid_ok(S, cdiv(in, kEdgeFT), cdiv(out, kEdgeOB))) return fail(KAGNN_ERR_UNSUPPORTED, "%s: shape too large for one launch", "kan_edge_abs_sum");
     int rc = edge_launch_rows<EDGE_SUM>(a, K, pf, dim3((unsigned)S, cdiv(in, kEdgeFT), cdiv(out, kEdgeOB)), st);
     if (rc) return rc;
-    kan_edge_sum_reduce_kernel<<<cdiv((long)out * in, 256), 256, 0, st>>>(ws, S, in, out, S_, ldS);
-    KAGNN_LAUNCH_CHECK();
-    return KAGNN_OK;
+    return edge_sum_reduce(ws, S, in, out, S_, ldS, st);
 }
 
 int kan_edge_abs_sum_bwd(const float* x, long ldx, long N, const float* knots, bool pf, int in, int out, int G, int K,
@@ -406,8 +399,8 @@ int kan_edge_abs_sum_bwd(const float* x, long ldx, long N, const float* knots, b
         int rc = NQ == 3 ? edge_launch_param<3>(a, K, pf, grid, st) : NQ == 5 ? edge_launch_param<5>(a, K, pf, grid, st)
                : NQ == 10 ? edge_launch_param<10>(a, K, pf, grid, st) : edge_launch_param<kEdgeMaxNQ>(a, K, pf, grid, st);
         if (rc) return rc;
-        kan_edge_param_reduce_kernel<<<cdiv((long)out * in, 256), 256, 0, st>>>(ws, S, in, out, C, gS, ldgS, sw, sc, g_bw, g_sw, g_sc);
-        KAGNN_LAUNCH_CHECK();
+        rc = edge_param_reduce(ws, S, in, out, C, gS, ldgS, sw, sc, g_bw, g_sw, g_sc, st);
+        if (rc) return rc;
     }
     if (gx) {
         long S, r;

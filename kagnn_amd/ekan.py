@@ -320,16 +320,18 @@ def _collect(layer: KANLinear, x: torch.Tensor) -> None:
 @contextlib.contextmanager
 def collect_edge_l1(model: nn.Module):
     """``with collect_edge_l1(model) as stats: out = model(...)`` fills ``stats`` with ``{qualified module name: edge_l1 [out, in]}``
-    for every ``KANLinear`` of spline order <= 4 under ``model``, taken on the input each layer sees during the forwards inside
+    for every ``KANLinear`` of spline order <= 4 and every ``FastKANLayer`` under ``model``, taken on the input each layer sees during the forwards inside
     the block (a layer called again overwrites its entry).  The statistics are differentiable: add a regulariser built from them
     to the loss.  While a block is active the fused layer / stack / model routes, which never expose a layer's input, take their
     composed per-layer form (``ops.layer_inputs_visible``); outside it nothing changes.
 
-    EVERY ``KANLinear.forward`` inside the block records -- also under ``torch.no_grad()`` or in eval mode -- and the latest call
+    EVERY ``KANLinear.forward`` / ``FastKANLayer.forward`` inside the block records -- also under ``torch.no_grad()`` or in eval mode -- and the latest call
     wins, so run inside the block only the forward whose statistics are wanted.  The chain walks of ``KAN.edge_l1`` and
     ``KAN.regularization_loss(x=)`` do not record.  The block belongs to the thread that opened it: forwards on other threads
     (data-parallel replicas, a loader thread) keep their fused routes and are not recorded."""
-    names = {id(m): n for n, m in model.named_modules() if isinstance(m, KANLinear) and not ops.high_order(m.spline_order)}
+    from .fastkan import FastKANLayer             # (FastKAN chains run composed as they are: FastKANLayer.forward records)
+    names = {id(m): n for n, m in model.named_modules()
+             if (isinstance(m, KANLinear) and not ops.high_order(m.spline_order)) or isinstance(m, FastKANLayer)}
     entry = (names, {})
     active = ops._edge_collectors()
     active.append(entry)

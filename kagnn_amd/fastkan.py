@@ -5,8 +5,9 @@ Drop-in for ``node_classification_clean/fastkan.py`` of the reference (``SplineL
 signatures and the same state_dict keys (``layernorm.weight, layernorm.bias, rbf.grid,
 spline_linear.weight, base_linear.weight, base_linear.bias``).  ``FastKANLayer.forward`` is one
 call to ``kagnn_fastkan_fwd`` -- LayerNorm statistics, the Gaussian RBF expansion and both linear
-maps are fused in the kernel; ``plot_curve`` and the attention helper of the reference are not
-part of the KAGNN path and are not provided.
+maps are fused in the kernel.  ``plot_curve`` (:87-115) is one column of ``edge_curves``; on the same kernels
+(``csrc/fastkan_edge.hip``) sit ``edge_l1`` and the KAN regulariser ``regularization_loss(x)``, which the reference has for
+efficient-KAN layers only.  The attention helper of the reference is not part of the KAGNN path and is not provided.
 
 Attribution: the module surface restated here (class names, constructor signatures, parameter layout and the
 trunc-normal / linspace initialisation of ``SplineLinear`` / ``RadialBasisFunction`` / ``FastKANLayer`` / ``FastKAN``)
@@ -72,6 +73,13 @@ class FastKANLayer(nn.Module):
             self.base_linear = nn.Linear(input_dim, output_dim)
 
     def forward(self, x, use_layernorm=True):
+        if ops.layer_inputs_visible():
+            _collect(self, x, use_layernorm)
+        return self._forward(x, use_layernorm)
+
+    def _forward(self, x, use_layernorm=True):
+        """the layer itself, without the statistics of a ``collect_edge_l1`` block (the chain walks of ``FastKAN.edge_l1`` /
+        ``FastKAN.regularization_loss`` are not the model's forward)"""
         lead = x.shape[:-1]
         x2 = x.reshape(-1, x.shape[-1])
         ln = self.layernorm if (self.layernorm is not None and use_layernorm) else None
@@ -83,6 +91,56 @@ class FastKANLayer(nn.Module):
             self.base_linear.bias if self.use_base_update else None,
             self.rbf.grid, self.rbf.denominator, 1e-5 if ln is None else ln.eps, self.precision)
         return y.reshape(*lead, self.output_dim)
+
+    # ------------------------------------------------------------------ the edge functions phi_{o,i}
+    #   phi_{o,i}(n) = sum_g spline_linear.weight[o, i*G+g] rbf_g(u[n,i]) + base_linear.weight[o,i] silu(x[n,i]),  u = layernorm(x) or x;
+    #   forward(x)[n,o] = sum_i phi_{o,i}(n) + base_linear.bias[o]
+    def _edge_weights(self):
+        return self.spline_linear.weight, (self.base_linear.weight if self.use_base_update else None)
+
+    def edge_l1(self, x: torch.Tensor, use_layernorm: bool = True) -> torch.Tensor:
+        """``[out, in]``: the mean magnitude ``mean_n |phi_{o,i}(n)|`` of every edge's activation over the rows of ``x`` -- what the
+        KAN paper's regulariser is defined on, and what tells which inputs / edges a trained layer uses.  One fused kernel
+        (``ops.fastkan_edge_abs_sum``): no [N, out, in] tensor.  Differentiable."""
+        x2 = x.reshape(-1, x.shape[-1])
+        assert x2.size(1) == self.input_dim
+        ln = self.layernorm if (self.layernorm is not None and use_layernorm) else None
+        sw, bw = self._edge_weights()
+        S = ops.fastkan_edge_abs_sum(x2, None if ln is None else ln.weight, None if ln is None else ln.bias, sw, bw,
+                                     self.rbf.grid, self.rbf.denominator, 1e-5 if ln is None else ln.eps)
+        return S / max(x2.size(0), 1)
+
+    @torch.no_grad()
+    def edge_curves(self, points: torch.Tensor, base_points: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``[P, out, in]``: every edge function sampled at ``points`` (``[P]``, shared by all inputs, or ``[P, in]``): the RBFs'
+        argument, i.e. the value after the layernorm.  ``base_points``: other abscissae for the base branch, which sees the
+        row before the layernorm (``None``: ``points``)."""
+        sw, bw = self._edge_weights()
+        return ops.fastkan_edge_curves(points, sw, bw, self.rbf.grid, self.rbf.denominator, base_points)
+
+    @torch.no_grad()
+    def plot_curve(self, input_index: int, output_index: int, num_pts: int = 1000, num_extrapolate_bins: int = 2):
+        """The reference's ``plot_curve`` (fastkan.py:87-115): ``(x, y)`` with ``x = linspace(grid_min - N_e h, grid_max + N_e h,
+        num_pts)`` and ``y`` the spline branch of edge ``(output_index, input_index)`` there -- that column of ``edge_curves``
+        without the base branch, evaluated for this one edge.  Both on the layer's device."""
+        ng, h = self.rbf.num_grids, self.rbf.denominator
+        assert input_index < self.input_dim
+        assert output_index < self.output_dim
+        w = self.spline_linear.weight[output_index:output_index + 1, input_index * ng:(input_index + 1) * ng]
+        x = torch.linspace(self.rbf.grid_min - num_extrapolate_bins * h, self.rbf.grid_max + num_extrapolate_bins * h, num_pts,
+                           dtype=w.dtype, device=w.device)
+        y = ops.fastkan_edge_curves(x, w, None, self.rbf.grid, h)
+        return x, y.reshape(-1)
+
+    def regularization_loss(self, x: torch.Tensor, regularize_activation=1.0, regularize_entropy=1.0):
+        """The KAN paper's L1 + entropy regulariser on the edge activations of the layer's input ``x``: the formula of
+        ``KANLinear.regularization_loss(x=)`` with ``mag = edge_l1(x)``.  (``x`` is required: the reference has no weight
+        stand-in for FastKAN.)  Like that formula, an all-zero ``mag`` (zero weights, no rows) gives 0 / 0 = NaN for the loss and
+        its gradients."""
+        mag = self.edge_l1(x)
+        total = mag.sum()
+        share = mag / total
+        return regularize_activation * total - regularize_entropy * torch.sum(share * share.log())
 
 
 class FastKAN(nn.Module):
@@ -100,3 +158,29 @@ class FastKAN(nn.Module):
         for layer in self.layers:
             x = layer(x)
         return x
+
+    def regularization_loss(self, x: torch.Tensor, regularize_activation=1.0, regularize_entropy=1.0):
+        """``x``: the chain's input -- every layer is regularised on the activations of ITS input (the chain is walked)"""
+        total = 0.0
+        for i, layer in enumerate(self.layers):
+            total = total + layer.regularization_loss(x, regularize_activation, regularize_entropy)
+            if i + 1 < len(self.layers):
+                x = layer._forward(x)             # (not a forward of the model: a collect_edge_l1 block does not record it)
+        return total
+
+    def edge_l1(self, x: torch.Tensor) -> List[torch.Tensor]:
+        """``FastKANLayer.edge_l1`` of every layer on its own input, ``x`` being the chain's"""
+        out = []
+        for i, layer in enumerate(self.layers):
+            out.append(layer.edge_l1(x))
+            if i + 1 < len(self.layers):
+                x = layer._forward(x)
+        return out
+
+
+def _collect(layer: FastKANLayer, x: torch.Tensor, use_layernorm: bool) -> None:
+    """inside ``kagnn_amd.collect_edge_l1`` blocks of this thread: ``edge_l1`` of the input ``forward`` sees, with its ``use_layernorm``"""
+    for names, stats in ops._edge_collectors():
+        name = names.get(id(layer))
+        if name is not None:
+            stats[name] = layer.edge_l1(x if x.dtype == torch.float32 else x.float(), use_layernorm)

@@ -1922,6 +1922,126 @@ class _FastKANFn(Function):
         return gx, glw, glb, gsw, gbw, (gbb if has_bb else None), None, None, None, None
 
 
+# ------------------------------------------------------------------------ per-edge activations of a FastKAN layer (fastkan_edge.hip)
+# phi_{o,i}(n) = sum_g spline_weight[o, i*G+g] exp(-((u[n,i] - c_g) / h)^2) + base_weight[o,i] silu(x[n,i]),  u = LayerNorm(x) or x:
+# the FastKAN twin of kan_edge_abs_sum / kan_edge_curves above.  Exact fp32 in every precision mode.
+def _fastkan_edge_operands(ln_weight, ln_bias, spline_weight, base_weight, centers, *rows):
+    _need_cuda(*rows, ln_weight, ln_bias, spline_weight, base_weight, centers)
+    if (ln_weight is None) != (ln_bias is None):
+        raise AssertionError("layernorm weight and bias must both be given or both be None")
+    c = centers.detach().to(torch.float32).contiguous()
+    ng = c.numel()
+    ts = [None if t is None else t.detach().contiguous() for t in (ln_weight, ln_bias, spline_weight, base_weight)]
+    for t in ts:
+        if t is not None and t.dtype != torch.float32:
+            raise TypeError(f"kagnn_amd kernels are fp32; got {t.dtype}")
+    lw, lb, sw, bw = ts
+    if sw is not None and (sw.dim() != 2 or sw.size(1) % max(ng, 1)):
+        raise AssertionError("spline_linear.weight must be [out, in*num_grids]")
+    if sw is None and bw is None:
+        raise AssertionError("neither spline_weight nor base_weight is given")
+    fout, fin = (bw.size(0), bw.size(1)) if bw is not None else (sw.size(0), sw.size(1) // ng)
+    if (sw is not None and sw.shape != (fout, fin * ng)) or (lw is not None and (lw.shape != (fin,) or lb.shape != (fin,))):
+        raise AssertionError("spline_weight must be [out, in*num_grids], base_weight [out, in], layernorm weight and bias [in]")
+    return lw, lb, sw, bw, c, ng, fin, fout
+
+
+def _fastkan_edge_abs_sum_raw(x, lw, lb, sw, bw, c, ng, fin, fout, denominator, ln_eps, out=None):
+    n = x.size(0)
+    S = torch.empty((fout, fin), dtype=torch.float32, device=x.device) if out is None else out
+    ws = _ws(_sizes("kagnn_fastkan_edge_abs_sum_workspace_bytes", n, fin, fout, ng, int(lw is not None)), x.device)
+    _call("kagnn_fastkan_edge_abs_sum", _ptr(x), _ld(x), n, fin, fout, ng, _ptr(c), float(denominator), _ptr(lw), _ptr(lb),
+          float(ln_eps), _ptr(sw), _ptr(bw), _ptr(S), _ld(S) if out is not None else fin, _ptr(ws), ws.numel(), _stream())
+    return S
+
+
+def _fastkan_edge_abs_sum_bwd_raw(x, lw, lb, sw, bw, c, ng, fin, fout, denominator, ln_eps, gS, want_sw, want_bw, want_x):
+    """-> (g_spline_weight, g_base_weight, gx, g_ln_weight, g_ln_bias); with a layernorm the last three come together"""
+    n, dev = x.size(0), x.device
+    f32 = dict(dtype=torch.float32, device=dev)
+    gsw = torch.empty((fout, fin * ng), **f32) if want_sw else None
+    gbw = torch.empty((fout, fin), **f32) if want_bw and bw is not None else None
+    gx = torch.empty((n, fin), **f32) if want_x else None
+    glw = torch.empty(fin, **f32) if want_x and lw is not None else None
+    glb = torch.empty(fin, **f32) if want_x and lw is not None else None
+    ws = _ws(_sizes("kagnn_fastkan_edge_abs_sum_bwd_workspace_bytes", n, fin, fout, ng, int(lw is not None)), dev)
+    _call("kagnn_fastkan_edge_abs_sum_bwd", _ptr(x), _ld(x), n, fin, fout, ng, _ptr(c), float(denominator), _ptr(lw), _ptr(lb),
+          float(ln_eps), _ptr(sw), _ptr(bw), _ptr(gS), _ld(gS), _ptr(gsw), _ptr(gbw), _ptr(gx), fin, _ptr(glw), _ptr(glb), _ptr(ws),
+          ws.numel(), _stream())
+    return gsw, gbw, gx, glw, glb
+
+
+class _FastKANEdgeAbsSumFn(Function):
+    """``S[o,i] = sum_n |phi_{o,i}(n)|``.  Saves the rows and the parameters, not phi: the backward evaluates it again."""
+
+    @staticmethod
+    @_on_operand_device
+    def forward(ctx, x, ln_weight, ln_bias, spline_weight, base_weight, centers, denominator, ln_eps):
+        if spline_weight is None:
+            raise AssertionError("fastkan_edge_abs_sum needs spline_weight")
+        lw, lb, sw, bw, c, ng, fin, fout = _fastkan_edge_operands(ln_weight, ln_bias, spline_weight, base_weight, centers, x)
+        x = _rows(x.detach())
+        if x.size(1) != fin:
+            raise AssertionError("x must be [rows, input_dim]")
+        ctx.save_for_backward(x, lw, lb, sw, bw, c)
+        ctx.dims = (ng, fin, fout, float(denominator), float(ln_eps))
+        return _fastkan_edge_abs_sum_raw(x, lw, lb, sw, bw, c, ng, fin, fout, denominator, ln_eps)
+
+    @staticmethod
+    @once_differentiable
+    @_on_operand_device
+    def backward(ctx, gS):
+        x, lw, lb, sw, bw, c = ctx.saved_tensors
+        ng, fin, fout, den, eps = ctx.dims
+        need = ctx.needs_input_grad
+        want_x = need[0] or (lw is not None and (need[1] or need[2]))
+        gsw, gbw, gx, glw, glb = _fastkan_edge_abs_sum_bwd_raw(x, lw, lb, sw, bw, c, ng, fin, fout, den, eps, _rows(gS), need[3], need[4],
+                                                               want_x)
+        return (gx if need[0] else None), (glw if need[1] else None), (glb if need[2] else None), gsw, gbw, None, None, None
+
+
+def fastkan_edge_abs_sum(x, ln_weight, ln_bias, spline_weight, base_weight, centers, denominator: float,
+                         ln_eps: float = 1e-5) -> torch.Tensor:
+    """``S[out, in] = sum_n |phi_{o,i}(n)|`` of a FastKAN layer -- the per-edge activation magnitude the KAN regulariser is defined
+    on, as a SUM over the rows (sums over a partition of the rows add; ``FastKANLayer.edge_l1`` divides by the row count).
+    ``ln_weight`` / ``ln_bias`` ``None``: no LayerNorm in front of the RBFs; ``base_weight`` ``None``: no base branch.
+    Differentiable in ``x``, both LayerNorm parameters and both weights; nothing of size [N, out, in] (or [N, out]) is stored."""
+    return _FastKANEdgeAbsSumFn.apply(x, ln_weight, ln_bias, spline_weight, base_weight, centers, float(denominator), float(ln_eps))
+
+
+def _edge_points(t, fin, what):
+    """-> (points with unit column stride, ld or 0 for one shared column)"""
+    if t.dtype != torch.float32:
+        raise TypeError(f"kagnn_amd kernels are fp32; got {t.dtype}")
+    t = t.detach()
+    if t.dim() == 1:
+        return t.contiguous(), 0
+    if t.dim() == 2 and t.size(1) == fin:
+        t = _rows(t)
+        return t, _ld(t)
+    raise AssertionError(f"{what} must be [P] or [P, input_dim]")
+
+
+def fastkan_edge_curves(points, spline_weight, base_weight, centers, denominator: float, base_points=None) -> torch.Tensor:
+    """``phi[P, out, in]``: every edge function of a FastKAN layer sampled at ``points`` -- ``[P]`` (the same abscissae for every
+    input feature) or ``[P, in]``; they are the RBFs' argument, i.e. the value AFTER any LayerNorm.  ``base_points`` (same shape):
+    other abscissae for the base branch, which in a LayerNorm layer sees the row before the normalisation; ``None``: ``points``.
+    ``spline_weight`` or ``base_weight`` ``None`` leaves that branch out (``points`` may then be ``None`` too).  Not differentiable."""
+    lw, lb, sw, bw, c, ng, fin, fout = _fastkan_edge_operands(None, None, spline_weight, base_weight, centers, points, base_points)
+    if points is None and (sw is not None or base_points is None):
+        raise AssertionError("points may be None only for the base branch alone, sampled at base_points")
+    t, ldt = (None, 0) if points is None else _edge_points(points, fin, "points")
+    tb, ldtb = (None, 0) if base_points is None else _edge_points(base_points, fin, "base_points")
+    first = t if t is not None else tb
+    if t is not None and tb is not None and tb.shape != t.shape:
+        raise AssertionError("base_points must have the shape of points")
+    out = torch.empty((first.size(0), fout, fin), dtype=torch.float32, device=first.device)
+    with _device_of(first):
+        _call("kagnn_fastkan_edge_curves", _ptr(t), ldt, _ptr(tb), ldtb, first.size(0), fin, fout, ng, _ptr(c), float(denominator),
+              _ptr(sw), _ptr(bw), _ptr(out), _stream())
+    return out
+
+
 # ------------------------------------------------------------------------ feature-sharded FastKAN layer (SURVEY.md 8(e))
 # The local-compute half of kagnn_amd.sharded.ShardedFastKANLayer: a rank holds `w` of the row's P*w input columns.  LayerNorm
 # (fastkan.py:77-78) is the only reduction over the sharded axis -- 2 floats per row each way; the collectives themselves are the

@@ -5,6 +5,10 @@ before: `ops.kan_bsplines` + `einsum` on the device, in row chunks small enough 
 autograd through that composition would keep every chunk's intermediate alive).
 
     python tools/edge_activation_step.py [--rows 1048576] [--width 64] [--grid 5] [--order 3] [--chunk 16384] [--json out.json]
+    python tools/edge_activation_step.py --fastkan [--rows 1048576] [--width 64] [--num-grids 8] [--json out.json]
+
+`--fastkan`: the FastKAN twin (csrc/fastkan_edge.hip) on a `FastKANLayer(width, width, num_grids)` with its LayerNorm and base branch:
+`edge_l1` and its backward (all five gradients) beside the same layer's own forward and backward, same rows, same process.
 
 Timing: device events around a window of back-to-back calls, each window at least `--window` seconds (0.2) long, five windows per
 variant, the variants ALTERNATING window by window in one process; reported per variant: median and range (min .. max) of the
@@ -58,8 +62,55 @@ def window(fn, min_seconds):
         calls = max(calls + 1, int(calls * 1.2e3 * min_seconds / max(ms, 1e-3)))
 
 
+def main_fastkan(args):
+    dev = "cuda:0"
+    torch.manual_seed(0)
+    layer = kagnn_amd.FastKANLayer(args.width, args.width, num_grids=args.num_grids).to(dev)
+    with torch.no_grad():
+        layer.spline_linear.weight.normal_(0, 0.3); layer.base_linear.weight.normal_(0, 0.3)
+        layer.layernorm.weight.normal_(1, 0.3); layer.layernorm.bias.normal_(0, 0.2)
+    x = (0.8 * torch.randn(args.rows, args.width, device=dev)).requires_grad_(True)
+    gS = torch.randn(args.width, args.width, device=dev)
+    gy = torch.randn(args.rows, args.width, device=dev)
+
+    def layer_step():
+        layer(x).backward(gy)
+
+    def edge_step():
+        layer.edge_l1(x).backward(gS)
+
+    def edge_forward():
+        with torch.no_grad():
+            layer.edge_l1(x)
+
+    def layer_forward():
+        with torch.no_grad():
+            layer(x)
+
+    variants = {"layer_forward": layer_forward, "layer_forward_backward": layer_step, "edge_l1_forward": edge_forward,
+                "edge_l1_forward_backward": edge_step}
+    for fn in variants.values():
+        fn(); fn()
+    torch.cuda.synchronize()
+    times = {k: [] for k in variants}
+    for _ in range(args.windows):
+        for name, fn in variants.items():
+            times[name].append(window(fn, args.window))
+    out = {"device": torch.cuda.get_device_name(0), "library_version": kagnn_amd._lib.load().kagnn_version(), "layer": "FastKANLayer",
+           "rows": args.rows, "width": args.width, "num_grids": args.num_grids, "window_s": args.window, "windows": args.windows,
+           "ms": {name: {"median": statistics.median(t), "min": min(t), "max": max(t)} for name, t in times.items()}}
+    out["edge_over_layer_forward_backward"] = out["ms"]["edge_l1_forward_backward"]["median"] / out["ms"]["layer_forward_backward"]["median"]
+    print(json.dumps(out))
+    if args.json:
+        os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
+        with open(args.json, "w") as f:
+            json.dump(out, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--fastkan", action="store_true")
+    ap.add_argument("--num-grids", type=int, default=8)
     ap.add_argument("--rows", type=int, default=1 << 20)
     ap.add_argument("--width", type=int, default=64)
     ap.add_argument("--grid", type=int, default=5)
@@ -71,6 +122,8 @@ def main():
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("edge_activation_step.py measures on the GPU: no device found")
+    if args.fastkan:
+        return main_fastkan(args)
     dev = "cuda:0"
     torch.manual_seed(0)
     layer = kagnn_amd.KANLinear(args.width, args.width, grid_size=args.grid, spline_order=args.order).to(dev)
