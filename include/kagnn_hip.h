@@ -649,6 +649,8 @@ int kagnn_fastkan_edge_curves(const float* t, int64_t ldt, const float* t_base, 
  *             the caller sums row_sums over the ranks (all-reduce);  kagnn_fastkan_shard_bwd_finish completes gx and writes
  *             g_ln_weight / g_ln_bias -- SAME shape arguments and SAME workspace (kagnn_fastkan_bwd_workspace_bytes), not
  *             touched between the two calls.  Without layernorm (ln_weight NULL) shard_bwd alone is the whole backward.
+ *   num_rows == 0 (a rank or row chunk without rows): every call succeeds and reads no row; the row arrays (x, gy, y, gx, moments,
+ *             row_stats, row_sums) may be NULL, the requested weight / bias / LayerNorm gradients are written as zeros.
  * ------------------------------------------------------------------------------------------ */
 int kagnn_fastkan_row_moments(const float* x, int64_t ldx, int64_t num_rows, int32_t in_features,
                               float* moments /* [N,2] */, void* stream);

@@ -789,9 +789,9 @@ int kagnn_fastkan_shard_bwd(const float* x, int64_t ldx, const float* gy, int64_
     KAGNN_CHECK_ARG(centers && spline_w && ws, "null array");
     KAGNN_CHECK_ARG(N == 0 || (x && gy), "null array");
     KAGNN_CHECK_ARG(!(parts & 1) || N == 0 || gx, "null array");
-    KAGNN_CHECK_ARG(!(parts & 1) || ln_w == nullptr || (ln_b && row_stats && (N == 0 || row_sums)), "layernorm needs bias, row_stats and row_sums");
+    KAGNN_CHECK_ARG(!(parts & 1) || ln_w == nullptr || N == 0 || row_sums, "layernorm needs row_sums");
     KAGNN_CHECK_ARG(!(parts & 2) || (g_spline_w && (base_w == nullptr || g_base_w)), "the weight-gradient half needs its outputs");
-    KAGNN_CHECK_ARG(ln_w == nullptr || (ln_b && row_stats), "layernorm needs bias and row_stats");
+    KAGNN_CHECK_ARG(ln_w == nullptr || (ln_b && (N == 0 || row_stats)), "layernorm needs bias and row_stats");   // (no rows: no statistics)
     if (mode == KAGNN_PREC_SPLIT && !(fits32(N, ldx) && fits32(N, ldgy) && fits32(N, ldgx)))
         return fail(KAGNN_ERR_UNSUPPORTED, "%s: leading dimension > 7680 floats; call with KAGNN_PREC_FP32", __func__);
     return fastkan_bwd(x, ldx, gy, ldgy, N, in, out, ng, centers, denominator, ln_w, ln_b, 0.0f, spline_w,

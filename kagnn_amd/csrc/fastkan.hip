@@ -845,6 +845,15 @@ int fastkan_bwd(const float* x, long ldx, const float* gy, long ldgy, long N, in
         KAGNN_LAUNCH_CHECK();
         return KAGNN_OK;
     }
+    if (N == 0 && shard) {
+        // a rank without rows (x, gy, stats may be NULL): gx and row_sums have no rows, the weight gradients are empty sums -- no kernel
+        if (do_dw) {
+            KAGNN_HIP(hipMemsetAsync(g_sw, 0, (size_t)out * in * ng * sizeof(float), st));
+            if (g_bw) KAGNN_HIP(hipMemsetAsync(g_bw, 0, (size_t)out * in * sizeof(float), st));
+            if (g_bb) KAGNN_HIP(hipMemsetAsync(g_bb, 0, (size_t)out * sizeof(float), st));
+        }
+        return KAGNN_OK;
+    }
     if (p.split) {
         // same split-precision kernels as the B-spline layer, K == 0 selecting the RBF basis
         const RbfArgs rb = fk_rbf(centers, ng, den, lnw, lnb, stats, nullptr, gz);

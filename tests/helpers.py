@@ -346,3 +346,71 @@ def half_parity(got, rounded, plain, what, l2_tol=HALF_L2_TOL, flip_tol=HALF_FLI
     lp = l2_rel(got, plain)
     check(5.0 * lr <= lp, what + ": the rounding oracle must explain the result at least 5x better than the unrounded one", (lr, lp))
     return lr, lp
+
+
+# ---------------------------------------------------------------------------------- feature-sharded FastKAN layer, restated
+# The local halves of the feature-sharded FastKAN layer (kagnn_amd.ops.fastkan_row_moments ... fastkan_shard_bwd_finish) with torch
+# ops in fp64: the stand-ins the gloo tests inject as ``local_ops`` (tests/test_sharded_gloo.py: what is under test there is the
+# exchange algebra around them) and the per-rank reference of tests/test_gpu_fastkan_shards.py.  Results come back in x's dtype.
+def fk_row_moments(x):
+    xd = x.double()
+    mean = xd.mean(1)
+    return torch.stack([mean, ((xd - mean[:, None]) ** 2).sum(1)], 1).to(x.dtype)
+
+
+def fk_merge_moments(gathered, width, eps):
+    g = gathered.double()
+    mean, m2 = g[0, :, 0].clone(), g[0, :, 1].clone()
+    for p in range(1, g.size(0)):                       # Chan's update, rank order
+        na, nb = float(p * width), float(width)
+        d = g[p, :, 0] - mean
+        mean = mean + d * (nb / (na + nb))
+        m2 = m2 + g[p, :, 1] + d * d * (na * nb / (na + nb))
+    return torch.stack([mean, torch.rsqrt(m2 / (g.size(0) * width) + eps)], 1).to(gathered.dtype)
+
+
+def fk_partial(z, x, sw, bw, bb, centers, den):
+    phi = orc.rbf_bases(z, centers.double(), den)
+    y = torch.nn.functional.linear(phi.view(z.size(0), -1), sw.double())
+    if bw is not None:
+        y = y + torch.nn.functional.linear(torch.nn.functional.silu(x), bw.double(), None if bb is None else bb.double())
+    return y
+
+
+def fk_shard_fwd(x, stats, ln_w, ln_b, sw, bw, bb, centers, den, mode=None):
+    xd = x.double()
+    with torch.no_grad():
+        z = xd if ln_w is None else (xd - stats[:, :1].double()) * stats[:, 1:].double() * ln_w.double() + ln_b.double()
+        return fk_partial(z, xd, sw, bw, bb, centers, den).to(x.dtype)
+
+
+def fk_shard_bwd(x, gy, stats, ln_w, ln_b, sw, bw, centers, den, mode=None, want_bias=False):
+    xd = x.detach().double()
+    zhat = None if ln_w is None else (xd - stats[:, :1].double()) * stats[:, 1:].double()
+    with torch.enable_grad():
+        xb = xd.clone().requires_grad_(True)                     # the base branch's (and, without LayerNorm, the RBF's) input
+        z = xb if ln_w is None else (zhat * ln_w.detach().double() + ln_b.detach().double()).requires_grad_(True)
+        swd = sw.detach().double().requires_grad_(True)
+        bwd = None if bw is None else bw.detach().double().requires_grad_(True)
+        bbd = torch.zeros(sw.size(0), dtype=torch.float64, requires_grad=True) if (want_bias and bw is not None) else None
+        y = fk_partial(z, xb, swd, bwd, bbd, centers, den)
+        y.backward(gy.double())
+    gxb = torch.zeros_like(xd) if xb.grad is None else xb.grad      # (LayerNorm without base branch: x enters through z alone)
+    st = dict(gx=gxb, gz=None if ln_w is None else z.grad, zhat=zhat, rstd=None if ln_w is None else stats[:, 1:].double(),
+              lw=ln_w, dtype=x.dtype)
+    sums = None
+    if ln_w is not None:
+        h = z.grad * ln_w.detach().double()
+        sums = torch.stack([h.sum(1), (h * zhat).sum(1)], 1).to(x.dtype)
+    f = x.dtype
+    return st, sums, swd.grad.to(f), None if bwd is None else bwd.grad.to(f), None if bbd is None else bbd.grad.to(f)
+
+
+def fk_shard_bwd_finish(st, sums, width_total):
+    f = st["dtype"]
+    if st["lw"] is None:
+        return st["gx"].to(f), None, None
+    h = st["gz"] * st["lw"].detach().double()
+    s = sums.double() / width_total
+    gx = st["gx"] + st["rstd"] * (h - s[:, :1] - st["zhat"] * s[:, 1:])
+    return gx.to(f), (st["gz"] * st["zhat"]).sum(0).to(f), st["gz"].sum(0).to(f)

@@ -228,6 +228,44 @@ def _graph_level(flavour):
     return build
 
 
+def _fastkan_shards(n, fi, fo, grid, use_base):
+    """P = 2 emulated ranks of the feature-sharded FastKAN layer (ops.fastkan_row_moments ... fastkan_shard_bwd_finish): forward, the
+    backward in its two halves and the finish.  ``st.gx`` (from torch.empty; without a base branch the finish ADDS into what the
+    input-gradient half left there) and ``st.ws`` (d loss / dz, alive from the first half to the finish) are the buffers in question"""
+    def build():
+        torch.manual_seed(n)
+        layer = kagnn_amd.FastKANLayer(fi, fo, num_grids=grid, use_base_update=use_base).to(DEV)
+        with torch.no_grad():
+            layer.layernorm.weight.uniform_(0.5, 1.5)
+            layer.layernorm.bias.uniform_(-0.3, 0.3)
+        x = (torch.randn(n, fi, generator=torch.Generator().manual_seed(2)) * 1.3 + 0.2).to(DEV)
+        gy = torch.randn(n, fo, generator=torch.Generator().manual_seed(7)).to(DEV)
+        w, den, eps = fi // 2, float(layer.rbf.denominator), float(layer.layernorm.eps)
+
+        def run():
+            with torch.no_grad():
+                xs = [x[:, p * w:(p + 1) * w].contiguous() for p in range(2)]
+                stats = ops.fastkan_merge_moments(torch.stack([ops.fastkan_row_moments(v) for v in xs]), w, eps)
+                out, states, total = [stats], [], None
+                for p, v in enumerate(xs):
+                    cols = slice(p * w, (p + 1) * w)
+                    prm = (stats, layer.layernorm.weight[cols], layer.layernorm.bias[cols],
+                           layer.spline_linear.weight.view(fo, fi, grid)[:, cols, :].reshape(fo, w * grid),
+                           layer.base_linear.weight[:, cols] if use_base else None)
+                    bb = layer.base_linear.bias if (use_base and p == 0) else None
+                    out.append(ops.fastkan_shard_fwd(v, *prm, bb, layer.rbf.grid, den))
+                    st, sums = ops.fastkan_shard_bwd_halves(v, gy, *prm, layer.rbf.grid, den, part="input")
+                    total = sums.clone() if total is None else total + sums
+                    out += [sums] + [g for g in ops.fastkan_shard_bwd_halves(v, gy, *prm, layer.rbf.grid, den, part="weight", state=st,
+                                                                             want_bias=bb is not None) if g is not None]
+                    states.append(st)
+                for st in states:
+                    out += list(ops.fastkan_shard_bwd_finish(st, total, fi))
+                return out
+        return layer, run
+    return build
+
+
 CASES = {}
 for _shape in [(1000, 64, 64, 5), (777, 37, 70, 5), (3, 5, 1, 3), (2049, 128, 128, 8), (513, 128, 64, 8), (300, 20, 130, 12), (1500, 256, 40, 5)]:
     for _mode in ("split", "half", "fp32"):
@@ -238,6 +276,9 @@ for _fl in ("kan", "fastkan"):
     for _shape in [(5000, 60000, 64, 64), (1201, 9000, 24, 48), (4000, 50000, 128, 128)]:
         CASES["%s GIN layer n%d e%d %d->%d" % (_fl, *_shape)] = ("split", _gin(_fl, *_shape))
     CASES[f"graph-level {_fl} step"] = ("split", _graph_level(_fl))
+for _mode in ("split", "fp32"):                 # odd shard widths (33, 15); the second: LayerNorm without base branch
+    CASES[f"FastKAN shards 301x66 P2->40 G8 {_mode}"] = (_mode, _fastkan_shards(301, 66, 40, 8, True))
+    CASES[f"FastKAN shards 203x30 P2->72 G5 no base {_mode}"] = (_mode, _fastkan_shards(203, 30, 72, 5, False))
 CASES["KAN GIN layer half mode"] = ("half", _gin("kan", 5000, 60000, 64, 64))
 for _a, _k, _p in [("kan", "gin", 0.0), ("kan", "gin", 0.3), ("kan", "gcn", 0.0), ("fastkan", "gin", 0.0), ("fastkan", "gcn", 0.2)]:
     CASES[f"{_a} {_k} node model dropout {_p}"] = ("split", _node_model(_a, _k, _p))
