@@ -55,7 +55,7 @@ extern "C" {
 #define KAGNN_DTYPE_F32 0
 #define KAGNN_DTYPE_BF16 1
 
-int kagnn_version(void);          /* 270 = 269 + kagnn_fastkan_edge_abs_sum, kagnn_fastkan_edge_abs_sum_bwd (+ _workspace_bytes), kagnn_fastkan_edge_curves; 269 = 268 + kagnn_kan_edge_abs_sum, kagnn_kan_edge_abs_sum_bwd (+ _workspace_bytes), kagnn_kan_edge_curves; 268 = 267 + spline orders 5..KAGNN_MAX_SPLINE_ORDER in the per-operation KANLinear calls (no new entry point); 267 = 266 + kagnn_linear_fwd, kagnn_linear_bwd_input, kagnn_linear_bwd_weight (+ _workspace_bytes); 266 = 265 + kagnn_l1_loss_meter_fwd, kagnn_regression_epoch_update; 265 = 264 + kagnn_node_eval, kagnn_early_stop_update, kagnn_copy_if; 264 = 263 + kagnn_degree_one_hot, kagnn_nll_loss_fwd / _bwd; 263 = 262 + kagnn_batch_assemble; 262 = 261 - the fields edge_src, edge_dst, csr_flags of kagnn_kagin_model_t; 261 = 260 + kagnn_fastkan_fwd_stats_in_kernel; 260 = round 6: + the feature-sharded FastKAN entry points kagnn_fastkan_row_moments .. _shard_bwd_finish, + kagnn_kagin_model_*; 250 = 240 + KAGNN_PREC_HALF; 240 = 230 + kagnn_gin_kan_layer_bwd_bn_sums; 230 = 220 + the *_affine entry points of a folded BatchNorm1d; 220 = 210 + the stage timer) */
+int kagnn_version(void);          /* 271 = 270 + kagnn_attention_fwd, kagnn_attention_bwd (+ _workspace_bytes); 270 = 269 + kagnn_fastkan_edge_abs_sum, kagnn_fastkan_edge_abs_sum_bwd (+ _workspace_bytes), kagnn_fastkan_edge_curves; 269 = 268 + kagnn_kan_edge_abs_sum, kagnn_kan_edge_abs_sum_bwd (+ _workspace_bytes), kagnn_kan_edge_curves; 268 = 267 + spline orders 5..KAGNN_MAX_SPLINE_ORDER in the per-operation KANLinear calls (no new entry point); 267 = 266 + kagnn_linear_fwd, kagnn_linear_bwd_input, kagnn_linear_bwd_weight (+ _workspace_bytes); 266 = 265 + kagnn_l1_loss_meter_fwd, kagnn_regression_epoch_update; 265 = 264 + kagnn_node_eval, kagnn_early_stop_update, kagnn_copy_if; 264 = 263 + kagnn_degree_one_hot, kagnn_nll_loss_fwd / _bwd; 263 = 262 + kagnn_batch_assemble; 262 = 261 - the fields edge_src, edge_dst, csr_flags of kagnn_kagin_model_t; 261 = 260 + kagnn_fastkan_fwd_stats_in_kernel; 260 = round 6: + the feature-sharded FastKAN entry points kagnn_fastkan_row_moments .. _shard_bwd_finish, + kagnn_kagin_model_*; 250 = 240 + KAGNN_PREC_HALF; 240 = 230 + kagnn_gin_kan_layer_bwd_bn_sums; 230 = 220 + the *_affine entry points of a folded BatchNorm1d; 220 = 210 + the stage timer) */
 const char* kagnn_last_error(void);
 
 /* Stage timer -- a measurement aid, off by default (no reference counterpart: the reference times whole epochs with
@@ -805,6 +805,42 @@ int kagnn_linear_bwd_input(const float* gy, int64_t ldgy, const float* y, int64_
 int kagnn_linear_bwd_weight(const float* x, int64_t ldx, const float* gy, int64_t ldgy, const float* y, int64_t ldy,
                             int64_t num_rows, int32_t in_features, int32_t out_features, float* g_weight, float* g_bias,
                             void* workspace, size_t workspace_bytes, void* stream);
+
+/* Dense multi-head attention with the bias added AFTER the softmax: the core of the reference's AttentionWithFastKANTransform
+ * (node_classification_clean/fastkan.py:182-198) between its projections and linear_o, and the backward of that.
+ *   s[b,q,k,h] = scale * sum_c wq[b,q,h,c] wk[b,k,h,c]         p = softmax over k of s
+ *   a[b,q,k,h] = p + bias[b,q,k]                                (one bias for every head; bias == NULL: a = p)
+ *   o[b,q,h,:] = sum_k a[b,q,k,h] wv[b,k,h,:]                   o *= sigmoid(gate[b,q,h,:])   (gate == NULL: no gate)
+ * Layouts: wq, gate, o, o_ungated and their gradients are [B * Q, H * c] fp32 rows, wk, wv and theirs [B * K, H * c], each with a
+ * row stride in elements (>= H * c) and unit column stride; head h owns columns [h * c, (h + 1) * c).  bias is [B, Q, K] with a
+ * batch stride and a row stride in elements and unit stride along K; a batch (or row) stride of 0 broadcasts on the read side.
+ * g_bias is a dense [B, Q, K] result (row stride >= K, batch stride >= Q * row stride).  stats is [2][B * Q * H] contiguous: the row
+ * maximum m of s, then log(sum_k exp(s - m)).  Limits: 1 <= head_dim <= 128 (else KAGNN_ERR_UNSUPPORTED), num_heads >= 1, batch,
+ * num_queries, num_keys 0 .. 2^31 - 1.  Nothing outside [rows, H * c] of an operand is read or written; nothing of size Q * K is
+ * allocated or written except g_bias.
+ * Forward: one pass over K with an online softmax; writes o, and with stats != NULL also stats and (o_ungated != NULL) the o before
+ * the gate -- what the backward takes.  K == 0: o = 0.  B * Q == 0: no launch.
+ * Backward (d_o = g_out * sigmoid(gate), the gradient of the ungated o; p recomputed from stats):
+ *   dA = <d_o[q,h,:], wv[k,h,:]>    g_wv[k] = sum_q a d_o[q]    g_bias[q,k] = sum_h dA    D[q,h] = sum_k p dA    dS = p (dA - D)
+ *   g_wq[q] = scale sum_k dS wk[k]    g_wk[k] = scale sum_q dS wq[q]    g_gate = g_out o_ungated sig (1 - sig)
+ * D is summed from p itself when there is a bias: the shortcut <d_o, o> equals D + sum_k bias dA there.  g_bias may be NULL (not
+ * computed); g_gate is required exactly when gate is given.  The workspace (kagnn_attention_bwd_workspace_bytes, 16-byte aligned)
+ * holds D and, with a gate, d_o: B * Q * H * (1 + c) floats, no term in Q * K.
+ * Precision: exact fp32 (ordered fma chains) in EVERY precision mode; KAGNN_PREC_* / KAGNN_PRECISION do not apply.
+ * Determinism: no atomics, every sum has one owner and a fixed order: the same inputs give bit-identical results from run to run. */
+int kagnn_attention_fwd(const float* wq, int64_t ldq, const float* wk, int64_t ldk, const float* wv, int64_t ldv, const float* bias,
+                        int64_t bias_batch_stride, int64_t bias_row_stride, const float* gate, int64_t ldgate, int64_t batch,
+                        int64_t num_queries, int64_t num_keys, int32_t num_heads, int32_t head_dim, float scale, float* o, int64_t ldo,
+                        float* o_ungated, int64_t ldo_ungated, float* stats, void* stream);
+int kagnn_attention_bwd_workspace_bytes(int64_t batch, int64_t num_queries, int64_t num_keys, int32_t num_heads, int32_t head_dim,
+                                        int32_t has_gate, size_t* bytes_host);
+int kagnn_attention_bwd(const float* g_out, int64_t ldg_out, const float* wq, int64_t ldq, const float* wk, int64_t ldk,
+                        const float* wv, int64_t ldv, const float* bias, int64_t bias_batch_stride, int64_t bias_row_stride,
+                        const float* gate, int64_t ldgate, const float* o_ungated, int64_t ldo_ungated, const float* stats,
+                        int64_t batch, int64_t num_queries, int64_t num_keys, int32_t num_heads, int32_t head_dim, float scale,
+                        float* g_wq, int64_t ldg_wq, float* g_wk, int64_t ldg_wk, float* g_wv, int64_t ldg_wv, float* g_bias,
+                        int64_t g_bias_batch_stride, int64_t g_bias_row_stride, float* g_gate, int64_t ldg_gate, void* workspace,
+                        size_t workspace_bytes, void* stream);
 
 /* What the graph-classification scripts wrap around their models (graph_classification/graph_classification_utils.py).
  *

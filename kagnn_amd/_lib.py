@@ -178,6 +178,15 @@ _SIGNATURES = {
     "kagnn_linear_bwd_input": (c_int32, [_P, c_int64, _P, c_int64, c_int64, c_int32, _P, c_int32, _P, c_int64, _P]),
     "kagnn_linear_bwd_weight": (c_int32, [_P, c_int64, _P, c_int64, _P, c_int64, c_int64, c_int32, c_int32, _P, _P, _P,
                                           c_size_t, _P]),
+    # wq ldq wk ldk wv ldv bias bias_bs bias_rs gate ldgate B Q K H c scale o ldo o_ungated ldou stats stream
+    "kagnn_attention_fwd": (c_int32, [_P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, c_int64, _P, c_int64, c_int64, c_int64, c_int64,
+                                      c_int32, c_int32, c_float, _P, c_int64, _P, c_int64, _P, _P]),
+    "kagnn_attention_bwd_workspace_bytes": (c_int32, [c_int64, c_int64, c_int64, c_int32, c_int32, c_int32, POINTER(c_size_t)]),
+    # g_out ldgo wq ldq wk ldk wv ldv bias bias_bs bias_rs gate ldgate o_ungated ldou stats B Q K H c scale g_wq ld g_wk ld g_wv ld
+    # g_bias gb_bs gb_rs g_gate ldgg ws bytes stream
+    "kagnn_attention_bwd": (c_int32, [_P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, c_int64, _P, c_int64, _P, c_int64,
+                                      _P, c_int64, c_int64, c_int64, c_int32, c_int32, c_float, _P, c_int64, _P, c_int64, _P, c_int64,
+                                      _P, c_int64, c_int64, _P, c_int64, _P, c_size_t, _P]),
     "kagnn_l1_loss_fwd": (c_int32, [_P, _P, c_int64, _P, _P]),
     "kagnn_l1_loss_bwd": (c_int32, [_P, _P, c_int64, _P, _P, _P]),
     "kagnn_degree_one_hot": (c_int32, [_P, c_int64, c_int32, _P, c_int64, _P]),

@@ -84,7 +84,7 @@ using namespace kagnn;
 #pragma GCC visibility push(default)
 extern "C" {
 
-int kagnn_version(void) { return 270; }
+int kagnn_version(void) { return 271; }
 const char* kagnn_last_error(void) { return g_err; }
 
 int kagnn_stage_timer_enable(const char* only) {
@@ -1101,6 +1101,64 @@ int kagnn_linear_bwd_weight(const float* x, int64_t ldx, const float* gy, int64_
     KAGNN_CHECK_ARG(x && gy && ws, "null array");
     KAGNN_CHECK_ARG(((uintptr_t)ws & 15) == 0, "the workspace must be 16-byte aligned");
     return linear_dw(x, ldx, gy, ldgy, y, ldy, N, in, out, gW, gb, (float*)ws, ws_bytes, as_stream(stream));
+}
+
+// ---------------------------------------------------------------- dense attention, bias after the softmax (attention.hip)
+// exact fp32 in every precision mode; every sum has one owner and a fixed order (no atomics)
+
+static int attention_shape_ok(const char* fn, int64_t B, int64_t Q, int64_t K, int32_t H, int32_t c) {
+    KAGNN_CHECK_ARG_AS(fn, B >= 0 && Q >= 0 && K >= 0 && B <= 0x7fffffffL && Q <= 0x7fffffffL && K <= 0x7fffffffL, "batch / num_queries / num_keys must be 0 .. 2^31 - 1");
+    KAGNN_CHECK_ARG_AS(fn, H >= 1, "num_heads must be >= 1");
+    if (c < 1 || c > 128) return fail(KAGNN_ERR_UNSUPPORTED, "%s: head_dim %ld is outside 1..128", fn, (long)c);
+    KAGNN_CHECK_ARG_AS(fn, (int64_t)H * c <= 0x7fffffffL, "num_heads * head_dim must fit int32");
+    return KAGNN_OK;
+}
+
+int kagnn_attention_fwd(const float* wq, int64_t ldq, const float* wk, int64_t ldk, const float* wv, int64_t ldv, const float* bias,
+                        int64_t bias_bs, int64_t bias_rs, const float* gate, int64_t ldgate, int64_t B, int64_t Q, int64_t K,
+                        int32_t H, int32_t c, float scale, float* o, int64_t ldo, float* o_ungated, int64_t ldou, float* stats,
+                        void* stream) {
+    KAGNN_STAGE(stream);
+    if (int rc = attention_shape_ok(__func__, B, Q, K, H, c)) return rc;
+    const int64_t hc = (int64_t)H * c;
+    KAGNN_CHECK_ARG(ldq >= hc && ldk >= hc && ldv >= hc && ldo >= hc, "a row stride is below num_heads * head_dim");
+    KAGNN_CHECK_ARG(!gate || ldgate >= hc, "the gate's row stride is below num_heads * head_dim");
+    KAGNN_CHECK_ARG(!o_ungated || ldou >= hc, "o_ungated's row stride is below num_heads * head_dim");
+    KAGNN_CHECK_ARG(!bias || (bias_bs >= 0 && bias_rs >= 0), "negative bias stride");
+    KAGNN_CHECK_ARG(!o_ungated || stats, "o_ungated is written together with stats");
+    if (B * Q == 0) return KAGNN_OK;
+    KAGNN_CHECK_ARG(wq && o && (K == 0 || (wk && wv)), "null array");
+    return attention_fwd(wq, ldq, wk, ldk, wv, ldv, bias, bias_bs, bias_rs, gate, ldgate, B, Q, K, H, c, scale, o, ldo, o_ungated, ldou,
+                         stats, as_stream(stream));
+}
+
+int kagnn_attention_bwd_workspace_bytes(int64_t B, int64_t Q, int64_t K, int32_t H, int32_t c, int32_t has_gate, size_t* bytes) {
+    KAGNN_CHECK_ARG(bytes != nullptr, "null bytes pointer");
+    if (int rc = attention_shape_ok(__func__, B, Q, K, H, c)) return rc;
+    *bytes = attention_bwd_ws_bytes(B, Q, K, H, c, has_gate != 0);
+    return KAGNN_OK;
+}
+
+int kagnn_attention_bwd(const float* g_out, int64_t ldgo, const float* wq, int64_t ldq, const float* wk, int64_t ldk, const float* wv,
+                        int64_t ldv, const float* bias, int64_t bias_bs, int64_t bias_rs, const float* gate, int64_t ldgate,
+                        const float* o_ungated, int64_t ldou, const float* stats, int64_t B, int64_t Q, int64_t K, int32_t H, int32_t c,
+                        float scale, float* g_wq, int64_t ldgq, float* g_wk, int64_t ldgk, float* g_wv, int64_t ldgv, float* g_bias,
+                        int64_t gb_bs, int64_t gb_rs, float* g_gate, int64_t ldgg, void* ws, size_t ws_bytes, void* stream) {
+    KAGNN_STAGE(stream);
+    if (int rc = attention_shape_ok(__func__, B, Q, K, H, c)) return rc;
+    const int64_t hc = (int64_t)H * c;
+    KAGNN_CHECK_ARG(ldgo >= hc && ldq >= hc && ldk >= hc && ldv >= hc && ldou >= hc && ldgq >= hc && ldgk >= hc && ldgv >= hc,
+                    "a row stride is below num_heads * head_dim");
+    KAGNN_CHECK_ARG(!gate || (ldgate >= hc && ldgg >= hc), "a gate row stride is below num_heads * head_dim");
+    KAGNN_CHECK_ARG(!bias || (bias_bs >= 0 && bias_rs >= 0), "negative bias stride");
+    KAGNN_CHECK_ARG(!g_bias || (gb_rs >= K && (B <= 1 || gb_bs >= Q * gb_rs)), "g_bias is a dense [B, Q, K] result: overlapping strides");
+    KAGNN_CHECK_ARG((gate != nullptr) == (g_gate != nullptr), "g_gate goes with gate");
+    if (B * (Q + K) == 0) return KAGNN_OK;
+    KAGNN_CHECK_ARG(ws != nullptr && ((uintptr_t)ws & 15) == 0, "the workspace must be non-null and 16-byte aligned");
+    KAGNN_CHECK_ARG((Q == 0 || (g_out && wq && o_ungated && stats && g_wq)) && (K == 0 || (wk && wv && g_wk && g_wv)), "null array");
+    return attention_bwd(g_out, ldgo, wq, ldq, wk, ldk, wv, ldv, bias, bias_bs, bias_rs, gate, ldgate, o_ungated, ldou, stats, B, Q, K, H,
+                         c, scale, g_wq, ldgq, g_wk, ldgk, g_wv, ldgv, g_bias, gb_bs, gb_rs, g_gate, ldgg, (float*)ws, ws_bytes,
+                         as_stream(stream));
 }
 
 // ---------------------------------------------------------------- per-edge activations of a KANLinear (kan_edge.hip)

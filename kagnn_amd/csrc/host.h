@@ -253,6 +253,19 @@ void linear_dw_plan(long N, int in, int out, long* slabs, long* rows_per_slab);
 size_t linear_dw_ws_bytes(long N, int in, int out);
 int linear_dw(const float* x, long ldx, const float* gy, long ldgy, const float* y, long ldy, long N, int in, int out, float* gW,
               float* gb, float* ws, size_t ws_bytes, hipStream_t st);
+// c[M,Nc] = a[M,K] b[Nc,K]^T with a row stride on all three (the forward's product without bias / ReLU and a strided weight)
+int linear_abt(const float* a, long lda, long M, int K, const float* b, long ldb, long Nc, float* c, long ldc, hipStream_t st);
+
+// ---- attention.hip (dense multi-head attention, bias after the softmax; exact fp32, no atomics)
+int attention_fwd(const float* wq, long ldq, const float* wk, long ldk, const float* wv, long ldv, const float* bias, long bias_bs,
+                  long bias_rs, const float* gate, long ldg, long B, long Q, long K, int H, int c, float scale, float* o, long ldo,
+                  float* o_ungated, long ldou, float* stats, hipStream_t st);
+size_t attention_bwd_ws_bytes(long B, long Q, long K, int H, int c, int has_gate);
+int attention_bwd(const float* g_out, long ldgo, const float* wq, long ldq, const float* wk, long ldk, const float* wv, long ldv,
+                  const float* bias, long bias_bs, long bias_rs, const float* gate, long ldg, const float* o_ungated, long ldou,
+                  const float* stats, long B, long Q, long K, int H, int c, float scale, float* g_wq, long ldgq, float* g_wk,
+                  long ldgk, float* g_wv, long ldgv, float* g_bias, long gb_bs, long gb_rs, float* g_gate, long ldgg, float* ws,
+                  size_t ws_bytes, hipStream_t st);
 
 // ---- kan_edge.hip (per-edge activations phi_{o,i}: abs sum over the rows, its backward, sampled curves; exact fp32, orders 1..4)
 size_t kan_edge_abs_sum_ws_bytes(long N, int in, int out);

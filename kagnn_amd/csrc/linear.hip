@@ -277,6 +277,13 @@ int linear_fwd(const float* x, long ldx, long N, int in, const float* W, const f
     return launch_tall<KC>(A, B, in, N, out, e, st);
 }
 
+int linear_abt(const float* a, long lda, long M, int K, const float* b, long ldb, long Nc, float* c, long ldc, hipStream_t st) {
+    const LinOperand A{a, lda, nullptr, 0, M, -1, vec_ok(a, lda)};
+    const LinOperand B{b, ldb, nullptr, 0, Nc, -1, vec_ok(b, ldb)};
+    const LinEpilogue e{c, ldc, 0, nullptr, 0};
+    return launch_tall<KC>(A, B, K, M, Nc, e, st);
+}
+
 int linear_dx(const float* gy, long ldgy, const float* y, long ldy, long N, int out, const float* W, int in,
               float* gx, long ldgx, hipStream_t st) {
     const LinOperand A{gy, ldgy, y, ldy, N, -1, vec_ok(gy, ldgy) && vec_ok(y, ldy)};

@@ -7,11 +7,13 @@ spline_linear.weight, base_linear.weight, base_linear.bias``).  ``FastKANLayer.f
 call to ``kagnn_fastkan_fwd`` -- LayerNorm statistics, the Gaussian RBF expansion and both linear
 maps are fused in the kernel.  ``plot_curve`` (:87-115) is one column of ``edge_curves``; on the same kernels
 (``csrc/fastkan_edge.hip``) sit ``edge_l1`` and the KAN regulariser ``regularization_loss(x)``, which the reference has for
-efficient-KAN layers only.  The attention helper of the reference is not part of the KAGNN path and is not provided.
+efficient-KAN layers only.  ``AttentionWithFastKANTransform`` (:148-202) is five ``FastKANLayer`` projections around ONE call
+to ``ops.dense_attention`` (``csrc/attention.hip``): the reference's broadcast products ``[*, Q, K, H, c]`` and its attention
+tensor ``[*, Q, K, H]`` never exist.
 
-Attribution: the module surface restated here (class names, constructor signatures, parameter layout and the
-trunc-normal / linspace initialisation of ``SplineLinear`` / ``RadialBasisFunction`` / ``FastKANLayer`` / ``FastKAN``)
-follows the reference's ``node_classification_clean/fastkan.py``, which is
+Attribution: the module surface restated here (class names, constructor signatures, attribute names, parameter layout and the
+trunc-normal / linspace initialisation of ``SplineLinear`` / ``RadialBasisFunction`` / ``FastKANLayer`` / ``FastKAN`` /
+``AttentionWithFastKANTransform``) follows the reference's ``node_classification_clean/fastkan.py``, which is
     Copyright 2024 Li, Ziyao -- Licensed under the Apache License, Version 2.0
     (http://www.apache.org/licenses/LICENSE-2.0); distributed there on an "AS IS" BASIS, WITHOUT WARRANTIES OR
     CONDITIONS OF ANY KIND.
@@ -176,6 +178,40 @@ class FastKAN(nn.Module):
             if i + 1 < len(self.layers):
                 x = layer._forward(x)
         return out
+
+
+class AttentionWithFastKANTransform(nn.Module):
+    """Multi-head attention whose five linear maps are ``FastKANLayer``s and whose additive ``bias`` enters AFTER the softmax
+    (the reference's formula, fastkan.py:182-198).  ``q [*, Q, q_dim]``, ``k [*, K, k_dim]``, ``v [*, K, v_dim]``, ``bias``
+    broadcastable to ``[*, Q, K]`` -> ``[*, Q, q_dim]``.  With ``gating`` the heads' output is multiplied by
+    ``sigmoid(linear_g(q))`` (the gate sees the raw ``q``) before ``linear_o``."""
+
+    def __init__(self, q_dim: int, k_dim: int, v_dim: int, head_dim: int, num_heads: int, gating: bool = True):
+        super().__init__()
+        self.num_heads = num_heads
+        total_dim = head_dim * self.num_heads
+        self.gating = gating
+        self.linear_q = FastKANLayer(q_dim, total_dim)
+        self.linear_k = FastKANLayer(k_dim, total_dim)
+        self.linear_v = FastKANLayer(v_dim, total_dim)
+        self.linear_o = FastKANLayer(total_dim, q_dim)
+        self.linear_g = None
+        if self.gating:
+            self.linear_g = FastKANLayer(q_dim, total_dim)
+        self.norm = head_dim ** -0.5
+
+    def forward(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, bias: torch.Tensor = None) -> torch.Tensor:
+        wq, wk, wv = self.linear_q(q), self.linear_k(k), self.linear_v(v)
+        g = None if self.linear_g is None else self.linear_g(q)
+        nq, nk = q.shape[-2], k.shape[-2]
+        lead = torch.broadcast_shapes(q.shape[:-2], k.shape[:-2], v.shape[:-2])
+        # equal leading dimensions: views.  Anything else that broadcasts is expanded and materialised here, after the projections
+        # (autograd sums the copies back)
+        rows = lambda t: t.expand(*lead, *t.shape[-2:]).reshape(-1, *t.shape[-2:])
+        if bias is not None:
+            bias = bias.expand(*lead, nq, nk).reshape(-1, nq, nk)        # (one leading dimension: still the stride-0 view)
+        o = ops.dense_attention(rows(wq), rows(wk), rows(wv), self.num_heads, self.norm, bias, None if g is None else rows(g))
+        return self.linear_o(o.reshape(*lead, nq, o.shape[-1]))
 
 
 def _collect(layer: FastKANLayer, x: torch.Tensor, use_layernorm: bool) -> None:

@@ -826,6 +826,96 @@ def linear(x, weight, bias=None, relu: bool = False) -> torch.Tensor:
     return y.view(*x.shape[:-1], weight.size(0))
 
 
+# ======================================================================== dense attention (bias after the softmax)
+def _att_rows(t: torch.Tensor, what: str):
+    """``[B, R, W]`` fp32 as the kernels' ``[B * R, W]`` rows with ONE row stride: ``(tensor, ld)``.  Copies only where the
+    strides cannot be described that way (a column slice of a wider matrix is passed as it is)."""
+    if t.dim() != 3:
+        raise ValueError(f"dense_attention: {what} must be [batch, rows, num_heads * head_dim], got shape {tuple(t.shape)}")
+    if t.dtype != torch.float32:
+        raise TypeError(f"kagnn_amd kernels are fp32; got {t.dtype} for {what}")
+    b, r, w = t.shape
+    for _ in range(2):
+        ld = t.stride(1) if r > 1 else (t.stride(0) if b > 1 else w)
+        if (w == 1 or t.stride(2) == 1) and ld >= w and (b <= 1 or r <= 1 or t.stride(0) == r * ld):
+            return t, ld
+        t = t.contiguous()
+    raise AssertionError("unreachable")
+
+
+class _DenseAttentionFn(Function):
+    """o = (softmax_k(scale <wq, wk>) + bias) wv per head, times sigmoid(gate): csrc/attention.hip.  Saves the operands, the row
+    statistics [2, B, Q, H] and the ungated o; nothing of size Q * K except the bias gradient, which is a result."""
+
+    @staticmethod
+    @_on_operand_device
+    def forward(ctx, wq, wk, wv, bias, gate, num_heads, scale):
+        _need_cuda(wq, wk, wv, bias, gate)
+        wq, ldq = _att_rows(wq, "wq")
+        wk, ldk = _att_rows(wk, "wk")
+        wv, ldv = _att_rows(wv, "wv")
+        B, Q, hc = wq.shape
+        K = wk.size(1)
+        H = int(num_heads)
+        if H < 1 or hc % H or wk.shape != (B, K, hc) or wv.shape != (B, K, hc):
+            raise ValueError(f"dense_attention: wq {tuple(wq.shape)}, wk {tuple(wk.shape)}, wv {tuple(wv.shape)} do not fit {H} heads")
+        c = hc // H
+        ldg = 0
+        if gate is not None:
+            gate, ldg = _att_rows(gate, "gate")
+            if gate.shape != wq.shape:
+                raise ValueError(f"dense_attention: gate {tuple(gate.shape)} is not wq's shape {tuple(wq.shape)}")
+        bbs = brs = 0
+        if bias is not None:
+            if bias.dtype != torch.float32:
+                raise TypeError(f"kagnn_amd kernels are fp32; got {bias.dtype} for bias")
+            if bias.shape != (B, Q, K):
+                raise ValueError(f"dense_attention: bias {tuple(bias.shape)} is not [batch, num_queries, num_keys] = {(B, Q, K)}")
+            if K > 1 and bias.stride(2) != 1:
+                bias = bias.contiguous()
+            bbs, brs = (bias.stride(0) if B > 1 else 0), (bias.stride(1) if Q > 1 else 0)
+        dev = wq.device
+        need = any(ctx.needs_input_grad[:5])
+        o = torch.empty((B, Q, hc), dtype=torch.float32, device=dev)
+        stats = torch.empty((2, B, Q, H), dtype=torch.float32, device=dev) if need else None
+        oung = torch.empty((B, Q, hc), dtype=torch.float32, device=dev) if need and gate is not None else None
+        _call("kagnn_attention_fwd", _ptr(wq), ldq, _ptr(wk), ldk, _ptr(wv), ldv, _ptr(bias), bbs, brs, _ptr(gate), ldg, B, Q, K, H, c,
+              float(scale), _ptr(o), hc, _ptr(oung), hc, _ptr(stats), _stream())
+        if need:
+            ctx.save_for_backward(wq, wk, wv, bias, gate, stats, o if oung is None else oung)
+            ctx.dims = (B, Q, K, H, c, float(scale), ldq, ldk, ldv, ldg, bbs, brs)
+        return o
+
+    @staticmethod
+    @once_differentiable
+    @_on_operand_device
+    def backward(ctx, gout):
+        wq, wk, wv, bias, gate, stats, oung = ctx.saved_tensors
+        B, Q, K, H, c, scale, ldq, ldk, ldv, ldg, bbs, brs = ctx.dims
+        hc = H * c
+        gout, ldgo = _att_rows(gout, "the upstream gradient")
+        dev = wq.device
+        g_wq = torch.empty((B, Q, hc), dtype=torch.float32, device=dev)
+        g_wk = torch.empty((B, K, hc), dtype=torch.float32, device=dev)
+        g_wv = torch.empty((B, K, hc), dtype=torch.float32, device=dev)
+        g_bias = torch.empty((B, Q, K), dtype=torch.float32, device=dev) if bias is not None and ctx.needs_input_grad[3] else None
+        g_gate = None if gate is None else torch.empty((B, Q, hc), dtype=torch.float32, device=dev)
+        ws = _ws(_sizes("kagnn_attention_bwd_workspace_bytes", B, Q, K, H, c, int(gate is not None)), dev)
+        _call("kagnn_attention_bwd", _ptr(gout), ldgo, _ptr(wq), ldq, _ptr(wk), ldk, _ptr(wv), ldv, _ptr(bias), bbs, brs, _ptr(gate), ldg,
+              _ptr(oung), hc, _ptr(stats), B, Q, K, H, c, scale, _ptr(g_wq), hc, _ptr(g_wk), hc, _ptr(g_wv), hc, _ptr(g_bias), Q * K, K,
+              _ptr(g_gate), hc, _ptr(ws), ws.numel(), _stream())
+        return g_wq, g_wk, g_wv, g_bias, g_gate, None, None
+
+
+def dense_attention(wq, wk, wv, num_heads: int, scale: float, bias=None, gate=None) -> torch.Tensor:
+    """Multi-head attention with the bias added AFTER the softmax, the core of the reference's ``AttentionWithFastKANTransform``:
+    ``o[b,q,h,:] = sum_k (softmax_k(scale <wq[b,q,h,:], wk[b,k,h,:]>) + bias[b,q,k]) wv[b,k,h,:]``, times ``sigmoid(gate)`` when a
+    gate is given.  ``wq``, ``gate`` ``[B, Q, H*c]``; ``wk``, ``wv`` ``[B, K, H*c]``; ``bias`` ``[B, Q, K]`` (an ``expand``ed view is read in
+    place).  ``1 <= c <= 128``.  One fused kernel each way plus the bias-gradient product: nothing of size ``Q*K`` is stored but the
+    bias gradient.  Exact fp32 in every precision mode, bit-reproducible.  Gradients: ``wq, wk, wv, bias, gate``."""
+    return _DenseAttentionFn.apply(wq, wk, wv, bias, gate, int(num_heads), float(scale))
+
+
 # ======================================================================== efficient-KAN layer
 def kan_pack_chain(layers, grid_size: int, spline_order: int, mode: int):
     """Pack the weights of all layers of a KAN chain in ONE launch (``kagnn_kan_pack_batch``): ``layers`` is a list of

@@ -45,6 +45,7 @@ HOT = [
     (r"bn_", 0, 0),
     (r"batch_assemble_kernel", 0, 0),                  # the loader's one launch per mini-batch
     (r"linear_gemm_kernel<|linear_dw_reduce_kernel", 0, 0),   # the dense layer of the MLP baselines
+    (r"attention_", 0, 0),                             # dense attention: up to 4 x 32 row registers per lane at head_dim 128
 ]
 
 
