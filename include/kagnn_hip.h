@@ -55,7 +55,7 @@ extern "C" {
 #define KAGNN_DTYPE_F32 0
 #define KAGNN_DTYPE_BF16 1
 
-int kagnn_version(void);          /* 271 = 270 + kagnn_attention_fwd, kagnn_attention_bwd (+ _workspace_bytes); 270 = 269 + kagnn_fastkan_edge_abs_sum, kagnn_fastkan_edge_abs_sum_bwd (+ _workspace_bytes), kagnn_fastkan_edge_curves; 269 = 268 + kagnn_kan_edge_abs_sum, kagnn_kan_edge_abs_sum_bwd (+ _workspace_bytes), kagnn_kan_edge_curves; 268 = 267 + spline orders 5..KAGNN_MAX_SPLINE_ORDER in the per-operation KANLinear calls (no new entry point); 267 = 266 + kagnn_linear_fwd, kagnn_linear_bwd_input, kagnn_linear_bwd_weight (+ _workspace_bytes); 266 = 265 + kagnn_l1_loss_meter_fwd, kagnn_regression_epoch_update; 265 = 264 + kagnn_node_eval, kagnn_early_stop_update, kagnn_copy_if; 264 = 263 + kagnn_degree_one_hot, kagnn_nll_loss_fwd / _bwd; 263 = 262 + kagnn_batch_assemble; 262 = 261 - the fields edge_src, edge_dst, csr_flags of kagnn_kagin_model_t; 261 = 260 + kagnn_fastkan_fwd_stats_in_kernel; 260 = round 6: + the feature-sharded FastKAN entry points kagnn_fastkan_row_moments .. _shard_bwd_finish, + kagnn_kagin_model_*; 250 = 240 + KAGNN_PREC_HALF; 240 = 230 + kagnn_gin_kan_layer_bwd_bn_sums; 230 = 220 + the *_affine entry points of a folded BatchNorm1d; 220 = 210 + the stage timer) */
+int kagnn_version(void);          /* 272 = 271 + kagnn_kan_grid_resize (+ _workspace_bytes); 271 = 270 + kagnn_attention_fwd, kagnn_attention_bwd (+ _workspace_bytes); 270 = 269 + kagnn_fastkan_edge_abs_sum, kagnn_fastkan_edge_abs_sum_bwd (+ _workspace_bytes), kagnn_fastkan_edge_curves; 269 = 268 + kagnn_kan_edge_abs_sum, kagnn_kan_edge_abs_sum_bwd (+ _workspace_bytes), kagnn_kan_edge_curves; 268 = 267 + spline orders 5..KAGNN_MAX_SPLINE_ORDER in the per-operation KANLinear calls (no new entry point); 267 = 266 + kagnn_linear_fwd, kagnn_linear_bwd_input, kagnn_linear_bwd_weight (+ _workspace_bytes); 266 = 265 + kagnn_l1_loss_meter_fwd, kagnn_regression_epoch_update; 265 = 264 + kagnn_node_eval, kagnn_early_stop_update, kagnn_copy_if; 264 = 263 + kagnn_degree_one_hot, kagnn_nll_loss_fwd / _bwd; 263 = 262 + kagnn_batch_assemble; 262 = 261 - the fields edge_src, edge_dst, csr_flags of kagnn_kagin_model_t; 261 = 260 + kagnn_fastkan_fwd_stats_in_kernel; 260 = round 6: + the feature-sharded FastKAN entry points kagnn_fastkan_row_moments .. _shard_bwd_finish, + kagnn_kagin_model_*; 250 = 240 + KAGNN_PREC_HALF; 240 = 230 + kagnn_gin_kan_layer_bwd_bn_sums; 230 = 220 + the *_affine entry points of a folded BatchNorm1d; 220 = 210 + the stage timer) */
 const char* kagnn_last_error(void);
 
 /* Stage timer -- a measurement aid, off by default (no reference counterpart: the reference times whole epochs with
@@ -517,6 +517,21 @@ int kagnn_kan_grid_refit(const float* x, int64_t ldx, int64_t num_rows, const fl
                          int32_t grid_size, int32_t spline_order, const float* spline_weight,
                          const float* spline_scaler, float* new_spline_weight, void* workspace,
                          size_t workspace_bytes, void* stream);
+
+/* grid resize (the KAN paper's grid extension, and its inverse): the same refit between grids of TWO sizes,
+ *   grid_old [in, grid_size_old+2k+1] -> grid_new [in, grid_size_new+2k+1], one spline_order 1..4 for both,
+ *   spline_weight [out, in, grid_size_old+k] -> new_spline_weight [out, in, grid_size_new+k],
+ * with grid_size + 2k + 1 <= 48 on either side (up to 46 coefficients: three 16-wide blocks of the fp64 Gram matrices).
+ * `window` [in, 2] or NULL: row n takes part in feature f's fit only when window[f][0] <= x[n,f] < window[f][1] (rows in the
+ * knot extension beyond the new grid's range cannot be represented there and would leak their misfit into the range).
+ * `untouched` [in] or NULL: per feature, the number of new bases no participating row reached (coefficient 0).
+ * Deterministic (fixed-order slab sums, no atomics); nothing of size num_rows * in * coefficients exists.  Not in place. */
+int kagnn_kan_grid_resize_workspace_bytes(int64_t num_rows, int32_t in_features, int32_t grid_size_old, int32_t grid_size_new,
+                                          int32_t spline_order, size_t* bytes_host);
+int kagnn_kan_grid_resize(const float* x, int64_t ldx, int64_t num_rows, const float* grid_old, const float* grid_new,
+                          const float* window, int32_t in_features, int32_t out_features, int32_t grid_size_old,
+                          int32_t grid_size_new, int32_t spline_order, const float* spline_weight, const float* spline_scaler,
+                          float* new_spline_weight, int32_t* untouched, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Per-edge activations of a KANLinear: the edge functions

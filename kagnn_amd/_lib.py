@@ -134,6 +134,10 @@ _SIGNATURES = {
     "kagnn_kan_grid_refit_workspace_bytes": (c_int32, [c_int64, c_int32, c_int32, c_int32, POINTER(c_size_t)]),
     "kagnn_kan_grid_refit": (c_int32, [_P, c_int64, c_int64, _P, _P, c_int32, c_int32, c_int32, c_int32, _P, _P, _P,
                                        _P, c_size_t, _P]),
+    "kagnn_kan_grid_resize_workspace_bytes": (c_int32, [c_int64, c_int32, c_int32, c_int32, c_int32, POINTER(c_size_t)]),
+    # x ldx N grid_old grid_new window in out G_old G_new K sw sc new_sw untouched ws bytes stream
+    "kagnn_kan_grid_resize": (c_int32, [_P, c_int64, c_int64, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P, _P,
+                                        _P, _P, c_size_t, _P]),
     "kagnn_fastkan_fwd_workspace_bytes": (c_int32, [c_int64, c_int32, c_int32, c_int32, c_int32, POINTER(c_size_t)]),
     "kagnn_fastkan_fwd": (c_int32, [_P, c_int64, c_int64, c_int32, c_int32, c_int32, _P, c_float, _P, _P,
                                     c_float, _P, _P, _P, _P, c_int64, _P, c_int32, _P, c_size_t, _P]),

@@ -134,6 +134,10 @@ class KANLinear(nn.Module):
     def forward(self, x: torch.Tensor, _packed=None) -> torch.Tensor:
         assert x.dim() == 2 and x.size(1) == self.in_features
         if ops.layer_inputs_visible():
+            walk = ops._refine_walk()
+            if walk is not None:
+                walk.visit(self, x)                # a refine_grids walk: the layer moves to the finer grid BEFORE it evaluates x
+                _packed = None
             _collect(self, x)
         return self._forward(x, _packed)
 
@@ -180,15 +184,8 @@ class KANLinear(nn.Module):
             raise NotImplementedError("update_grid is not implemented at spline_order above 4: the least-squares refit of the "
                                       "coefficients is ill-conditioned at these orders (the reference's own fp64 refit loses the "
                                       "function from order 12). A layer whose grid buffer already holds per-feature knot rows runs.")
-        n, g, k, dev = x.size(0), self.grid_size, self.spline_order, x.device
-        ranked = torch.sort(x, dim=0).values
-        quantiles = ranked[torch.linspace(0, n - 1, g + 1, dtype=torch.int64, device=dev)]       # [G+1, in]
-        step = (ranked[-1] - ranked[0] + 2 * margin) / g
-        even = torch.arange(g + 1, dtype=torch.float32, device=dev).unsqueeze(1) * step + ranked[0] - margin
-        inner = self.grid_eps * even + (1 - self.grid_eps) * quantiles
-        below = inner[:1] - step * torch.arange(k, 0, -1, device=dev).unsqueeze(1)
-        above = inner[-1:] + step * torch.arange(1, k + 1, device=dev).unsqueeze(1)
-        new_grid = torch.cat([below, inner, above], dim=0).T.contiguous()
+        g, k = self.grid_size, self.spline_order
+        new_grid = self._quantile_knots(x, g, margin)
         scaler = self.spline_scaler if self.enable_standalone_scale_spline else None
         if g + k <= 16:
             fitted = ops.kan_grid_refit(x, self.grid, new_grid, self.spline_weight, scaler, g, k)
@@ -196,6 +193,68 @@ class KANLinear(nn.Module):
             fitted = self._refit_wide(x, new_grid, scaler)
         self.grid.copy_(new_grid)
         self.spline_weight.data.copy_(fitted)
+
+    def _quantile_knots(self, x: torch.Tensor, g: int, margin: float) -> torch.Tensor:
+        """``update_grid``'s knot rule (``ekan.py:180-205``) for ``g`` intervals: ``[in, g+2k+1]``"""
+        n, k, dev = x.size(0), self.spline_order, x.device
+        ranked = torch.sort(x, dim=0).values
+        quantiles = ranked[torch.linspace(0, n - 1, g + 1, dtype=torch.int64, device=dev)]       # [G+1, in]
+        step = (ranked[-1] - ranked[0] + 2 * margin) / g
+        even = torch.arange(g + 1, dtype=torch.float32, device=dev).unsqueeze(1) * step + ranked[0] - margin
+        inner = self.grid_eps * even + (1 - self.grid_eps) * quantiles
+        below = inner[:1] - step * torch.arange(k, 0, -1, device=dev).unsqueeze(1)
+        above = inner[-1:] + step * torch.arange(1, k + 1, device=dev).unsqueeze(1)
+        return torch.cat([below, inner, above], dim=0).T.contiguous()
+
+    @torch.no_grad()
+    def refine(self, x: torch.Tensor, grid_size: int, adaptive: bool = False, grid_range=None, margin=0.01) -> torch.Tensor:
+        """Grid extension (KAN paper, section 2.4): move the layer onto a grid of ``grid_size`` intervals -- finer, or coarser -- and
+        refit the coefficients on the rows of ``x`` (the layer's own input) so that its curves are kept; one device call,
+        ``ops.kan_grid_resize``, up to 46 coefficients.  Returns ``untouched [in]``: per input feature, the new bases no row reached.
+
+        ``adaptive=False``: every feature's new knot row is uniform over its current inner range ``[grid[f, k], grid[f, -k-1]]`` (or
+        ``grid_range``), extended by ``k`` steps either side as the constructor does; a layer on one shared uniform row stays on one
+        (and so on the split / sparse kernels).  Only rows inside the new inner range take part in the fit: beyond it the finer
+        space cannot represent the old curve, and the misfit of such rows would leak into the range (6e-2 of the function for
+        0.8 randn inputs on [-1, 1], against 4e-8 with the window).  ``adaptive=True``: ``update_grid``'s quantile knots (``grid_eps``,
+        ``margin``) at the new size, every row taking part.
+
+        The UNSCALED coefficients are fitted and ``spline_scaler`` is kept: the scaling is linear per edge, so the layer's function
+        is kept (``update_grid`` folds the scaler into the fit and keeps it too, as the reference does; that is not copied here).
+        ``grid`` and ``spline_weight`` become NEW tensors of the new shapes: an optimizer built on the old Parameter must be rebuilt."""
+        assert x.dim() == 2 and x.size(1) == self.in_features
+        k, g_new = self.spline_order, int(grid_size)
+        if ops.high_order(k):
+            raise NotImplementedError("refine is not implemented at spline_order above 4: like update_grid's, the least-squares refit "
+                                      "of the coefficients is ill-conditioned at these orders (the reference's own fp64 refit loses "
+                                      "the function from order 12)")
+        if g_new < 1 or g_new + 2 * k + 1 > ops.MAX_KNOTS:
+            raise ValueError(f"refine: grid_size must be >= 1 with grid_size + 2 * spline_order + 1 <= {ops.MAX_KNOTS} "
+                             f"(got {grid_size} at spline_order {k})")
+        ops._need_cuda(x, self.grid, self.spline_weight)
+        dev = x.device
+        if adaptive:
+            new_grid, window = self._quantile_knots(x, g_new, margin), None
+        else:
+            steps = torch.arange(-k, g_new + k + 1)
+            if grid_range is not None or self._knots().dim() == 1:        # one shared uniform row, built as the constructor builds it
+                lo, hi = (float(self.grid[0, k]), float(self.grid[0, -k - 1])) if grid_range is None else (float(grid_range[0]), float(grid_range[1]))
+                if not hi > lo:
+                    raise ValueError("refine: grid_range must be increasing")
+                row = steps * ((hi - lo) / g_new) + lo
+                new_grid = row.to(device=dev, dtype=torch.float32).expand(self.in_features, -1).contiguous()
+            else:                                                           # per-feature rows: each over its own inner range
+                lo, hi = self.grid[:, k].float(), self.grid[:, -k - 1].float()
+                new_grid = (lo.unsqueeze(1) + steps.to(dev).float().unsqueeze(0) * ((hi - lo) / g_new).unsqueeze(1)).contiguous()
+            window = torch.stack([new_grid[:, k], new_grid[:, -k - 1]], dim=1).contiguous()
+        fitted, untouched = ops.kan_grid_resize(x, self.grid, new_grid, self.spline_weight, None, self.grid_size, g_new, k, window)
+        old = self.spline_weight
+        self.grid = new_grid.to(self.grid.dtype)
+        self.spline_weight = nn.Parameter(fitted.to(old.dtype), requires_grad=old.requires_grad)
+        self.grid_size = g_new
+        self._knots_key = None
+        self._knots_row = None
+        return untouched
 
     @torch.no_grad()
     def _refit_wide(self, x: torch.Tensor, new_grid: torch.Tensor, scaler) -> torch.Tensor:
@@ -277,6 +336,18 @@ class KAN(nn.Module):
             x = layer(x) if packs is None else layer(x, _packed=packs[i])
         return x
 
+    @torch.no_grad()
+    def refine(self, x: torch.Tensor, grid_size: int, adaptive: bool = False, grid_range=None, margin=0.01) -> List[torch.Tensor]:
+        """``KANLinear.refine`` of every layer on its own input (``x`` is the chain's): each layer is refined, then evaluated
+        refined for the next one.  Returns the layers' ``untouched`` counts."""
+        out = []
+        for i, layer in enumerate(self.layers):
+            out.append(layer.refine(x, grid_size, adaptive=adaptive, grid_range=grid_range, margin=margin))
+            if i + 1 < len(self.layers):
+                x = layer._forward(x)
+        self.grid_size = int(grid_size)
+        return out
+
     def _pack_chain(self, x):
         """all layers' weight packs in one launch when the chain runs on the sparse-forward / split kernels"""
         first = self.layers[0]
@@ -339,3 +410,72 @@ def collect_edge_l1(model: nn.Module):
         yield entry[1]
     finally:
         active.remove(entry)
+
+
+class _RefineWalk:
+    """the state of one ``refine_grids`` call: which layers to refine, how, and what happened"""
+
+    def __init__(self, names, grid_size, adaptive, keep_inputs):
+        self.names, self.grid_size, self.adaptive, self.keep_inputs = names, int(grid_size), adaptive, keep_inputs
+        self.report: Dict[str, dict] = {}
+
+    def visit(self, layer: KANLinear, x: torch.Tensor) -> None:
+        name = self.names.get(id(layer))
+        if name is None or name in self.report:           # not under the model, or already refined on its first input
+            return
+        rows = x.detach() if x.dtype == torch.float32 else x.detach().float()
+        old = layer.grid_size
+        untouched = layer.refine(rows, self.grid_size, adaptive=self.adaptive)
+        entry = {"grid_size": (old, self.grid_size), "rows": rows.size(0), "untouched": untouched}
+        if self.keep_inputs:
+            entry["input"] = rows.clone()
+        self.report[name] = entry
+
+
+def refine_grids(model: nn.Module, grid_size: int, *args, adaptive: bool = False, keep_inputs: bool = False, **kwargs) -> dict:
+    """Grid extension for a whole model: ONE forward ``model(*args, **kwargs)`` under ``no_grad`` in eval mode (no dropout, no
+    running statistics move; the ``training`` flags are restored), during which every ``KANLinear`` of spline order <= 4 under
+    ``model`` is refined to ``grid_size`` (``KANLinear.refine``) on the first input it sees, BEFORE it evaluates that input -- so
+    every layer downstream is fitted on what the refined layers upstream produce, as in ``KAN.forward(update_grid=True)``.  As
+    inside a ``collect_edge_l1`` block, the fused layer / stack / model routes take their composed per-layer form for this one
+    forward (``ops.layer_inputs_visible``).  Wrapper modules that mirror ``grid_size`` (``KAN``) follow their layers.
+
+    Returns ``{module name: {"grid_size": (old, new), "rows": N, "untouched": int32 [in], "input": x if keep_inputs}}`` plus
+    ``"skipped"``: the names of the ``KANLinear`` layers of order 5..16 and of the ``FastKANLayer`` s, which are left as they are (and
+    of layers the forward never reached).  ``grid`` and ``spline_weight`` of every refined layer are NEW tensors: build a new optimizer."""
+    from .fastkan import FastKANLayer
+    if ops._refine_walk() is not None:
+        raise RuntimeError("refine_grids is already running on this thread")
+    names, skipped = {}, []
+    for n, m in model.named_modules():
+        if isinstance(m, KANLinear) and not ops.high_order(m.spline_order):
+            names[id(m)] = n
+        elif isinstance(m, (KANLinear, FastKANLayer)):
+            skipped.append(n)
+    k_max = max((m.spline_order for m in model.modules() if id(m) in names), default=1)
+    if int(grid_size) < 1 or int(grid_size) + 2 * k_max + 1 > ops.MAX_KNOTS:
+        raise ValueError(f"refine_grids: grid_size must be >= 1 with grid_size + 2 * spline_order + 1 <= {ops.MAX_KNOTS} (got {grid_size})")
+    walk = _RefineWalk(names, grid_size, adaptive, keep_inputs)
+    flags = [(m, m.training) for m in model.modules()]
+    model.eval()
+    ops._set_refine_walk(walk)
+    try:
+        with torch.no_grad():
+            model(*args, **kwargs)
+    finally:
+        ops._set_refine_walk(None)
+        for m, flag in flags:
+            m.training = flag
+        # everything derived from the old shapes or parameters: the knot comparisons and the graph-level model call's template
+        ops._KNOTS_EQUAL.clear()
+        for m in model.modules():
+            m.__dict__.pop("_kagnn_model_call_template", None)
+    for n, m in model.named_modules():                    # wrappers that mirror their layers' grid_size
+        if isinstance(m, (KANLinear, FastKANLayer)) or not isinstance(getattr(m, "grid_size", None), int):
+            continue
+        below = [walk.report.get(names.get(id(l))) for l in m.modules() if isinstance(l, KANLinear)]
+        if below and all(e is not None for e in below):
+            m.grid_size = int(grid_size)
+    report = dict(walk.report)
+    report["skipped"] = skipped + [n for n in names.values() if n not in walk.report]
+    return report

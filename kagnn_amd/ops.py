@@ -1819,6 +1819,48 @@ def kan_grid_refit(x, grid_old, grid_new, spline_weight, spline_scaler, grid_siz
     return out
 
 
+MAX_KNOTS = 48                     # grid_size + 2 * spline_order + 1 at orders 1..4 (kMaxKnots of the kernels)
+
+
+def kan_grid_resize(x, grid_old, grid_new, spline_weight, spline_scaler, grid_size_old: int, grid_size_new: int,
+                    spline_order: int, window=None):
+    """``kan_grid_refit`` between grids of TWO sizes (grid extension: a coarse grid's curves moved onto a finer one, or back):
+    ``grid_old [in, G_old+2k+1]``, ``grid_new [in, G_new+2k+1]``, ``spline_weight [out, in, G_old+k]``; returns
+    ``(new_spline_weight [out, in, G_new+k], untouched [in] int32)``.  ``window [in, 2]``: row ``n`` takes part in feature ``f``'s
+    fit only when ``window[f, 0] <= x[n, f] < window[f, 1]``.  ``untouched[f]``: the new bases of feature ``f`` no participating
+    row reached (their coefficients are 0).  Orders 1..4, ``G + 2k + 1 <= 48`` on either side."""
+    g0, g1, k = int(grid_size_old), int(grid_size_new), int(spline_order)
+    if high_order(k) or k < 1:
+        raise NotImplementedError(f"kan_grid_resize: spline_order must be in 1..{FUSED_MAX_SPLINE_ORDER} (got {spline_order})")
+    for g in (g0, g1):
+        if g < 1 or g + 2 * k + 1 > MAX_KNOTS:
+            raise ValueError(f"kan_grid_resize: grid_size must be >= 1 with grid_size + 2 * spline_order + 1 <= {MAX_KNOTS} (got {g} at order {k})")
+    _need_cuda(x, grid_old, grid_new, spline_weight, spline_scaler, window)
+    x = _rows(x.detach())
+    n, fin = x.shape
+    fout = spline_weight.size(0)
+    if n < 1:
+        raise ValueError("kan_grid_resize: no rows to fit on")
+    go = grid_old.detach().to(torch.float32).contiguous()
+    gn = grid_new.detach().to(torch.float32).contiguous()
+    if go.shape != (fin, g0 + 2 * k + 1) or gn.shape != (fin, g1 + 2 * k + 1):
+        raise AssertionError("grids must be [in_features, G+2k+1]")
+    if tuple(spline_weight.shape) != (fout, fin, g0 + k):
+        raise AssertionError("spline_weight must be [out_features, in_features, G_old+k]")
+    sw = spline_weight.detach().to(torch.float32).contiguous()
+    sc = None if spline_scaler is None else spline_scaler.detach().to(torch.float32).contiguous()
+    win = None if window is None else window.detach().to(torch.float32).contiguous()
+    if win is not None and win.shape != (fin, 2):
+        raise AssertionError("window must be [in_features, 2]")
+    ws = _ws(_sizes("kagnn_kan_grid_resize_workspace_bytes", n, fin, g0, g1, k), x.device)
+    out = torch.empty((fout, fin, g1 + k), dtype=torch.float32, device=x.device)
+    untouched = torch.empty((fin,), dtype=torch.int32, device=x.device)
+    with _device_of(x):
+        _call("kagnn_kan_grid_resize", _ptr(x), _ld(x), n, _ptr(go), _ptr(gn), _ptr(win), fin, fout, g0, g1, k, _ptr(sw), _ptr(sc),
+              _ptr(out), _ptr(untouched), _ptr(ws), ws.numel(), _stream())
+    return out, untouched
+
+
 # ======================================================================== per-edge activations (kan_edge.hip)
 # phi_{o,i}(t) = base_weight[o,i] silu(t) + spline_scaler[o,i] sum_c spline_weight[o,i,c] B_c(t): what a KAN user inspects and
 # regularises.  Exact fp32 in every precision mode; spline orders 1..FUSED_MAX_SPLINE_ORDER.
@@ -1839,7 +1881,17 @@ def layer_inputs_visible() -> bool:
     """True inside a ``kagnn_amd.collect_edge_l1`` block of the calling thread: every route that hides a KANLinear's input from ``KANLinear.forward``
     (the fused layer / stack / model nodes, the chain pack, the concatenation-free read-out) then takes its composed
     per-layer form, so each layer sees -- and can take statistics of -- its own input."""
-    return bool(getattr(_EDGE_STATE, "collectors", None))
+    return bool(getattr(_EDGE_STATE, "collectors", None)) or getattr(_EDGE_STATE, "refine", None) is not None
+
+
+def _refine_walk():
+    """the ``kagnn_amd.refine_grids`` walk open on THIS thread, or None.  While one is open ``layer_inputs_visible()`` holds, exactly
+    as inside a ``collect_edge_l1`` block: every KANLinear.forward sees its own input and refines itself on it first."""
+    return getattr(_EDGE_STATE, "refine", None)
+
+
+def _set_refine_walk(walk) -> None:
+    _EDGE_STATE.refine = walk
 
 
 def _edge_operands(what, rows, base_weight, spline_weight, spline_scaler, knots, grid_size, spline_order):
