@@ -84,7 +84,7 @@ using namespace kagnn;
 #pragma GCC visibility push(default)
 extern "C" {
 
-int kagnn_version(void) { return 272; }
+int kagnn_version(void) { return 273; }
 const char* kagnn_last_error(void) { return g_err; }
 
 int kagnn_stage_timer_enable(const char* only) {
@@ -577,7 +577,7 @@ int kagnn_kan_grid_refit_workspace_bytes(int64_t N, int32_t in, int32_t G, int32
     int rc = check_kan_dims(__func__, in, 1, G, K, KAGNN_PREC_FP32_GRID);
     if (rc) return rc;
     KAGNN_CHECK_ARG(bytes != nullptr && N >= 1, "null output or no rows");
-    *bytes = kan_grid_refit_ws_bytes(N, in);
+    *bytes = kan_grid_resize_ws_bytes(N, in, G + K, G + K);
     return KAGNN_OK;
 }
 
@@ -589,10 +589,12 @@ int kagnn_kan_grid_refit(const float* x, int64_t ldx, int64_t N, const float* gr
     KAGNN_CHECK_ARG(N >= 1 && ldx >= in, "bad shape");
     KAGNN_CHECK_ARG(x && grid_old && grid_new && sw && new_sw && ws, "null array");
     KAGNN_CHECK_ARG(sw != new_sw, "the refit is not in place");
-    return kan_grid_refit(x, ldx, N, grid_old, grid_new, in, out, G, K, sw, sc, new_sw, ws, ws_bytes, as_stream(stream));
+    return kan_grid_resize(x, ldx, N, grid_old, grid_new, nullptr, in, out, G, G, K, sw, sc, new_sw, nullptr, ws, ws_bytes,
+                           as_stream(stream));
 }
 
-// grid resize: the refit between grids of two sizes (grid extension), up to kMaxKnots knots on either side
+// grid resize: the refit between grids of two sizes (grid extension), up to kMaxKnots knots on either side; the two calls above
+// are this one with equal sizes, every row taking part
 int kagnn_kan_grid_resize_workspace_bytes(int64_t N, int32_t in, int32_t G_old, int32_t G_new, int32_t K, size_t* bytes) {
     int rc = check_kan_dims(__func__, in, 1, G_old, K, KAGNN_PREC_FP32_GRID);
     if (!rc) rc = check_kan_dims(__func__, in, 1, G_new, K, KAGNN_PREC_FP32_GRID);

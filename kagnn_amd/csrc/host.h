@@ -210,9 +210,6 @@ int gat_att_grad(const float* xh, long ld, const float* g_src, const float* g_ds
 
 // ---- kan_grid.hip
 int kan_bsplines(const float* x, long ldx, long N, const float* grid, int in, int G, int K, float* bases, hipStream_t st);
-size_t kan_grid_refit_ws_bytes(long N, int in);
-int kan_grid_refit(const float* x, long ldx, long N, const float* grid_old, const float* grid_new, int in, int out, int G, int K,
-                   const float* sw, const float* sc, float* new_sw, void* ws, size_t ws_bytes, hipStream_t st);
 size_t kan_grid_resize_ws_bytes(long N, int in, int Cn, int Co);
 int kan_grid_resize(const float* x, long ldx, long N, const float* grid_old, const float* grid_new, const float* window, int in,
                     int out, int G_old, int G_new, int K, const float* sw, const float* sc, float* new_sw, int* untouched, void* ws,

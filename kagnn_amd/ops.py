@@ -1802,21 +1802,9 @@ def kan_bsplines(x, grid, grid_size: int, spline_order: int) -> torch.Tensor:
 def kan_grid_refit(x, grid_old, grid_new, spline_weight, spline_scaler, grid_size: int,
                    spline_order: int) -> torch.Tensor:
     """Coefficients on ``grid_new`` that reproduce, in the least-squares sense over the rows of ``x``, the
-    per-feature curves the layer had on ``grid_old`` (the refit inside ``update_grid``, ekan.py:169-177,211)."""
-    _need_cuda(x, grid_old, grid_new, spline_weight, spline_scaler)
-    x = _rows(x.detach())
-    n, fin = x.shape
-    fout = spline_weight.size(0)
-    go = grid_old.detach().to(torch.float32).contiguous()
-    gn = grid_new.detach().to(torch.float32).contiguous()
-    sw = spline_weight.detach().contiguous()
-    sc = None if spline_scaler is None else spline_scaler.detach().contiguous()
-    ws = _ws(_sizes("kagnn_kan_grid_refit_workspace_bytes", n, fin, int(grid_size), int(spline_order)), x.device)
-    out = torch.empty_like(sw)
-    with _device_of(x):
-        _call("kagnn_kan_grid_refit", _ptr(x), _ld(x), n, _ptr(go), _ptr(gn), fin, fout, int(grid_size),
-              int(spline_order), _ptr(sw), _ptr(sc), _ptr(out), _ptr(ws), ws.numel(), _stream())
-    return out
+    per-feature curves the layer had on ``grid_old`` (the refit inside ``update_grid``, ekan.py:169-177,211):
+    ``kan_grid_resize`` between two grids of one size, every row taking part."""
+    return kan_grid_resize(x, grid_old, grid_new, spline_weight, spline_scaler, grid_size, grid_size, spline_order, window=None)[0]
 
 
 MAX_KNOTS = 48                     # grid_size + 2 * spline_order + 1 at orders 1..4 (kMaxKnots of the kernels)
@@ -1824,7 +1812,8 @@ MAX_KNOTS = 48                     # grid_size + 2 * spline_order + 1 at orders 
 
 def kan_grid_resize(x, grid_old, grid_new, spline_weight, spline_scaler, grid_size_old: int, grid_size_new: int,
                     spline_order: int, window=None):
-    """``kan_grid_refit`` between grids of TWO sizes (grid extension: a coarse grid's curves moved onto a finer one, or back):
+    """The least-squares coefficient refit between grids of TWO sizes (grid extension: a coarse grid's curves moved onto a finer one,
+    or back; ``kan_grid_refit`` is the equal-size case):
     ``grid_old [in, G_old+2k+1]``, ``grid_new [in, G_new+2k+1]``, ``spline_weight [out, in, G_old+k]``; returns
     ``(new_spline_weight [out, in, G_new+k], untouched [in] int32)``.  ``window [in, 2]``: row ``n`` takes part in feature ``f``'s
     fit only when ``window[f, 0] <= x[n, f] < window[f, 1]``.  ``untouched[f]``: the new bases of feature ``f`` no participating

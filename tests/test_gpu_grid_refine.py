@@ -223,6 +223,23 @@ def test_column_slice_and_second_call_give_the_same_bits():
     assert torch.equal(first, sliced) and torch.equal(u1, u3)
 
 
+@pytest.mark.parametrize("n,fin,fout,g,k,scaler", [(300, 4, 3, 5, 3, True), (300, 3, 2, 20, 3, False)],      # 8 coefficients; 23: two 16-blocks
+                         ids=["300x4-3_G5_k3_scaler", "300x3-2_G20_k3"])
+def test_refit_is_the_resize_between_two_grids_of_one_size(n, fin, fout, g, k, scaler):
+    """``ops.kan_grid_refit`` (what ``update_grid`` calls) and ``ops.kan_grid_resize`` with equal sizes and no window: one arithmetic,
+    the same bits.  The new knots are per-feature rows, each knot moved by up to 0.3 of a step."""
+    c = make_case(n, fin, fout, g, g, k, dist="randn", scaler=scaler)
+    assert (c.sc is not None and bool((c.sc < 0).any())) == scaler
+    step = float(c.gn[0, 1] - c.gn[0, 0])
+    c.gn = c.gn + 0.3 * step * (2 * torch.rand(c.gn.shape, generator=torch.Generator().manual_seed(g)) - 1)
+    assert bool((c.gn[:, 1:] > c.gn[:, :-1]).all()) and not torch.equal(c.gn[0], c.gn[1])
+    d = lambda t: None if t is None else t.to(DEV)
+    refit = ops.kan_grid_refit(d(c.x), d(c.go), d(c.gn), d(c.sw), d(c.sc), g, k)
+    resized, _ = device_fit(c)
+    assert refit.shape == (fout, fin, g + k) and bool(torch.isfinite(refit).all())
+    assert torch.equal(refit, resized)
+
+
 def test_bases_no_sample_reaches_get_zero_and_are_counted():
     c = make_case(4000, 4, 3, 5, 20, 3)
     c.x = -0.99 * torch.rand(c.n, c.fin, generator=torch.Generator().manual_seed(5))            # half the range: (-0.99, 0]

@@ -1405,9 +1405,10 @@ def test_update_grid_golden(golden):
             layer.load_state_dict({n: v for n, v in p.items()})
 
 
-# (the last two: MORE than 16 coefficients -- the reference's searches reach grid_size 32, ekan.py:164-211 has no limit; KANLinear._refit_wide, round 6)
+# (the last four: MORE than 16 coefficients, two and three 16-blocks of the Gram matrices -- the reference's searches reach grid_size 32,
+# ekan.py:164-211 has no limit; 43 coefficients on 47 knots, and 46 on 48, the limit of orders 1..4)
 @pytest.mark.parametrize("n,fi,fo,G,k", [(20000, 16, 8, 5, 3), (3001, 70, 5, 8, 3), (17, 3, 2, 3, 2), (5000, 4, 40, 12, 4),
-                                         (9000, 6, 5, 20, 3), (12000, 3, 4, 32, 3)])
+                                         (9000, 6, 5, 20, 3), (12000, 3, 4, 32, 3), (12000, 3, 4, 40, 3), (12000, 2, 2, 45, 1)])
 def test_update_grid_vs_oracle(n, fi, fo, G, k):
     torch.manual_seed(n)
     layer = kagnn_amd.KANLinear(fi, fo, grid_size=G, spline_order=k)

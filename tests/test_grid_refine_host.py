@@ -43,6 +43,19 @@ def test_size_query():
     assert lib.kagnn_kan_grid_resize_workspace_bytes(1000, 8, 5, 10, 3, None) != 0
 
 
+def test_one_size_query():
+    """``kagnn_kan_grid_refit`` is the resize between two grids of one size: its size query answers what the resize's does"""
+    lib = _lib.load()
+    refit = ctypes.c_size_t(0)
+    for n, fin, g, k in [(1000, 8, 5, 3), (1000, 8, 32, 3), (100000, 64, 13, 3), (1, 1, 1, 1)]:
+        rc, nbytes = _query(lib, n, fin, g, g, k)
+        assert rc == 0 and nbytes > 0, (n, fin, g, k)
+        assert lib.kagnn_kan_grid_refit_workspace_bytes(n, fin, g, k, ctypes.byref(refit)) == 0, (n, fin, g, k)
+        assert refit.value == nbytes, (n, fin, g, k)
+    rc = lib.kagnn_kan_grid_refit_workspace_bytes(1000, 8, 42, 3, ctypes.byref(refit))          # 49 knots
+    assert rc == _query(lib, 1000, 8, 42, 42, 3)[0] == -3                                         # KAGNN_ERR_UNSUPPORTED
+
+
 def test_a_finer_grid_needs_more_workspace_but_nothing_per_row():
     lib = _lib.load()
     small, big = _query(lib, 4096, 8, 5, 10, 3)[1], _query(lib, 4096, 8, 8, 40, 3)[1]

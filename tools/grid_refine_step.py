@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """What a grid refinement costs: `ops.kan_grid_resize` (csrc/kan_grid.hip) at a KAN-GNN layer's shape (64 -> 64, order 3, N = 2^20 rows)
-for 5 -> 10 and 8 -> 40, beside the only route the package had for more than 16 coefficients: the arithmetic of
-`KANLinear._refit_wide` -- dense bases from `ops.kan_bsplines` 8192 rows at a time, fp64 `einsum` Gram matrices on the device, a
-minimum-norm `lstsq` on the host -- run on the same inputs with the two grid sizes.
+for 5 -> 10 and 8 -> 40, beside the same normal equations composed from the package's other calls (`composed_resize`): dense bases
+from `ops.kan_bsplines` 8192 rows at a time, fp64 `einsum` Gram matrices on the device, a minimum-norm `lstsq` on the host -- run
+on the same inputs with the two grid sizes.
 
     python tools/grid_refine_step.py [--rows 1048576] [--width 64] [--order 3] [--pairs 5:10,8:40] [--json out.json]
 
@@ -29,7 +29,7 @@ from kagnn_amd import ops                          # noqa: E402
 
 
 def composed_resize(x, grid_old, grid_new, sw, g0, g1, k, chunk=8192):
-    """`KANLinear._refit_wide` with two grid sizes: [chunk, in, C] dense bases, fp64 einsum, host solve"""
+    """the comparison route: [chunk, in, C] dense bases, fp64 einsum Gram matrices, host solve"""
     fin = x.size(1)
     a = torch.zeros((fin, g1 + k, g1 + k), dtype=torch.float64, device=x.device)
     b = torch.zeros((fin, g1 + k, g0 + k), dtype=torch.float64, device=x.device)
