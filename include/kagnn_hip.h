@@ -147,6 +147,25 @@ int kagnn_aggregate_sum_add(const float* x, int64_t ldx, float* out, int64_t ldo
                             const float* addend, int64_t ld_addend,
                             void* workspace, size_t workspace_bytes, void* stream);
 
+/* Gradient of that aggregation with respect to its EDGE WEIGHTS (torch_geometric's GCNConv differentiates through `edge_weight`;
+ * GNNExplainer's edge mask, learned edge weights): for every CSR position e of row i, j = col[e],
+ *
+ *   g_edge_weight[perm ? perm[e] : e] = out_scale[i] * s(j) * < gout[i, :num_feat], x[j, :num_feat] >
+ *
+ * exactly 0 where `skip_self_loops` and j == i; NULL scales = 1.  `x` is the matrix the forward gathered, `gout` the gradient of
+ * its result, `rowptr / col / perm / hub_seg` the by-destination structure of kagnn_csr_build (`perm` NULL: CSR order).  fp32,
+ * every width and leading dimension kagnn_aggregate_sum takes (float4 rows where num_feat % 4 == 0, num_feat <= 256 and both
+ * operands are 16-byte aligned with leading dimensions % 4 == 0; a scalar kernel otherwise).  `perm` is a permutation, so every
+ * output element is written once: no atomics, no workspace, a fixed reduction order -- bit-reproducible run to run.  Rows above
+ * `hub_threshold` edges run through their hub segments (one workgroup each).  num_nodes == 0 or num_edges == 0: nothing is
+ * launched.                                                                                                                    */
+int kagnn_aggregate_edge_grad(const float* x, int64_t ldx, const float* gout, int64_t ldg,
+                              const int32_t* rowptr, const int32_t* col, const int32_t* perm,
+                              int64_t num_nodes, int64_t num_edges, int32_t num_feat,
+                              const float* in_scale, const float* out_scale, int32_t skip_self_loops,
+                              const int32_t* hub_seg, int64_t num_hub_seg, int32_t hub_threshold,
+                              float* g_edge_weight, void* stream);
+
 /* The same aggregation with bf16 GATHER OPERANDS (`KAGNN_ACT=bf16`; BASELINE.json config 2 -- the reference has no
  * reduced-precision path, SURVEY.md 8(d) makes this a build-defined mode): `x` rows are bf16 (leading dimension in
  * ELEMENTS, a multiple of 8; 16-byte aligned), sums are accumulated in fp32 and written as fp32 (`out_dtype` =

@@ -43,6 +43,9 @@ _SIGNATURES = {
                                       _P, _P, _P, c_int32, _P, c_int64, c_int32, _P, c_size_t, _P]),
     "kagnn_aggregate_sum_add": (c_int32, [_P, c_int64, _P, c_int64, _P, _P, _P, c_int64, c_int32, c_float,
                                           _P, _P, _P, c_int32, _P, c_int64, c_int32, _P, c_int64, _P, c_size_t, _P]),
+    # x ldx gout ldg rowptr col perm N E F in_scale out_scale skip_self hub_seg nseg hub_threshold g_edge_weight stream
+    "kagnn_aggregate_edge_grad": (c_int32, [_P, c_int64, _P, c_int64, _P, _P, _P, c_int64, c_int64, c_int32, _P, _P, c_int32,
+                                            _P, c_int64, c_int32, _P, _P]),
     "kagnn_aggregate_sum_bf16": (c_int32, [_P, c_int64, _P, c_int64, c_int32, _P, _P, _P, c_int64, c_int32, c_float,
                                            _P, _P, _P, c_int32, _P, c_int64, c_int32, _P, c_size_t, _P]),
     "kagnn_rows_to_bf16": (c_int32, [_P, c_int64, _P, c_int64, c_int64, c_int32, _P]),

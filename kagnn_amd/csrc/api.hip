@@ -84,7 +84,7 @@ using namespace kagnn;
 #pragma GCC visibility push(default)
 extern "C" {
 
-int kagnn_version(void) { return 273; }
+int kagnn_version(void) { return 274; }
 const char* kagnn_last_error(void) { return g_err; }
 
 int kagnn_stage_timer_enable(const char* only) {
@@ -212,6 +212,23 @@ int kagnn_aggregate_sum_affine(const float* x, int64_t ldx, float* out, int64_t 
               0, hub_threshold > 0 ? hub_threshold : 0x7fffffff, addend, ld_addend};
     a.col_scale = col_scale; a.col_shift = col_shift;
     return aggregate_sum(a, hub_seg, num_hub_seg, static_cast<float*>(workspace), workspace_bytes, as_stream(stream));
+}
+
+// d loss / d edge_weight of kagnn_aggregate_sum (aggregate_edge.hip): one value per CSR position, written to ORIGINAL edge order
+// through `perm` (NULL: CSR order).  fp32 only.
+int kagnn_aggregate_edge_grad(const float* x, int64_t ldx, const float* gout, int64_t ldg, const int32_t* rowptr, const int32_t* col,
+                              const int32_t* perm, int64_t N, int64_t E, int32_t F, const float* in_scale, const float* out_scale,
+                              int32_t skip_self_loops, const int32_t* hub_seg, int64_t num_hub_seg, int32_t hub_threshold,
+                              float* g_edge_weight, void* stream) {
+    KAGNN_STAGE(stream);
+    KAGNN_CHECK_ARG(N >= 0 && E >= 0 && F >= 1 && N < 2147483647LL && E < 2147483647LL && num_hub_seg >= 0, "bad shape");
+    KAGNN_CHECK_ARG(ldx >= F && ldg >= F, "leading dimension smaller than num_feat");
+    if (N == 0 || E == 0) return KAGNN_OK;
+    KAGNN_CHECK_ARG(x && gout && rowptr && col && g_edge_weight, "null array");
+    KAGNN_CHECK_ARG(num_hub_seg == 0 || hub_seg, "hub segments counted but not given");
+    EdgeGradArgs a{x, ldx, gout, ldg, rowptr, col, perm, N, E, F, in_scale, out_scale, skip_self_loops,
+                   hub_threshold > 0 ? hub_threshold : 0x7fffffff, g_edge_weight};
+    return aggregate_edge_grad(a, hub_seg, num_hub_seg, as_stream(stream));
 }
 
 int kagnn_aggregate_sum_bf16(const void* x, int64_t ldx, void* out, int64_t ldo, int32_t out_dtype, const int32_t* rowptr,

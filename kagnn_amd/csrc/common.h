@@ -272,6 +272,18 @@ struct AggArgs {
     float* st_partial = nullptr;
 };
 
+// arguments of the edge-weight gradient of that aggregation (aggregate_edge.hip): for CSR position e of row i, j = col[e],
+//   out[perm ? perm[e] : e] = out_scale[i] * in_scale[j] * <gout[i, :F], x[j, :F]>      (0 where skip_self && j == i; null scale = 1)
+struct EdgeGradArgs {
+    const float* x; long ldx;
+    const float* gout; long ldg;
+    const int* rowptr; const int* col; const int* perm;
+    long N; long E; int F;
+    const float* in_scale; const float* out_scale;
+    int skip_self; int hub_threshold;
+    float* out;                        // [E]
+};
+
 // BatchNorm1d backward, training mode, as ONE expression per element of the incoming gradient g (y = the norm's input):
 //   gy = k (g - mean(g) - xhat mean(g xhat)),  xhat = (y - m) q,  k = gamma q     ==>  gy = A g + B (y - m) + C
 // with per column  A = k,  B = -k q mean(g xhat),  C = -k mean(g)  (bn_finish_table_kernel, bn.hip).  The deviation y - m is

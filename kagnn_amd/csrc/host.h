@@ -30,6 +30,9 @@ size_t embedding_bwd_ws_bytes(long N, int V, int F);
 
 int aggregate_hub_rows(const AggArgs& a, const int* hub_seg, long num_hub_seg, float* ws, size_t ws_bytes, hipStream_t st);
 
+// ---- aggregate_edge.hip
+int aggregate_edge_grad(const EdgeGradArgs& a, const int* hub_seg, long num_hub_seg, hipStream_t st);
+
 // ---- aggregate_bf16.hip
 size_t aggregate_bf16_ws_bytes(long num_hub_seg, int F);
 bool aggregate_bf16_ok(const void* x, long ldx, const void* out, long ldo, int out_bf16, int F, const float* bias);

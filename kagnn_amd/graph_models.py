@@ -103,6 +103,8 @@ FASTKAGAT_Layer = FASTKAGATConv
 
 class _GraphLevel(nn.Module):
     def _message_passing(self, x, g, edge_attr=None):
+        if edge_attr is not None and ops.aggregation_visible():
+            raise NotImplementedError("edge_mask: the GINE convolutions are not supported inside the block")
         # GINE stacks (graph_regression/models.py:107-119): all convolutions + norms as ONE tape node where the shapes allow it
         if (edge_attr is not None and self.training and not (self.dropout.p > 0.0) and all(isinstance(c, GINEKANLayer) for c in self.conv)
                 and all(type(b) is BatchNorm1d for b in self.bn) and not any(_has_hooks(m) for m in list(self.conv) + list(self.bn))):
@@ -172,10 +174,14 @@ class GINEKANLayer(nn.Module):
     def forward_fused_norm(self, x, edge_index, edge_attr, bn):
         """``bn(self(x, edge_index, edge_attr))`` for a training-mode BatchNorm1d as ONE tape node (``graph_ops._GineKanLayerFn``: one
         library call each way), or ``None`` when the chain is outside what the node covers -- nothing has been touched then."""
+        if ops.aggregation_visible():
+            raise NotImplementedError("edge_mask: the GINE convolutions are not supported inside the block")
         g = edge_index if isinstance(edge_index, ops.GraphIndex) else ops.graph_index(edge_index, x.size(0))
         return graph_ops.gine_kan_layer(x, edge_attr, g, 1.0 + self._eps(), self.nn, batch_norm=bn)
 
     def forward(self, x, edge_index, edge_attr):
+        if ops.aggregation_visible():
+            raise NotImplementedError("edge_mask: the GINE convolutions are not supported inside the block")
         g = edge_index if isinstance(edge_index, ops.GraphIndex) else ops.graph_index(edge_index, x.size(0))
         y = graph_ops.gine_kan_layer(x, edge_attr, g, 1.0 + self._eps(), self.nn)          # one tape node: aggregate + KAN chain
         if y is not None:
@@ -202,7 +208,8 @@ class KAGINRegression(_GraphLevel):
         self.dropout = nn.Dropout(dropout)
 
     def forward(self, data):
-        if type(self) is KAGINRegression:                 # the whole forward as ONE tape node where the model and the batch allow it
+        if type(self) is KAGINRegression and not ops.aggregation_visible():     # (an edge_mask block: _message_passing refuses)
+            # the whole forward as ONE tape node where the model and the batch allow it
             out = graph_ops.kagin_regression_forward(self, data)
             if out is not None:
                 return out

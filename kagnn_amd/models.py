@@ -122,6 +122,9 @@ class _SumAggregateConv(nn.Module):
 
     def forward(self, x: torch.Tensor, edge_index: torch.Tensor) -> torch.Tensor:
         g = edge_index if isinstance(edge_index, ops.GraphIndex) else ops.graph_index(edge_index, x.size(0))
+        mask = ops.edge_mask_of(g)
+        if mask is not None:          # a kagnn_amd.edge_mask block: the message of edge e times mask[e], the self term as it is
+            return self.nn(ops.aggregate_sum(x, g, self_scale=1.0 + self._eps(), edge_weight=mask))
         if _FUSED_LAYER and isinstance(self.nn, eKAN) and x.is_cuda and x.size(0) > 0 and not torch.compiler.is_compiling():
             want = self.__dict__.get("_want_moments", False) and x.size(0) > 1
             y = ops.gin_kan_layer(x, g, 1.0 + self._eps(), self.nn, moments=want,    # one tape node: aggregate + KAN chain
@@ -149,7 +152,22 @@ class _NormalisedConv(nn.Module):
 
     def forward(self, x: torch.Tensor, edge_index: torch.Tensor,
                 edge_weight: Optional[torch.Tensor] = None) -> torch.Tensor:
-        if edge_weight is not None or (isinstance(edge_index, torch.Tensor) and edge_index.is_sparse):
+        sparse = isinstance(edge_index, torch.Tensor) and edge_index.is_sparse
+        if ops.aggregation_visible():
+            # a kagnn_amd.edge_mask block (torch_geometric's explain hook): the normalisation is the UNMASKED graph's, the mask
+            # multiplies the messages of the original edges; the added self loops stay, loops in the edge list stay dropped
+            if sparse or edge_weight is not None:
+                raise NotImplementedError("edge_mask: a sparse adjacency or an explicit edge_weight is not supported inside the block")
+            g = edge_index if isinstance(edge_index, ops.GraphIndex) else ops.graph_index(edge_index, x.size(0))
+            mask = ops.edge_mask_of(g)
+            dis = g.gcn_dis
+            return ops.aggregate_sum(self.lin(x), g, self_scale=1.0, edge_weight=mask, in_scale=dis, out_scale=dis,
+                                     bias=self.bias, skip_self_loops=True)
+        if edge_weight is not None and edge_weight.requires_grad and not sparse and not torch.compiler.is_compiling():
+            # weights that want a gradient: the normalisation in differentiable torch ops, nothing cached (ops.gcn_norm_weights)
+            graph, w_hat = ops.gcn_norm_weights(edge_index, edge_weight, x.size(0))
+            return ops.aggregate_sum(self.lin(x), graph, self_scale=0.0, edge_weight=w_hat, bias=self.bias)
+        if edge_weight is not None or sparse:
             # weighted edges / the sparse adjacency of the reference's gcn timing branch (time_model.py:70-80)
             wg = ops.weighted_gcn_graph(edge_index, edge_weight, x.size(0))
             return ops.aggregate_sum(self.lin(x), wg.graph, self_scale=0.0, edge_weight=wg.weight,
@@ -181,6 +199,8 @@ class _AttentionConv(nn.Module):
         nn.init.xavier_uniform_(self.att_dst)
 
     def forward(self, x: torch.Tensor, edge_index: torch.Tensor) -> torch.Tensor:
+        if ops.aggregation_visible():
+            raise NotImplementedError("edge_mask: the attention convolutions are not supported inside the block")
         g = edge_index if isinstance(edge_index, ops.GraphIndex) else ops.graph_index(edge_index, x.size(0))
         return ops.gat_aggregate(self.lin(x), self.att_src, self.att_dst, self.bias, g, self.heads, self.out_channels)
 
@@ -321,7 +341,8 @@ class _NodeModel(nn.Module):
         # and the read-out's three kernels apply to the rows they load.  Only where every consumer can: the one-launch skip
         # read-out on the split-precision cubic kernels, <= 64 classes, blocks wider than 32 columns, dropout off (the
         # per-layer conditions -- training-mode norm, no hooks, fp32 rows -- are checked by conv_bn_dropout)
-        lazy = (_LAZY_NORM and split and x.is_cuda and not torch.compiler.is_compiling() and isinstance(self.lay_out, KANLinear) and self.lay_out.spline_order == 3
+        # (not inside a kagnn_amd.edge_mask block: the aggregation that folds the affine is unit-weight only)
+        lazy = (_LAZY_NORM and split and not ops.aggregation_visible() and x.is_cuda and not torch.compiler.is_compiling() and isinstance(self.lay_out, KANLinear) and self.lay_out.spline_order == 3
                 and self.lay_out.grid_size + 3 <= 8 and self.lay_out.out_features <= 64 and not (self.dropout.training and self.dropout.p > 0.0)
                 and all(bn.num_features > 32 for bn in self.bns)
                 and ops.split_like(self.lay_out.precision if self.lay_out.precision is not None else ops.default_precision()))

@@ -617,9 +617,40 @@ def _aggregate_csr(x, rowptr, col, hub, nhub, hub_threshold, self_scale, edge_we
     return out
 
 
+def aggregate_edge_grad(x, gout, g: GraphIndex, in_scale=None, out_scale=None, skip_self_loops: bool = False, out=None) -> torch.Tensor:
+    """d loss / d edge_weight of ``aggregate_sum(x, g, edge_weight=w, in_scale=, out_scale=, skip_self_loops=)`` given the gradient
+    ``gout`` of its result: ``[E]`` fp32 in ORIGINAL edge order, ``out_scale[dst] * in_scale[src] * <gout[dst], x[src]>`` per edge and
+    exactly 0 for a dropped self loop (``kagnn_aggregate_edge_grad``: no atomics, bit-reproducible).  Raw and non-differentiable:
+    ``aggregate_sum`` calls it in its backward when the weights require a gradient.  ``out``: write into the first ``E`` elements of
+    this contiguous fp32 vector instead of a new one."""
+    _need_cuda(x, gout, in_scale, out_scale, out)
+    x, gout = _rows(x.detach()), _rows(gout.detach())
+    n, f = x.shape
+    if n != g.num_nodes or gout.shape != x.shape:
+        raise ValueError(f"x {tuple(x.shape)} and gout {tuple(gout.shape)} must both be [{g.num_nodes}, F]")
+    scales = []
+    for s in (in_scale, out_scale):
+        if s is not None:
+            s = s.detach().to(torch.float32).contiguous()
+            if s.shape != (n,):
+                raise ValueError(f"in_scale / out_scale must be [{n}]")
+        scales.append(s)
+    e = g.num_edges
+    if out is None:
+        out = torch.empty(e, dtype=torch.float32, device=x.device)
+    elif out.dtype != torch.float32 or out.dim() != 1 or out.numel() < e or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous fp32 vector of at least {e} elements")
+    with _device_of(x):
+        _call("kagnn_aggregate_edge_grad", _ptr(x), _ld(x), _ptr(gout), _ld(gout), _ptr(g.rowptr), _ptr(g.col), _ptr(g.perm), n, e, f,
+              _ptr(scales[0]), _ptr(scales[1]), int(bool(skip_self_loops)), _ptr(g.hub_seg) if g.num_hub_seg else None, g.num_hub_seg,
+              g.hub_threshold, _ptr(out), _stream())
+    return out
+
+
 class _AggregateFn(Function):
     """out = out_scale * (self_scale*s*x_i + sum_e w_e * s_j * x_j) + bias over the by-dst CSR;
-    backward is the same kernel on the transposed CSR with in/out scales swapped."""
+    backward is the same kernel on the transposed CSR with in/out scales swapped, and -- only when the edge weights require a
+    gradient, the one case in which the gathered rows are kept -- ``aggregate_edge_grad`` for theirs."""
 
     @staticmethod
     @_on_operand_device
@@ -629,6 +660,12 @@ class _AggregateFn(Function):
         ctx.in_scale, ctx.out_scale = in_scale, out_scale
         ctx.edge_weight_t = None
         if edge_weight is not None:
+            if ctx.needs_input_grad[4]:
+                if edge_weight.shape != (g.num_edges,):
+                    raise ValueError(f"edge_weight must be [{g.num_edges}] to receive a gradient, got {tuple(edge_weight.shape)}")
+                rows = _rows(x, allow_bf16=True)
+                ctx.save_for_backward(rows if rows.dtype == torch.float32 else rows.float())    # (bf16 rows: the values that were summed)
+                ctx.edge_weight_dtype = edge_weight.dtype
             w = edge_weight.to(torch.float32)
             ctx.edge_weight_t = w[g.perm_t.long()].contiguous()
             edge_weight = w[g.perm.long()].contiguous()
@@ -639,13 +676,15 @@ class _AggregateFn(Function):
     @once_differentiable
     @_on_operand_device
     def backward(ctx, gout):
-        gx = gb = None
+        gx = gb = gw = None
         if ctx.needs_input_grad[0]:
             gx = _aggregate_raw(gout, ctx.g, True, ctx.self_scale, ctx.edge_weight_t, ctx.out_scale,
                                 ctx.in_scale, None, ctx.skip_self, out_dtype=ctx.x_dtype)
         if ctx.needs_input_grad[1]:
             gb = gout.sum(0)
-        return gx, gb, None, None, None, None, None, None
+        if ctx.needs_input_grad[4]:
+            gw = aggregate_edge_grad(ctx.saved_tensors[0], gout, ctx.g, ctx.in_scale, ctx.out_scale, ctx.skip_self).to(ctx.edge_weight_dtype)
+        return gx, gb, None, None, gw, None, None, None
 
 
 def aggregate_sum(x, g: GraphIndex, self_scale: float = 1.0, edge_weight=None, in_scale=None,
@@ -1538,6 +1577,8 @@ def gin_kan_layer(x, g: GraphIndex, self_scale: float, chain, act_dtype: Optiona
     and the normalised rows are returned."""
     if layer_inputs_visible():        # a collect_edge_l1 block: the composed form, every KANLinear.forward sees its input
         return None
+    if aggregation_visible():         # an edge_mask block: the aggregation runs on its own, with the mask as edge weights
+        return None
     layers = list(chain.layers)
     act = default_activation_dtype() if act_dtype is None else act_dtype
     plan = _chain_plan(layers)
@@ -1881,6 +1922,49 @@ def _refine_walk():
 
 def _set_refine_walk(walk) -> None:
     _EDGE_STATE.refine = walk
+
+
+def edge_mask_of(g: Optional[GraphIndex] = None):
+    """the mask of the ``kagnn_amd.edge_mask`` block open on THIS thread, or None.  With the graph a convolution is about to
+    aggregate over: checked against its edge count."""
+    mask = getattr(_EDGE_STATE, "mask", None)
+    if mask is not None and g is not None and mask.numel() != g.num_edges:
+        raise ValueError(f"edge_mask: the mask has {mask.numel()} entries but this convolution's graph has {g.num_edges} edges")
+    return mask
+
+
+def _set_edge_mask(mask) -> None:
+    _EDGE_STATE.mask = mask
+
+
+def aggregation_visible() -> bool:
+    """True inside a ``kagnn_amd.edge_mask`` block of the calling thread -- the sibling of ``layer_inputs_visible()``: every route
+    that hides a convolution's aggregation step (the fused ``gin_kan_layer`` node with or without its norm, the lazy-norm
+    ``AffineRows`` form whose folded aggregation is unit-weight only) then takes its per-operation form, so the step runs as
+    ``aggregate_sum(..., edge_weight=mask)``."""
+    return getattr(_EDGE_STATE, "mask", None) is not None
+
+
+def gcn_norm_weights(edge_index: torch.Tensor, edge_weight: torch.Tensor, num_nodes: int):
+    """``(graph, w_hat)``: the augmented edge list of ``WeightedGcnGraph`` (non-loop edges, then one self loop per node -- an
+    existing loop keeps its weight, otherwise 1) and its normalised weights ``w_hat[e] = dis[src] * w[e] * dis[dst]``,
+    ``dis = deg^-1/2`` (inf -> 0) of the weighted in-degree, in differentiable torch ops: the form ``_NormalisedConv`` takes for
+    weights that require a gradient, which then reaches them through the message AND the degrees, as in torch_geometric's
+    ``gcn_norm``.  Only the index of the augmented list (weight-independent) comes from the per-``edge_index`` cache."""
+    _need_cuda(edge_index, edge_weight)
+    if edge_weight.shape != (edge_index.size(1),):
+        raise ValueError(f"edge_weight must be [{edge_index.size(1)}], got {tuple(edge_weight.shape)}")
+    src, dst = edge_index[0], edge_index[1]
+    w = edge_weight.to(torch.float32)
+    keep = src != dst
+    loop_w = torch.ones(num_nodes, dtype=torch.float32, device=w.device).index_put((src[~keep],), w[~keep])
+    wa = torch.cat([w[keep], loop_w])
+    ar = torch.arange(num_nodes, dtype=src.dtype, device=src.device)
+    a_src, a_dst = torch.cat([src[keep], ar]), torch.cat([dst[keep], ar])
+    deg = torch.zeros(num_nodes, dtype=torch.float32, device=w.device).index_add(0, a_dst, wa)
+    dis = deg.pow(-0.5)
+    dis = torch.where(torch.isinf(dis), torch.zeros_like(dis), dis)
+    return weighted_gcn_graph(edge_index, None, num_nodes).graph, dis[a_src] * wa * dis[a_dst]
 
 
 def _edge_operands(what, rows, base_weight, spline_weight, spline_scaler, knots, grid_size, spline_order):

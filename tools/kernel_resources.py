@@ -42,6 +42,7 @@ HOT = [
     (r"agg_rows_v4_kernel<", 0, 0),
     (r"agg_hub", 0, 0),
     (r"agg16_", 0, 0),
+    (r"edge_grad_", 0, 0),                             # the edge-weight gradient of the aggregation (aggregate_edge.hip)
     (r"bn_", 0, 0),
     (r"batch_assemble_kernel", 0, 0),                  # the loader's one launch per mini-batch
     (r"linear_gemm_kernel<|linear_dw_reduce_kernel", 0, 0),   # the dense layer of the MLP baselines
