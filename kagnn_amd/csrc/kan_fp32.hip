@@ -324,9 +324,16 @@ __global__ void kan_dw_unpack_kernel(const float* __restrict__ gcat, int in, int
     const long of = (long)o * in + f;
     float gs = 0.0f;
     const float scale = sc ? sc[of] : 1.0f;
+    // a non-finite x[n, f] or gy[n, o] reaches the slabs through the k + 1 bases of ONE span only (bspline_local: span 0); in the
+    // reference's dense basis table it is NaN * 0 in every coefficient of the edge: one NaN coefficient makes all of them NaN
+    bool poisoned = false;
     for (int c = 0; c < C; ++c) {
         const float g = gcat[((long)c * inP + f) * outP + o];
-        g_sw[of * C + c] = g * scale;
+        poisoned |= g != g;
+    }
+    for (int c = 0; c < C; ++c) {
+        const float g = gcat[((long)c * inP + f) * outP + o];
+        g_sw[of * C + c] = poisoned ? __builtin_nanf("") : g * scale;
         gs = fmaf(g, sw[of * C + c], gs);
     }
     if (g_sc) g_sc[of] = gs;

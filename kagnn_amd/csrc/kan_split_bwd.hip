@@ -1730,7 +1730,8 @@ __device__ __forceinline__ void dw_reduce_unpack_body(const float* __restrict__ 
                                                       float* __restrict__ g_sw, float* __restrict__ g_sc, int SG, int bx, int by) {
     // thread = (output ol of 32, plane c of C+1, slab group sg of SG): the slab sum is split over SG groups (shorter
     // dependent load chains), combined through LDS in group order -- still a fixed summation order
-    extern __shared__ float s_red[];                 // [SG][C+1][32] partial sums, then [C][32] products
+    extern __shared__ float s_red[];                 // [SG][C+1][32] partial sums, then [C][32] products; behind them [C][32] sums
+    float* s_g = s_red + SG * (C + 1) * 32;
     const int ol = threadIdx.x & 31, pc = threadIdx.x >> 5;
     const int c = pc % (C + 1), sg = pc / (C + 1);
     const int f = by, o = bx * 32 + ol;
@@ -1755,14 +1756,23 @@ __device__ __forceinline__ void dw_reduce_unpack_body(const float* __restrict__ 
     const long of = (long)min(o, out - 1) * in + f;
     if (sg == 0) {
         if (c < C) {
-            const float scale = sc ? sc[of] : 1.0f;
-            if (live) g_sw[of * C + c] = g * scale;
             s_red[c * 32 + ol] = g * sw[of * C + c];
+            s_g[c * 32 + ol] = g;
         } else if (live && g_bw) {
             g_bw[of] = g;
         }
     }
     __syncthreads();
+    if (sg == 0 && c < C && live) {
+        // a non-finite x[n, f] or gy[n, o] reaches the slabs through the k + 1 bases of ONE span only (bspline_local: span 0); in
+        // the reference's dense basis table it is NaN * 0 in every coefficient of the edge: one NaN plane makes all of them NaN
+        bool poisoned = false;
+        for (int k = 0; k < C; ++k) {
+            const float v = s_g[k * 32 + ol];
+            poisoned |= v != v;
+        }
+        g_sw[of * C + c] = poisoned ? __builtin_nanf("") : g * (sc ? sc[of] : 1.0f);
+    }
     if (sg == 0 && c == 0 && live && g_sc) {
         float gs = 0.0f;
         for (int k = 0; k < C; ++k) gs += s_red[k * 32 + ol];
@@ -1797,7 +1807,7 @@ int dw_defer_flush(DwDefer* d, hipStream_t st) {
         gy = max(gy, (unsigned)d->item[k].in);
     }
     const int C = d->item[0].C, SG = d->item[0].SG;
-    kan_dw_reduce_unpack_batch_kernel<<<dim3(gx, gy, (unsigned)d->n), 32 * (C + 1) * SG, (size_t)SG * (C + 1) * 32 * sizeof(float), st>>>(b);
+    kan_dw_reduce_unpack_batch_kernel<<<dim3(gx, gy, (unsigned)d->n), 32 * (C + 1) * SG, (size_t)(SG * (C + 1) + C) * 32 * sizeof(float), st>>>(b);
     d->n = 0;
     KAGNN_LAUNCH_CHECK();
     return KAGNN_OK;
@@ -1812,7 +1822,7 @@ static int dw_reduce_unpack(const float* slab, long NS, int in, int out, int C, 
         d->item[d->n++] = DwReduceItem{slab, NS, in, out, C, SG, inP, outP, sw, sc, g_bw, g_sw, g_sc};
         return KAGNN_OK;
     }
-    kan_dw_reduce_unpack_kernel<<<dim3((unsigned)(outP / 32), (unsigned)in), 32 * (C + 1) * SG, (size_t)SG * (C + 1) * 32 * sizeof(float), st>>>(
+    kan_dw_reduce_unpack_kernel<<<dim3((unsigned)(outP / 32), (unsigned)in), 32 * (C + 1) * SG, (size_t)(SG * (C + 1) + C) * 32 * sizeof(float), st>>>(
         slab, NS, in, out, C, inP, outP, sw, sc, g_bw, g_sw, g_sc, SG);
     KAGNN_LAUNCH_CHECK();
     return KAGNN_OK;
@@ -1830,9 +1840,14 @@ __global__ void kan_dw_unpack_v_kernel(const float* __restrict__ gcat, int in, i
     const long of = (long)o * in + f;
     float gs = 0.0f;
     const float scale = sc ? sc[of] : 1.0f;
+    bool poisoned = false;                     // one NaN coefficient of an edge makes all of them NaN (kan_dw_unpack_kernel)
     for (int c = 0; c < C; ++c) {
         const float g = gcat[((long)(c & 7) * inP + 2 * f + (c >> 3)) * outP + o];
-        g_sw[of * C + c] = g * scale;
+        poisoned |= g != g;
+    }
+    for (int c = 0; c < C; ++c) {
+        const float g = gcat[((long)(c & 7) * inP + 2 * f + (c >> 3)) * outP + o];
+        g_sw[of * C + c] = poisoned ? __builtin_nanf("") : g * scale;
         gs = fmaf(g, sw[of * C + c], gs);
     }
     if (g_sc) g_sc[of] = gs;

@@ -80,6 +80,7 @@ class KANLinear(nn.Module):
         self._knots_key = None
         self._knots_row = None
         self.reset_parameters()
+        self.refresh_knots()
 
     # ------------------------------------------------------------------ init (host side)
     def reset_parameters(self):
@@ -112,24 +113,59 @@ class KANLinear(nn.Module):
     # ------------------------------------------------------------------ hot path
     def _knots(self) -> torch.Tensor:
         if torch.compiler.is_compiling():
-            # dynamo cannot trace the data_ptr-keyed cache below or its host-side uniformity check: use what an eager
-            # call cached, else assume the (uniform) grid the constructor made -- adaptive grids need one eager call first
-            return self._knots_row if self._knots_row is not None else self.grid[0].contiguous()
+            # dynamo cannot trace the data_ptr-keyed cache below or its host-side uniformity check: traced code reads what
+            # ``refresh_knots`` left.  Every eager site that writes the grid (the constructor, update_grid, refine, state loading,
+            # a move to another device or dtype) calls it, so no eager forward is needed first; only a direct write to
+            # ``layer.grid`` must be followed by ``layer.refresh_knots()``
+            row = self._knots_row
+            if row is None or row.device != self.grid.device or row.size(-1) != self.grid.size(1):
+                raise RuntimeError("KANLinear under torch.compile: the knots cache does not belong to this grid; call "
+                                   "layer.refresh_knots() (or run the layer once eagerly) after writing to layer.grid")
+            return row
         g = self.grid
         key = (g.data_ptr(), g._version, g.device)          # (the device object itself: str() of it was 1.5 us x 13 calls per graph-level step)
         if key != self._knots_key:
-            row = g[0].detach().to(torch.float32)
-            steps = row[1:] - row[:-1]
-            h = float(steps.mean())
-            same = bool((g == row).all()) and bool(((steps - h).abs() <= 1e-4 * abs(h)).all()) and h > 0
-            if same:
-                self._knots_row = row.contiguous().clone()
-            else:        # adaptive grid (update_grid was called): the whole buffer, per-feature knot rows
-                if not bool((g[:, 1:] > g[:, :-1]).all()):
-                    raise ValueError("KANLinear.grid rows must be strictly increasing")
-                self._knots_row = g.detach().to(torch.float32).contiguous().clone()
+            self._knots_row = self._knots_of(g)
             self._knots_key = key
         return self._knots_row
+
+    @staticmethod
+    def _knots_of(g: torch.Tensor) -> torch.Tensor:
+        """what the kernels take for the grid buffer ``g``: its first row when all rows are that one uniform row, else the whole
+        buffer (per-feature knot rows), fp32"""
+        row = g[0].detach().to(torch.float32)
+        steps = row[1:] - row[:-1]
+        h = float(steps.mean())
+        same = bool((g == row).all()) and bool(((steps - h).abs() <= 1e-4 * abs(h)).all()) and h > 0
+        if same:
+            return row.contiguous().clone()
+        # adaptive grid (update_grid was called): the whole buffer, per-feature knot rows
+        if not bool((g[:, 1:] > g[:, :-1]).all()):
+            raise ValueError("KANLinear.grid rows must be strictly increasing")
+        return g.detach().to(torch.float32).contiguous().clone()
+
+    def refresh_knots(self) -> None:
+        """Bring the knots cache in line with ``self.grid`` now (host code: it reads the grid).  Eager forwards do this on their
+        own; a compiled forward cannot, so every method of the layer that writes the grid ends with this call.  A grid whose rows
+        are not strictly increasing leaves the cache empty: the next forward raises, as it always did."""
+        self._knots_key = self._knots_row = None
+        g = self.grid
+        if g.is_meta or torch.compiler.is_compiling():
+            return
+        try:
+            self._knots_row = self._knots_of(g)
+        except ValueError:
+            return
+        self._knots_key = (g.data_ptr(), g._version, g.device)
+
+    def _apply(self, fn, *args, **kwargs):
+        out = super()._apply(fn, *args, **kwargs)          # .to() / .cuda() / .float(): the cache is a plain attribute and does not move
+        self.refresh_knots()
+        return out
+
+    def _load_from_state_dict(self, *args, **kwargs):
+        super()._load_from_state_dict(*args, **kwargs)     # a checkpoint's grid may hold per-feature rows
+        self.refresh_knots()
 
     def forward(self, x: torch.Tensor, _packed=None) -> torch.Tensor:
         assert x.dim() == 2 and x.size(1) == self.in_features
@@ -191,6 +227,7 @@ class KANLinear(nn.Module):
         fitted = ops.kan_grid_refit(x, self.grid, new_grid, self.spline_weight, scaler, g, k)
         self.grid.copy_(new_grid)
         self.spline_weight.data.copy_(fitted)
+        self.refresh_knots()
 
     def _quantile_knots(self, x: torch.Tensor, g: int, margin: float) -> torch.Tensor:
         """``update_grid``'s knot rule (``ekan.py:180-205``) for ``g`` intervals: ``[in, g+2k+1]``"""
@@ -250,8 +287,7 @@ class KANLinear(nn.Module):
         self.grid = new_grid.to(self.grid.dtype)
         self.spline_weight = nn.Parameter(fitted.to(old.dtype), requires_grad=old.requires_grad)
         self.grid_size = g_new
-        self._knots_key = None
-        self._knots_row = None
+        self.refresh_knots()
         return untouched
 
     # ------------------------------------------------------------------ the edge functions phi_{o,i}

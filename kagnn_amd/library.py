@@ -9,6 +9,7 @@ ctypes calls.  Both paths end in the same raw functions, i.e. the same ``libkagn
 
 Ops (all fp32, CUDA only -- there is no CPU kernel to register):
   kagnn::aggregate_sum            self-adjoint: its backward is the same op on the transposed CSR
+  kagnn::aggregate_edge_grad      the gradient of its edge weights, when they require one (raw: no formula of its own)
   kagnn::kan_linear (+ _bwd_input, _bwd_weight)
   kagnn::fastkan_layer (+ _bwd)
   kagnn::batch_norm (+ _bwd)      functional; the running statistics are updated by traced aten ops next to it
@@ -50,6 +51,24 @@ def _(x, rowptr, col, edge_weight, in_scale, out_scale, bias, hub_seg, num_hub_s
     return x.new_empty(x.shape)
 
 
+@_lib.custom_op("kagnn::aggregate_edge_grad", mutates_args=())
+def aggregate_edge_grad(x: Tensor, gout: Tensor, rowptr: Tensor, col: Tensor, perm: Tensor, in_scale: Optional[Tensor],
+                        out_scale: Optional[Tensor], hub_seg: Optional[Tensor], num_hub_seg: int, hub_threshold: int,
+                        num_edges: int, skip_self: bool) -> Tensor:
+    """d loss / d edge_weight of ``aggregate_sum`` on the by-destination CSR, ``[E]`` fp32 in ORIGINAL edge order
+    (``ops.aggregate_edge_grad``: the same launch)"""
+    with _ops._device_of(x):
+        ins = None if in_scale is None else in_scale.to(torch.float32).contiguous()
+        outs = None if out_scale is None else out_scale.to(torch.float32).contiguous()
+        return _ops._aggregate_edge_grad_csr(_ops._rows(x), _ops._rows(gout), rowptr, col, perm, hub_seg, num_hub_seg,
+                                             hub_threshold, num_edges, ins, outs, skip_self)
+
+
+@aggregate_edge_grad.register_fake
+def _(x, gout, rowptr, col, perm, in_scale, out_scale, hub_seg, num_hub_seg, hub_threshold, num_edges, skip_self):
+    return x.new_empty((num_edges,))
+
+
 # ---------------------------------------------------------------------------------------- KANLinear
 @_lib.custom_op("kagnn::kan_linear", mutates_args=())
 def kan_linear(x: Tensor, base_weight: Optional[Tensor], spline_weight: Tensor, spline_scaler: Optional[Tensor],
@@ -57,7 +76,8 @@ def kan_linear(x: Tensor, base_weight: Optional[Tensor], spline_weight: Tensor, 
     with _ops._device_of(x):
         bw = None if base_weight is None else base_weight.contiguous()
         sc = None if spline_scaler is None else spline_scaler.contiguous()
-        return _ops._kan_fwd_raw(_ops._rows(x), bw, spline_weight.contiguous(), sc, knots, grid_size, spline_order, mode)
+        return _ops._kan_fwd_raw(_ops._rows(x), bw, spline_weight.contiguous(), sc, knots, grid_size, spline_order, mode,
+                                 zero_pack=True)
 
 
 @kan_linear.register_fake
@@ -276,7 +296,8 @@ def aggregate(x, g, self_scale, edge_weight, in_scale, out_scale, bias, skip_sel
 
 
 class _AggregateBoth(torch.autograd.Function):
-    """thin tape node around the opaque op: it only chooses which side of the GraphIndex the op sees"""
+    """thin tape node around the opaque ops: it only chooses which side of the GraphIndex they see.  Edge weights that require
+    a gradient get it from ``kagnn::aggregate_edge_grad``, as on the eager route."""
 
     @staticmethod
     def forward(ctx, x, bias, g, self_scale, edge_weight, in_scale, out_scale, skip_self):
@@ -285,6 +306,11 @@ class _AggregateBoth(torch.autograd.Function):
         ctx.ew_t = None
         ew = None
         if edge_weight is not None:
+            if edge_weight.requires_grad:          # the one case in which the gathered rows are kept, as in ops._AggregateFn
+                if edge_weight.shape != (g.num_edges,):
+                    raise ValueError(f"edge_weight must be [{g.num_edges}] to receive a gradient, got {tuple(edge_weight.shape)}")
+                ctx.save_for_backward(x)
+                ctx.ew_dtype = edge_weight.dtype
             w = edge_weight.to(torch.float32)
             ctx.ew_t = w[g.perm_t.long()].contiguous()
             ew = w[g.perm.long()].contiguous()
@@ -294,11 +320,15 @@ class _AggregateBoth(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gout):
         g = ctx.g
-        gx = gb = None
+        gx = gb = gw = None
         if ctx.needs_input_grad[0]:
             gx = aggregate_sum(gout, g.rowptr_t, g.col_t, ctx.ew_t, ctx.out_scale, ctx.in_scale, None,
                                g.hub_seg_t if g.num_hub_seg_t else None, g.num_hub_seg_t, g.hub_threshold,
                                ctx.self_scale, ctx.skip_self)
         if ctx.needs_input_grad[1]:
             gb = gout.sum(0)
-        return gx, gb, None, None, None, None, None, None
+        if ctx.needs_input_grad[4]:
+            gw = aggregate_edge_grad(ctx.saved_tensors[0], gout, g.rowptr, g.col, g.perm, ctx.in_scale, ctx.out_scale,
+                                     g.hub_seg if g.num_hub_seg else None, g.num_hub_seg, g.hub_threshold, g.num_edges,
+                                     ctx.skip_self).to(ctx.ew_dtype)
+        return gx, gb, None, None, gw, None, None, None

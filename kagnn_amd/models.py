@@ -163,8 +163,10 @@ class _NormalisedConv(nn.Module):
             dis = g.gcn_dis
             return ops.aggregate_sum(self.lin(x), g, self_scale=1.0, edge_weight=mask, in_scale=dis, out_scale=dis,
                                      bias=self.bias, skip_self_loops=True)
-        if edge_weight is not None and edge_weight.requires_grad and not sparse and not torch.compiler.is_compiling():
-            # weights that want a gradient: the normalisation in differentiable torch ops, nothing cached (ops.gcn_norm_weights)
+        if edge_weight is not None and edge_weight.requires_grad and not sparse:
+            # weights that want a gradient: the normalisation in differentiable torch ops, nothing cached (ops.gcn_norm_weights).
+            # Traced code too: its boolean-mask selections break the graph (an error under fullgraph=True), which beats a gradient
+            # without the degree term
             graph, w_hat = ops.gcn_norm_weights(edge_index, edge_weight, x.size(0))
             return ops.aggregate_sum(self.lin(x), graph, self_scale=0.0, edge_weight=w_hat, bias=self.bias)
         if edge_weight is not None or sparse:

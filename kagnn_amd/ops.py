@@ -636,14 +636,21 @@ def aggregate_edge_grad(x, gout, g: GraphIndex, in_scale=None, out_scale=None, s
                 raise ValueError(f"in_scale / out_scale must be [{n}]")
         scales.append(s)
     e = g.num_edges
-    if out is None:
-        out = torch.empty(e, dtype=torch.float32, device=x.device)
-    elif out.dtype != torch.float32 or out.dim() != 1 or out.numel() < e or not out.is_contiguous():
+    if out is not None and (out.dtype != torch.float32 or out.dim() != 1 or out.numel() < e or not out.is_contiguous()):
         raise ValueError(f"out must be a contiguous fp32 vector of at least {e} elements")
     with _device_of(x):
-        _call("kagnn_aggregate_edge_grad", _ptr(x), _ld(x), _ptr(gout), _ld(gout), _ptr(g.rowptr), _ptr(g.col), _ptr(g.perm), n, e, f,
-              _ptr(scales[0]), _ptr(scales[1]), int(bool(skip_self_loops)), _ptr(g.hub_seg) if g.num_hub_seg else None, g.num_hub_seg,
-              g.hub_threshold, _ptr(out), _stream())
+        return _aggregate_edge_grad_csr(x, gout, g.rowptr, g.col, g.perm, g.hub_seg if g.num_hub_seg else None, g.num_hub_seg,
+                                        g.hub_threshold, e, scales[0], scales[1], skip_self_loops, out)
+
+
+def _aggregate_edge_grad_csr(x, gout, rowptr, col, perm, hub, nhub, hub_threshold, num_edges, in_scale, out_scale, skip_self, out=None):
+    """the launch of ``aggregate_edge_grad`` on the arrays of the by-destination CSR (also what ``kagnn::aggregate_edge_grad`` of
+    ``kagnn_amd.library`` runs): fp32 rows with unit column stride, fp32 scales or None"""
+    n, f = x.shape
+    if out is None:
+        out = torch.empty(num_edges, dtype=torch.float32, device=x.device)
+    _call("kagnn_aggregate_edge_grad", _ptr(x), _ld(x), _ptr(gout), _ld(gout), _ptr(rowptr), _ptr(col), _ptr(perm), n, num_edges, f,
+          _ptr(in_scale), _ptr(out_scale), int(bool(skip_self)), _ptr(hub) if nhub else None, nhub, hub_threshold, _ptr(out), _stream())
     return out
 
 
@@ -992,9 +999,12 @@ def _weights_key(bw, sw, sc):
 
 # raw (no autograd) pieces of the KANLinear forward / backward: shared by the autograd.Function below (eager) and by the
 # torch.library ops of kagnn_amd/library.py (torch.compile sees those as opaque ops)
-def _kan_fwd_raw(x, bw, sw, sc, knots, grid_size, spline_order, mode, packed=None, pack_key=None, moments=False, out=None):
+def _kan_fwd_raw(x, bw, sw, sc, knots, grid_size, spline_order, mode, packed=None, pack_key=None, moments=False, out=None,
+                 zero_pack=False):
     """-> (y, pack_dx): forward output and the input-gradient pack of the current weights; with ``moments`` also the
-    column moments of y, ``(mean [out], M2 [out])`` (``kagnn_kan_linear_fwd_moments``: the BatchNorm1d statistics)"""
+    column moments of y, ``(mean [out], M2 [out])`` (``kagnn_kan_linear_fwd_moments``: the BatchNorm1d statistics).
+    ``zero_pack``: the bytes of pack_dx that the pack kernel skips (padding nothing reads) are 0 instead of whatever the
+    allocator handed out -- for ``kagnn::kan_linear``, which RETURNS the pack: an op's output must be a function of its inputs"""
     n, fin = x.shape
     fout = sw.size(0)
     if packed is not None and packed[2] == pack_key:
@@ -1002,6 +1012,8 @@ def _kan_fwd_raw(x, bw, sw, sc, knots, grid_size, spline_order, mode, packed=Non
     else:
         fb, db = _sizes("kagnn_kan_pack_bytes", fin, fout, grid_size, spline_order, mode, outputs=2)
         pack_f, pack_d = _ws(fb, x.device), _ws(db, x.device)
+        if zero_pack:
+            pack_d.zero_()
         _call("kagnn_kan_pack", _ptr(bw), _ptr(sw), _ptr(sc), fin, fout, grid_size, spline_order, mode,
               _ptr(pack_f), _ptr(pack_d), _stream())
     if out is not None and (out.shape != (n, fout) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != x.device):
@@ -1635,11 +1647,15 @@ def kan_linear(x, base_weight, spline_weight, spline_scaler, knots, grid_size: i
         groups = -(-n_coef // 16)
         size, extra = divmod(n_coef, groups)
         y, c0 = None, 0
+        one_group = _KANLinearFn.apply
+        if torch.compiler.is_compiling():                 # traced code: every group is one opaque kagnn::kan_linear op
+            from . import library
+            one_group = lambda *a: library.kan_linear(*a)[0]
         for g in range(groups):
             cg = size + (1 if g < extra else 0)
-            part = _KANLinearFn.apply(x, base_weight if g == 0 else None, spline_weight[:, :, c0:c0 + cg], spline_scaler,
-                                      knots[c0:c0 + cg + int(spline_order) + 1], cg - int(spline_order),
-                                      int(spline_order), int(mode))
+            part = one_group(x, base_weight if g == 0 else None, spline_weight[:, :, c0:c0 + cg], spline_scaler,
+                             knots[c0:c0 + cg + int(spline_order) + 1], cg - int(spline_order),
+                             int(spline_order), int(mode))
             y = part if y is None else y + part
             c0 += cg
         return y
@@ -3072,11 +3088,15 @@ def fastkan_layer(x, ln_weight, ln_bias, spline_weight, base_weight, base_bias, 
         groups = -(-ng // 16)
         size, extra = divmod(ng, groups)
         y, c0 = None, 0
+        one_group = _FastKANFn.apply
+        if torch.compiler.is_compiling():                 # traced code: every group is one opaque kagnn::fastkan_layer op
+            from . import library
+            one_group = lambda *a: library.fastkan_layer(*a)[0]
         for g in range(groups):
             cg = size + (1 if g < extra else 0)
-            part = _FastKANFn.apply(x, ln_weight, ln_bias, w3[:, :, c0:c0 + cg].reshape(fout, fin * cg),
-                                    base_weight if g == 0 else None, base_bias if g == 0 else None,
-                                    centers[c0:c0 + cg], float(denominator), float(ln_eps), int(mode))
+            part = one_group(x, ln_weight, ln_bias, w3[:, :, c0:c0 + cg].reshape(fout, fin * cg),
+                             base_weight if g == 0 else None, base_bias if g == 0 else None,
+                             centers[c0:c0 + cg], float(denominator), float(ln_eps), int(mode))
             y = part if y is None else y + part
             c0 += cg
         return y

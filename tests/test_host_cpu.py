@@ -442,3 +442,33 @@ def test_bench_dump_outputs_samples_the_same_rows_within_the_budget(tmp_path):
     assert np.array_equal(got["grad.w"], arrays["grad.w"].numpy()) and got["loss"] == np.float32(1.5)
     for name, a in got.items():
         assert np.array_equal(a, np.load(tmp_path / "b" / f"{name}.npy")), name
+
+
+def test_knots_cache_follows_every_host_write_of_the_grid():
+    """the knots a compiled KANLinear evaluates on (``_knots_row``: dynamo cannot trace the check behind it) are refreshed by the
+    constructor, state loading and every move of the module -- no eager forward needed; a direct write needs ``refresh_knots()``"""
+    import copy
+    layer = kagnn_amd.KANLinear(5, 3, grid_size=4)
+    assert layer._knots_row.dim() == 1 and torch.equal(layer._knots_row, layer.grid[0])
+    uniform = layer.grid.clone()
+    state = copy.deepcopy(layer.state_dict())
+    state["grid"] = state["grid"] + 0.01 * torch.arange(5.0).unsqueeze(1)          # per-feature rows, each still increasing
+    layer.load_state_dict(state)
+    assert layer._knots_row.shape == (5, 11) and torch.equal(layer._knots_row, state["grid"])
+    layer.double()                                                                 # (a move: the cache is a plain attribute)
+    assert layer._knots_row.dtype == torch.float32 and torch.equal(layer._knots_row, state["grid"])
+    assert layer._knots_key == (layer.grid.data_ptr(), layer.grid._version, layer.grid.device)
+    layer.float()
+    with torch.no_grad():
+        layer.grid.copy_(uniform)                                                  # a direct write: the cache is stale until refreshed
+    assert layer._knots_row.dim() == 2
+    layer.refresh_knots()
+    assert layer._knots_row.dim() == 1 and torch.equal(layer._knots_row, uniform[0])
+    with torch.no_grad():
+        layer.grid[:, 3] = layer.grid[:, 2]                                        # not strictly increasing: no cache, the forward raises
+    layer.refresh_knots()
+    assert layer._knots_row is None and layer._knots_key is None
+    with pytest.raises(ValueError, match="strictly increasing"):
+        layer._knots()
+    clone = copy.deepcopy(kagnn_amd.KANLinear(5, 3, grid_size=4))
+    assert torch.equal(clone._knots_row, clone.grid[0])
