@@ -35,13 +35,21 @@ __device__ __forceinline__ void stats_products(const AggArgs& a, long row, int c
 // STATS: also leave the workgroup's column sums of the rows it stores (and of their products with xhat) in
 // a.st_partial[row group][2][F] -- rows of one workgroup meet in LDS and are added in row order (deterministic); hub rows
 // contribute nothing here (their final value exists only in agg_hub_merge_kernel, which adds their share)
-template <int LPR, bool STATS = false>
-__global__ __launch_bounds__(256) void agg_rows_v4_kernel(AggArgs a) {
+// LEAN (agg_rows_v4_corun_kernel below): unit edge weights and no scales, bias, self-loop filter or column affine -- the GIN
+// gradient's shape, known at compile time.  The same operations in the same order with the constants the options default to (a
+// weight and a scale of 1.0f, a bias of 0.0f), so the same bits; what goes is the registers the options hold across the gather loop.
+template <int LPR, bool STATS, bool LEAN>
+__device__ __forceinline__ void agg_rows_v4_body(const AggArgs& args) {
+    AggArgs a = args;
+    if constexpr (LEAN) {
+        a.ew = nullptr; a.in_scale = nullptr; a.out_scale = nullptr; a.bias = nullptr; a.skip_self = 0;
+        a.col_scale = nullptr; a.col_shift = nullptr;
+    }
     // XCD placement (speed only -- nothing depends on it): workgroups reach the 8 XCDs round-robin (block b runs on XCD b % 8:
     // observed, not promised).  Each XCD takes ONE contiguous eighth of the row groups instead of every 8th one, so the rowptr / col
     // lines two neighbouring row groups share land in one L2 instead of two: -0.012 ms of 0.868 per step at the headline graph
     // (profiles/r06_experiments.md 6).  The launch rounds the grid up to whole eighths; `wg` is the row group, as blockIdx.x was.
-    const unsigned wg = (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
+    const unsigned wg = (LEAN ? a.wg0 : 0u) + (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
     const long gid = (wg * 256L + threadIdx.x) / LPR;
     const int c4 = (threadIdx.x % LPR) * 4;
     const bool live = gid < a.N && c4 < a.F;
@@ -106,6 +114,16 @@ __global__ __launch_bounds__(256) void agg_rows_v4_kernel(AggArgs a) {
         }
     }
 }
+
+template <int LPR, bool STATS = false>
+__global__ __launch_bounds__(256) void agg_rows_v4_kernel(AggArgs a) { agg_rows_v4_body<LPR, STATS, false>(a); }
+
+// The row kernel of the backward's transposed aggregation when the layer's deferred weight gradients run beside it (layer_bwd_impl,
+// fused_calls.hip; host.h: AggCorun).  A weight-gradient wave holds 352 of a SIMD's 512 registers, so what runs beside it has 160:
+// this instantiation must stay at or below kAggCorunVgprs = 40 allocated registers, four waves per SIMD
+// (tests/test_bwd_overlap_cpu.py reads the compiler's metadata).  It covers the row groups from a.wg0 on.
+template <int LPR>
+__global__ __launch_bounds__(256) void agg_rows_v4_corun_kernel(AggArgs a) { agg_rows_v4_body<LPR, false, true>(a); }
 
 // Narrow rows (F <= 16): with LPR = F/4 lanes per row a wave would own 64/LPR rows and run as long as the
 // longest of their neighbour lists -- on power-law graphs several times the mean.  Here a row still gets 16
@@ -550,8 +568,18 @@ bool aggregate_stats_ok(const AggArgs& a) {
 }
 long aggregate_stats_rows(long N, int F, long num_hub_seg) { return (long)cdiv(N * stats_lpr(F), 256) + (num_hub_seg > 0 ? num_hub_seg : 0); }
 
-int aggregate_sum(const AggArgs& a, const int* hub_seg, long num_hub_seg, float* ws, size_t ws_bytes, hipStream_t st) {
+// The co-run launch (fused_calls.hip: the backward's transposed aggregation beside the deferred weight gradients) exists for the
+// shape it was measured at (profiles/bwd_overlap.md): 16 lanes per row, what agg_rows_v4_corun_kernel leaves out not asked for
+bool aggregate_corun_ok(const AggArgs& a) {
+    return vec4_ok(a) && a.F > 32 && a.F <= 64 && !a.ew && !a.in_scale && !a.out_scale && !a.bias && !a.skip_self && !a.col_scale && !a.st_partial;
+}
+
+// corun (only where aggregate_corun_ok): the rows go through agg_rows_v4_corun_kernel in two launches (host.h: AggCorun); the hub
+// kernels are short and stay as they are, behind both.  Every row is computed as in the plain launch: same bits.
+int aggregate_sum(const AggArgs& a, const int* hub_seg, long num_hub_seg, float* ws, size_t ws_bytes, hipStream_t st, const AggCorun* corun) {
     if (a.N == 0) return KAGNN_OK;
+    if (corun && !(aggregate_corun_ok(a) && corun->head_pct >= 0 && corun->head_pct < 100 && corun->side_done))
+        return fail(KAGNN_ERR_ARG, "%s: the co-run launch does not cover this call", "aggregate_sum");
     const bool stats = a.st_partial != nullptr;
     if (stats && !aggregate_stats_ok(a)) return fail(KAGNN_ERR_UNSUPPORTED, "%s: column statistics need 16-byte aligned fp32 rows of 17..256 columns", "aggregate_sum");
     if (!vec4_ok(a)) {
@@ -582,7 +610,19 @@ int aggregate_sum(const AggArgs& a, const int* hub_seg, long num_hub_seg, float*
             KAGNN_LAUNCH_CHECK();                                                     \
             HUBS(LPR, true)                                                           \
         } else {                                                                      \
-            agg_rows_v4_kernel<LPR><<<AGG_ROWS_GRID(a.N * LPR), 256, 0, st>>>(b);       \
+            if (corun && LPR == 16) {        /* head beside the side stream's work, tail after it (host.h: AggCorun) */ \
+                const unsigned total = AGG_ROWS_GRID(a.N * LPR);      /* whole eighths, and so are both parts */ \
+                const unsigned head = (unsigned)((unsigned long)total * (unsigned)corun->head_pct / 100) & ~7u; \
+                if (head) {                                                           \
+                    agg_rows_v4_corun_kernel<16><<<head, 256, kAggCorunLds, st>>>(b); \
+                    KAGNN_LAUNCH_CHECK();                                             \
+                }                                                                     \
+                KAGNN_HIP(hipStreamWaitEvent(st, corun->side_done, 0));               \
+                AggArgs t = b;                                                        \
+                t.wg0 = head;                                                         \
+                agg_rows_v4_corun_kernel<16><<<total - head, 256, 0, st>>>(t);        \
+            } else                                                                    \
+                agg_rows_v4_kernel<LPR><<<AGG_ROWS_GRID(a.N * LPR), 256, 0, st>>>(b);   \
             KAGNN_LAUNCH_CHECK();                                                     \
             HUBS(LPR, false)                                                          \
         }                                                                             \

@@ -270,6 +270,8 @@ struct AggArgs {
     // own statistics pass over g and y.
     const float* st_y = nullptr; long st_ldy = 0; const float* st_mean = nullptr; const float* st_rstd = nullptr;
     float* st_partial = nullptr;
+    // first row group of this launch (agg_rows_v4_corun_kernel only: the co-run launch covers the row groups in two launches)
+    unsigned wg0 = 0;
 };
 
 // arguments of the edge-weight gradient of that aggregation (aggregate_edge.hip): for CSR position e of row i, j = col[e],

@@ -3,6 +3,7 @@
 // and launchers (same kernels, same order, same bits as composing them), on ONE caller-provided workspace whose layout is written
 // down once per call family (LayerLayout, StackLayout, KmLayout) and read by the size query and by both directions.
 #include "host.h"
+#include <mutex>
 
 using namespace kagnn;
 
@@ -203,6 +204,79 @@ int layer_fwd_impl(const GraphSide& gr, const KanChain& c, const LayerIn& in, co
     return KAGNN_OK;
 }
 
+// ---- the backward's fork: weight gradients on a side stream beside the transposed aggregation (layer_bwd_impl)
+// One side stream and one event pair per device, created on first use and never destroyed (timing disabled: they only order).
+// The mutex is held from the fork to the join of a call: the enqueue of one call's {fork, side-stream work, join} is atomic against
+// another host thread's, so the shared events are never re-recorded between a record and the wait that belongs to it (a wait that
+// is already enqueued keeps the record it saw), and two calls on one device queue behind each other on the side stream.
+struct BwdSide { hipStream_t stream = nullptr; hipEvent_t fork = nullptr, join = nullptr; };
+constexpr int kBwdSideMaxDevices = 64;
+std::mutex g_bwd_side_mu;
+BwdSide g_bwd_side[kBwdSideMaxDevices];
+
+class BwdFork {
+    std::unique_lock<std::mutex> lk_;
+    BwdSide* s_ = nullptr;
+    hipStream_t caller_ = nullptr;
+    bool forked_ = false, recorded_ = false;
+public:
+    BwdFork() = default;
+    BwdFork(const BwdFork&) = delete;
+    BwdFork& operator=(const BwdFork&) = delete;
+    // the device's side stream and events (created here the first time); takes the lock
+    int prepare(hipStream_t caller) {
+        int dev = 0;
+        KAGNN_HIP(hipGetDevice(&dev));
+        if (dev < 0 || dev >= kBwdSideMaxDevices) return fail(KAGNN_ERR_UNSUPPORTED, "%s: device index out of range", "layer_bwd");
+        lk_ = std::unique_lock<std::mutex>(g_bwd_side_mu);
+        BwdSide& s = g_bwd_side[dev];
+        // (non-blocking: torch's default stream is the legacy null stream, which every blocking stream synchronises with)
+        if (!s.stream) KAGNN_HIP(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
+        if (!s.fork) KAGNN_HIP(hipEventCreateWithFlags(&s.fork, hipEventDisableTiming));
+        if (!s.join) KAGNN_HIP(hipEventCreateWithFlags(&s.join, hipEventDisableTiming));
+        s_ = &s; caller_ = caller;
+        return KAGNN_OK;
+    }
+    // everything launched on the caller's stream so far happens before what the side stream is given from here on
+    int fork() {
+        KAGNN_HIP(hipEventRecord(s_->fork, caller_));
+        KAGNN_HIP(hipStreamWaitEvent(s_->stream, s_->fork, 0));
+        forked_ = true;
+        return KAGNN_OK;
+    }
+    hipStream_t side() const { return s_->stream; }
+    // everything given to the side stream (all of it: nothing may follow), as the event the caller's stream has to wait for
+    int side_done(hipEvent_t* ev) {
+        KAGNN_HIP(hipEventRecord(s_->join, s_->stream));
+        recorded_ = true;
+        *ev = s_->join;
+        return KAGNN_OK;
+    }
+    // the caller's stream has been made to wait for that event (the aggregation's launcher does it between its two parts)
+    void joined() { forked_ = false; }
+    // the join on every other path out of the call after the fork, error returns included
+    int join() {
+        if (!forked_) return KAGNN_OK;
+        forked_ = false;
+        if (!recorded_) KAGNN_HIP(hipEventRecord(s_->join, s_->stream));
+        KAGNN_HIP(hipStreamWaitEvent(caller_, s_->join, 0));
+        return KAGNN_OK;
+    }
+    ~BwdFork() { (void)join(); }
+};
+
+// the weight gradient whose footprint the co-run launch of the aggregation was sized for (host.h: kAggCorunLds): the cubic
+// kan_split_dw_kernel of one 64 x 64 role, one workgroup per CU.  Other shapes run other kernels; they keep their place.
+// kAggCorunHeadPct: the share of the aggregation's row groups that runs beside ONE such weight gradient -- at the headline shape
+// (N = 1M, E = 10M, 64 features) two of them take 0.61 ms and the held-back row kernel covers 55-60 % of its rows meanwhile; a
+// head of 70 % measured best and 55-80 % within the run-to-run spread of it (profiles/bwd_overlap.md).  A graph with other degrees
+// moves the balance, not the result: the head that outlasts the weight gradients runs on with four waves per SIMD, the tail
+// of a head that ends early waits for them.
+constexpr int kAggCorunHeadPct = 35;
+bool dw_corun_ok(int in, int out, int G, int K, int mode) {
+    return use_split_dw(in, out, G, K, mode) && !g_half_products && K == 3 && G + K <= 8 && in > 32 && in <= 64 && out <= 64;
+}
+
 int layer_bwd_impl(const GraphSide& gr, const KanChain& c, const LayerGrads& io, const BnStage* bn, const float* bn_sums_in,
                    const StatsOut* so, const GineStage* gine, const DwPiece* piece, void* workspace, size_t workspace_bytes, void* stream,
                    const char* fn) {
@@ -230,12 +304,49 @@ int layer_bwd_impl(const GraphSide& gr, const KanChain& c, const LayerGrads& io,
     unsigned char* gbuf[2] = {ws + lay.g[0], ws + lay.g[1]};
     // layer l's weight gradient: its row slabs go to the shared area and their reduction is launched -- or, inside a stack call that
     // reduces the slabs of all its layers in one launch at the end, to the layer's place in the call's arena, and it is recorded
-    auto dw = [&](int l, const float* g, long ldg) {
+    auto dw_on = [&](void* st, int l, const float* g, long ldg) {
         unsigned char* area = piece ? piece->base + lay.dw_piece[l] : ws + lay.dw;
         const size_t bytes = piece ? lay.dw_piece_bytes[l] : lay.dw_bytes;
         return kan_linear_bwd_weight(acts[l], widths[l], nullptr, g, ldg, N, c.knots, widths[l], widths[l + 1], G, K, mode, c.sw[l],
                                      c.sc ? c.sc[l] : nullptr, io.g_bw ? io.g_bw[l] : nullptr, io.g_sw[l], io.g_sc ? io.g_sc[l] : nullptr,
-                                     area, bytes, stream, piece ? piece->defer : nullptr);
+                                     area, bytes, st, piece ? piece->defer : nullptr);
+    };
+    // The weight gradients feed nothing inside this call, and they leave the memory system mostly idle while the transposed
+    // aggregation at the end of the call is limited by it: those whose operands are still alive after the dX chain -- layer 0's (its
+    // gradient rows sit in the ping-pong matrix the last dX does not write) and, without a BatchNorm stage, the last layer's (it
+    // reads the caller's gy) -- are launched after the chain on a side stream, beside the aggregation (its co-run launch, host.h);
+    // the layers between keep their place, their rows are overwritten by the ping-pong.  Same kernels, operands and slab order:
+    // same bits.  KAGNN_BWD_OVERLAP=0 (read per call) keeps the serial order; so do a capturing stream (a captured step keeps the
+    // graph it has, without parallel branches) and every shape the co-run launch was not measured at (profiles/bwd_overlap.md).
+    BwdFork side;
+    struct { int l; const float* g; long ldg; } deferred[2];
+    int n_deferred = 0;
+    bool overlap = false;
+    if (gx && !gine && !piece && !so && !io.bf16_gather && io.gx_dtype == KAGNN_DTYPE_F32 && dw_corun_ok(widths[0], widths[1], G, K, mode)) {
+        const char* env = getenv("KAGNN_BWD_OVERLAP");
+        const AggArgs probe{reinterpret_cast<const float*>(gbuf[0]), widths[0], static_cast<float*>(gx), io.ldgx, gr.rowptr, gr.col, nullptr, N,
+                            widths[0], gr.self_scale, nullptr, nullptr, nullptr, 0, 0x7fffffff, io.gx_addend, io.ld_addend};
+        // (a call the aggregation's entry point would refuse -- short leading dimensions, gx inside the workspace -- stays on the
+        // serial path and is refused there, with that path's message)
+        const bool gx_in_ws = static_cast<unsigned char*>(gx) + (size_t)N * io.ldgx * sizeof(float) > ws &&
+                              static_cast<unsigned char*>(gx) < ws + workspace_bytes;
+        overlap = (env == nullptr || atoi(env) != 0) && io.ldgx >= widths[0] && (!io.gx_addend || io.ld_addend >= widths[0]) && !gx_in_ws &&
+                  aggregate_corun_ok(probe);
+        if (overlap) {
+            hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+            if (hipStreamIsCapturing(as_stream(stream), &cap) != hipSuccess) { (void)hipGetLastError(); overlap = false; }
+            else overlap = cap == hipStreamCaptureStatusNone;
+        }
+        if (overlap) { rc = side.prepare(as_stream(stream)); if (rc) return rc; }
+    }
+    // layer l's weight gradient: launched in its place, or noted for the side stream
+    auto dw = [&](int l, const float* g, long ldg) {
+        const bool alive = l == 0 || (l == L - 1 && !bn);        // (l == L - 1 with a BatchNorm stage: its rows are in gbuf[1], see below)
+        if (overlap && alive && dw_corun_ok(widths[l], widths[l + 1], G, K, mode)) {
+            deferred[n_deferred++] = {l, g, ldg};
+            return (int)KAGNN_OK;
+        }
+        return dw_on(stream, l, g, ldg);
     };
     const float* g = io.gy;
     long ldg = io.ldgy;
@@ -306,6 +417,30 @@ int layer_bwd_impl(const GraphSide& gr, const KanChain& c, const LayerGrads& io,
     }
     if (gx == nullptr) return KAGNN_OK;
     const int f0 = widths[0];
+    if (overlap) {
+        // fork: the side stream takes the noted weight gradients in layer order L-1 .. 0 (one slab area: they stay serial there),
+        // this stream the aggregation.  The call never returns with side-stream work this stream has not been made to wait for
+        // (on an error return the destructor issues the wait), so nothing later touches the workspace while it is outstanding
+        rc = side.fork();
+        if (rc) return rc;
+        for (int k = 0; k < n_deferred; ++k) {
+            rc = dw_on(side.side(), deferred[k].l, deferred[k].g, deferred[k].ldg);
+            if (rc) return rc;
+        }
+        const AggArgs a{g, ldg, static_cast<float*>(gx), io.ldgx, gr.rowptr, gr.col, nullptr, N, f0, gr.self_scale, nullptr, nullptr, nullptr,
+                        0, gr.hub_threshold > 0 ? gr.hub_threshold : 0x7fffffff, io.gx_addend, io.ld_addend};
+        // the join sits INSIDE the aggregation: kAggCorunHeadPct of the row groups per deferred weight gradient run beside them, held
+        // to what a weight-gradient wave leaves free; then this stream waits for the side stream and the rest of the rows have the
+        // machine to themselves (host.h: AggCorun)
+        AggCorun corun{kAggCorunHeadPct * n_deferred, nullptr};
+        rc = side.side_done(&corun.side_done);
+        if (rc) return rc;
+        KAGNN_STAGE_AS("kagnn_aggregate_sum", stream);
+        rc = aggregate_sum(a, gr.hub_seg, gr.num_hub_seg, reinterpret_cast<float*>(ws), lay.bwd_hub_bytes, as_stream(stream), &corun);
+        if (rc) return rc;
+        side.joined();
+        return KAGNN_OK;
+    }
     if (gine)        // GINE: gradient of the relu(x_j + e_ij) messages on the transposed structure -> gx and the edge-attribute gradient
         return gine_bwd(gine->x, gine->ldx, gine->ea, gine->lde, g, ldg, static_cast<float*>(gx), io.ldgx, gine->g_ea, gine->ldge,
                         gr.rowptr, gr.col, gine->perm, N, f0, gr.self_scale, as_stream(stream), gine->accumulate_g_ea);

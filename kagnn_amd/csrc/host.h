@@ -11,7 +11,20 @@ struct RbfArgs;                                     // split_common.h (device-si
 
 // ---- aggregate.hip
 size_t aggregate_ws_bytes(long num_hub_seg, int F);
-int aggregate_sum(const AggArgs& a, const int* hub_seg, long num_hub_seg, float* ws, size_t ws_bytes, hipStream_t st);
+// The co-run launch of the row kernel: the backward's transposed aggregation while the layer's deferred weight gradients run on
+// a side stream (fused_calls.hip: layer_bwd_impl; measurements: profiles/bwd_overlap.md).  The row groups go in two launches of
+// agg_rows_v4_corun_kernel.  The HEAD -- the first head_pct per cent of them -- runs beside the weight gradients and must never keep
+// one of their workgroups from being placed: a weight-gradient wave holds 352 of a SIMD's 512 registers and its workgroup 2.5 KB of
+// a CU's 160 KiB of LDS, so the head asks for kAggCorunLds bytes of dynamic LDS it never touches -- four such requests fit beside
+// that workgroup, five do not even alone -- which holds it to four 256-thread workgroups per CU = four waves per SIMD of at most
+// kAggCorunVgprs registers each, the 160 a weight-gradient wave leaves, whichever kernel the hardware starts first.  Then the stream
+// waits for side_done (the side stream's work) and the TAIL, the remaining row groups, runs with the whole machine.
+struct AggCorun { int head_pct; hipEvent_t side_done; };
+constexpr unsigned kAggCorunLds = 40000;
+constexpr int kAggCorunVgprs = 40;
+int aggregate_sum(const AggArgs& a, const int* hub_seg, long num_hub_seg, float* ws, size_t ws_bytes, hipStream_t st,
+                  const AggCorun* corun = nullptr);
+bool aggregate_corun_ok(const AggArgs& a);
 bool aggregate_stats_ok(const AggArgs& a);
 long aggregate_stats_rows(long N, int F, long num_hub_seg);
 int gcn_deg_inv_sqrt(const int* rowptr, const int* col, long N, float* dis, hipStream_t st);

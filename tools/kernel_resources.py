@@ -40,6 +40,7 @@ HOT = [
     (r"kan_dx_f32_kernel<|kan_dw_f32_kernel<|kan_fwd_f32_kernel<", 0, 0),   # exact-fp32 mode: the documented fallback (round 4: was up to 53 spilled)
     (r"kan_ho_", 0, 0),                                # spline orders 5..16 (order a kernel argument: a run-time index into a private array would be scratch)
     (r"agg_rows_v4_kernel<", 0, 0),
+    (r"agg_rows_v4_corun_kernel<", 0, 0),              # the backward's transposed aggregation beside the weight gradients
     (r"agg_hub", 0, 0),
     (r"agg16_", 0, 0),
     (r"edge_grad_", 0, 0),                             # the edge-weight gradient of the aggregation (aggregate_edge.hip)
