@@ -7,8 +7,12 @@ that pattern: all outputs and gradients must be the same bits whatever the patte
 partial-sum slab -- which parity tests at "nice" shapes and a freshly zeroed heap never see -- follows the pattern instead.
 (Found nothing when written, round 5; it stays as the guard.)
 
-And no kernel WRITES outside the buffers it was handed: the same cases with every device `torch.empty` of the host layer
-(outputs, gradients, workspaces, CSR arrays) wrapped in two 64 KB guard bands, which must be intact afterwards."""
+And no kernel WRITES outside the buffers it was handed: the same cases with every device `torch.empty` -- and `torch.empty_like`,
+`Tensor.new_empty`, `torch.zeros` -- of the host layer (outputs, gradients, workspaces, CSR arrays) wrapped in two 64 KB guard
+bands, which must be intact afterwards.
+
+The kernel families added after this file's case list was written have their cases in tests/test_gpu_poison_families.py, which
+runs them through `_heap_case` / `_guard_case` below."""
 import math
 
 import pytest
@@ -287,23 +291,41 @@ CASES["kan gat node model 4x16 hubs"] = ("split", _gat_node_model("kan", 16))   
 CASES["fastkan gat node model 4x20 hubs"] = ("split", _gat_node_model("fastkan", 20))  # wave kernels
 
 
-@pytest.mark.parametrize("case", list(CASES))
-def test_blind_to_the_heap(monkeypatch, case):
-    mode, build = CASES[case]
+def _heap_case(monkeypatch, cases, case):
+    """one entry of a case table -- ``(precision mode, build[, guarded-buffer floor])`` -- under every heap pattern"""
+    mode, build = cases[case][:2]
     monkeypatch.setenv("KAGNN_PRECISION", mode)
     module, run = build()
     _under_every_pattern(module, run, case)
 
 
+@pytest.mark.parametrize("case", list(CASES))
+def test_blind_to_the_heap(monkeypatch, case):
+    _heap_case(monkeypatch, CASES, case)
+
+
 # ---------------------------------------------------------------------------------------------------------------- guard bands
 class _GuardedEmpty:
     """`torch.empty` for device tensors = a view into a buffer with GUARD bytes of 0xA5 on both sides (the band starts at the
-    first byte after the tensor: a one-element overrun lands in it)."""
+    first byte after the tensor: a one-element overrun lands in it).  ``install`` also routes the other ways the host layer
+    allocates through it -- device `torch.empty_like`, `Tensor.new_empty` and `torch.zeros` (the guarded buffer, then zeroed)."""
     GUARD = 1 << 16
 
     def __init__(self):
         self.real = torch.empty
+        self.real_like, self.real_zeros, self.real_new = torch.empty_like, torch.zeros, torch.Tensor.new_empty
         self.live = []
+
+    def install(self, monkeypatch):
+        guard = self
+
+        def new_empty(t, *size, **kw):
+            return guard.new_empty(t, *size, **kw)
+        monkeypatch.setattr(torch, "empty", self)
+        monkeypatch.setattr(torch, "empty_like", self.empty_like)
+        monkeypatch.setattr(torch, "zeros", self.zeros)
+        monkeypatch.setattr(torch.Tensor, "new_empty", new_empty)
+        return self
 
     def __call__(self, *size, dtype=None, device=None, pin_memory=False, **kw):
         dev = None if device is None else torch.device(device)
@@ -311,13 +333,32 @@ class _GuardedEmpty:
             return self.real(*size, dtype=dtype, device=device, pin_memory=pin_memory, **kw)
         shape = tuple(size[0]) if len(size) == 1 and isinstance(size[0], (tuple, list, torch.Size)) else tuple(int(v) for v in size)
         dtype = dtype or torch.get_default_dtype()
-        nbytes = math.prod(shape) * torch.empty(0, dtype=dtype).element_size()
+        nbytes = math.prod(shape) * self.real(0, dtype=dtype).element_size()
         G = self.GUARD
         buf = self.real(G + nbytes + G, dtype=torch.uint8, device=dev)
         buf[:G].fill_(0xA5)
         buf[G + nbytes:].fill_(0xA5)
         self.live.append((buf, nbytes, shape, dtype))
         return buf[G:G + nbytes].view(dtype).view(shape)
+
+    def empty_like(self, t, *, dtype=None, device=None, **kw):
+        """a device tensor's contiguous twin (the only kind the host layer asks for); anything else is torch's own business"""
+        dev = t.device if device is None else torch.device(device)
+        if dev.type != "cuda" or kw or not t.is_contiguous() or t.layout != torch.strided:
+            return self.real_like(t, dtype=dtype, device=device, **kw)
+        return self(tuple(t.shape), dtype=dtype or t.dtype, device=dev)
+
+    def new_empty(self, t, *size, dtype=None, device=None, **kw):
+        dev = t.device if device is None else torch.device(device)
+        if dev.type != "cuda" or kw:
+            return self.real_new(t, *size, dtype=dtype, device=device, **kw)
+        return self(*size, dtype=dtype or t.dtype, device=dev)
+
+    def zeros(self, *size, dtype=None, device=None, **kw):
+        dev = None if device is None else torch.device(device)
+        if dev is None or dev.type != "cuda" or kw:
+            return self.real_zeros(*size, dtype=dtype, device=device, **kw)
+        return self(*size, dtype=dtype, device=dev).zero_()
 
     def check(self, what):
         torch.cuda.synchronize()
@@ -340,21 +381,45 @@ def test_the_guard_bands_catch_an_overrun(monkeypatch):
     t.as_strided((71,), (1,)).fill_(2.0)                        # one float past the end
     with pytest.raises(AssertionError, match="past the end"):
         guarded.check("overrun")
+    monkeypatch.undo()
+    # the other allocators of the host layer, each caught by the same one-float overrun inside a torch-owned buffer
+    like = torch.ones((10, 7), dtype=torch.float32, device=DEV)
+    makers = {"torch.empty_like": lambda: torch.empty_like(like), "Tensor.new_empty": lambda: like.new_empty((10, 7)),
+              "torch.zeros": lambda: torch.zeros((10, 7), dtype=torch.float32, device=DEV)}
+    for name, make in makers.items():
+        guarded = _GuardedEmpty().install(monkeypatch)
+        t = make()
+        assert t.shape == (10, 7) and t.dtype == torch.float32 and t.is_contiguous() and t.data_ptr() % 512 == 0, name
+        assert name != "torch.zeros" or not bool(t.any())
+        t.fill_(1.0)
+        assert guarded.check(name) == 1, name
+        t.as_strided((71,), (1,)).fill_(2.0)
+        with pytest.raises(AssertionError, match="past the end"):
+            guarded.check(name)
+        monkeypatch.undo()
+        assert torch.empty_like is guarded.real_like and torch.zeros is guarded.real_zeros and "new_empty" not in vars(torch.Tensor), name
+
+
+def _guard_case(monkeypatch, cases, case):
+    """one entry of a case table with every device allocation of the host layer between guard bands.  At least three guarded
+    buffers per case; a raw-op case states the number its op really allocates as the entry's third element."""
+    mode, build = cases[case][:2]
+    floor = cases[case][2] if len(cases[case]) > 2 else 3
+    monkeypatch.setenv("KAGNN_PRECISION", mode)
+    module, run = build()
+    run()                                                       # (first use: caches, packs)
+    if module is not None:
+        module.zero_grad(set_to_none=True)
+        with torch.no_grad():
+            for p in module.parameters():
+                p.add_(0.0)                                     # packs are rebuilt inside guarded buffers too
+    guarded = _GuardedEmpty().install(monkeypatch)
+    out = run()
+    n = guarded.check(case)
+    monkeypatch.undo()
+    assert n >= floor and all(bool(torch.isfinite(t.float()).all()) for t in out), (case, n)
 
 
 @pytest.mark.parametrize("case", list(CASES))
 def test_writes_stay_inside_their_buffers(monkeypatch, case):
-    mode, build = CASES[case]
-    monkeypatch.setenv("KAGNN_PRECISION", mode)
-    module, run = build()
-    run()                                                       # (first use: caches, packs)
-    module.zero_grad(set_to_none=True)
-    with torch.no_grad():
-        for p in module.parameters():
-            p.add_(0.0)                                         # packs are rebuilt inside guarded buffers too
-    guarded = _GuardedEmpty()
-    monkeypatch.setattr(torch, "empty", guarded)
-    out = run()
-    n = guarded.check(case)
-    monkeypatch.undo()
-    assert n >= 3 and all(bool(torch.isfinite(t.float()).all()) for t in out), (case, n)
+    _guard_case(monkeypatch, CASES, case)

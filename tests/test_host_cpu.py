@@ -323,6 +323,39 @@ def test_gat_kernel_cases_reach_every_gat_kernel_and_variant():
     assert tg.gat_kernels(1, 129, 10, 10, 1) == {"refused"}
 
 
+def test_every_newer_kernel_family_has_a_heap_and_a_guard_case():
+    """tests/test_gpu_poison_families.py registers one builder or more per kernel family that tests/test_gpu_poison.py's own case
+    list predates; both of its tests run over the whole table, so a registered case IS a heap case and a guard case.  Without a GPU:
+    no family has lost its cases, every case belongs to a family, the source each family is named for is still there, the eleven
+    kagnn::* ops are all called, and a lowered guarded-buffer floor is stated only by cases that run raw ops."""
+    import test_gpu_poison as tp
+    import test_gpu_poison_families as tf
+    sources = {"linear": ["linear.hip"], "high order": ["kan_high_order.hip"], "edge norms": ["kan_edge.hip", "fastkan_edge.hip"],
+               "attention": ["attention.hip"], "grid refinement": ["kan_grid.hip"], "edge gradient": ["aggregate_edge.hip"],
+               "classification": ["classify.hip"], "node classification": ["nodeclass.hip"], "regression": ["regress.hip", "loss.hip"],
+               "device datasets": ["batch.hip", "csr.hip"], "primitives": ["aggregate.hip", "aggregate_bf16.hip"],
+               "library ops": ["api.hip"], "overlap": ["fused_calls.hip"], "parts": ["kan_split_bwd.hip"]}
+    assert set(tf.FAMILIES) == set(sources), sorted(set(tf.FAMILIES) ^ set(sources))
+    for family, files in sources.items():
+        assert tf.FAMILIES[family], f"no heap / guard case is left for the family '{family}'"
+        for name in files:
+            assert os.path.exists(os.path.join(ROOT, "kagnn_amd", "csrc", name)), name
+    listed = [c for cases in tf.FAMILIES.values() for c in cases]
+    assert sorted(listed) == sorted(tf.CASES) and not set(tf.CASES) & set(tp.CASES)
+    assert len(tf.FAMILIES["edge norms"]) >= 4 and len(tf.FAMILIES["attention"]) >= 4 and len(tf.FAMILIES["linear"]) >= 6
+    from kagnn_amd import library
+    ops_registered = sorted(n for n in tf.LIBRARY_OPS if hasattr(library, n))
+    assert ops_registered == sorted(tf.LIBRARY_OPS) and len(ops_registered) == 11
+    assert [f"kagnn::{n} eager" for n in tf.LIBRARY_OPS] == tf.FAMILIES["library ops"]
+    for name, (mode, build, floor) in tf.CASES.items():
+        assert mode in ("split", "half", "fp32") and callable(build)
+        raw = name in tf.FAMILIES["library ops"] or name.startswith(("segment pool", "harness.Adam"))
+        assert floor == 3 or (raw and 1 <= floor), (name, floor)
+    for fn in (tf.test_blind_to_the_heap, tf.test_writes_stay_inside_their_buffers):
+        (mark,) = [m for m in fn.pytestmark if m.name == "parametrize"]
+        assert list(mark.args[1]) == list(tf.CASES)
+
+
 def test_assert_close_scales_by_the_reference_itself_and_can_fail():
     """tests/helpers.assert_close (round 5): the bound is relative to max|reference| of the tensor, so small
     tensors are held to the same RELATIVE accuracy as large ones; zeros and 1e-3 perturbations are rejected whatever the
