@@ -170,14 +170,23 @@ def load_kanlinear(layer, z, prefix, device):
     return layer.to(device)
 
 
-def oracle_kan_linear_fwd_bwd(x, gy, p, k, dtype=torch.float64):
-    """fp64 'truth' through the oracle (same algorithm as the reference, wider arithmetic)."""
-    x = x.detach().cpu().to(dtype).requires_grad_(True)
+def oracle_kan_linear_fwd_bwd(x, gy, p, k, dtype=torch.float64, chunk=None):
+    """fp64 'truth' through the oracle (same algorithm as the reference, wider arithmetic).  ``chunk``: rows per pass (the rows of
+    a KANLinear are independent and the parameter gradients add up over them in ``dtype``) -- for row counts whose dense basis
+    tensors would not fit at once."""
+    x = x.detach().cpu().to(dtype)
+    gy = gy.detach().cpu().to(dtype)
     ps = {n: (v.detach().cpu().to(dtype).requires_grad_(True) if n != "grid" else v.detach().cpu().to(dtype))
           for n, v in p.items()}
-    y = orc.kan_linear_forward(x, ps["base_weight"], ps["spline_weight"], ps["spline_scaler"], ps["grid"], k)
-    y.backward(gy.detach().cpu().to(dtype))
-    return y.detach(), x.grad, {n: ps[n].grad for n in ("base_weight", "spline_weight", "spline_scaler")}
+    ys, gxs = [], []
+    step = x.size(0) if not chunk else int(chunk)
+    for lo in range(0, max(x.size(0), 1), max(step, 1)):
+        xc = x[lo:lo + step].clone().requires_grad_(True)
+        y = orc.kan_linear_forward(xc, ps["base_weight"], ps["spline_weight"], ps["spline_scaler"], ps["grid"], k)
+        y.backward(gy[lo:lo + step])
+        ys.append(y.detach())
+        gxs.append(xc.grad)
+    return torch.cat(ys), torch.cat(gxs), {n: ps[n].grad for n in ("base_weight", "spline_weight", "spline_scaler")}
 
 
 def oracle_node_model_fwd_bwd(x, edge_index, state, gout, arch, conv_type, mp_layers, spline_order=3, chunk=None,
@@ -266,17 +275,52 @@ def round11(t):
     return torch.ldexp(torch.round(m * 2048.0) / 2048.0, e)
 
 
+def half_routing(fin, fout, G, k):
+    """(round_fwd, round_dx, round_dw): which of a KANLinear's three GEMMs KAGNN_PREC_HALF runs as ONE fp16 product per fp32 product.
+    Everything else runs the split mode's three-product kernel on the same pack (host.h: ModeScope rewrites the mode to SPLIT and
+    raises a flag that only the launchers below look at).  Restated from the host code, once:
+      forward            kan_sparse_fwd.hip: launch_sparse (``!SH && !NARROW && OT != 4``), launch_sparse_parts -- cubic, <= 8
+                         coefficients (SH), more than 32 inputs (NARROW), and the 64-wide output block: sp_out_blk takes the
+                         128-wide one (OT = 4) when ``out % 128 == 0`` (KAGNN_FWD_WIDE, on by default)
+      input gradient     kan_split_bwd.hip: launch_dx_pp (``K == 3 && !GEN && Q2 <= 2``) -- cubic, <= 8 coefficients (GEN: more, or an
+                         accumulating output block beyond the first 128) and <= 64 outputs (split_common.h: dx_q2)
+      weight gradients   kan_split_bwd.hip: kan_split_dw_any (``half = g_half_products && K == 3 && !sh``) -- cubic, <= 8
+                         coefficients, any width (9..16 coefficients leave earlier through kan_dw_w2_ok; the shared-expansion kernel
+                         is switched off while the flag is up)
+    More than 16 coefficients run as a sum of layers over coefficient groups of <= 16 (ops.kan_linear, ``coefficient_groups`` below)
+    and every group is routed on its own: groups of 9..16 coefficients run three products, but 17 coefficients split 9 + 8 and the
+    second group is a cubic 8-coefficient layer -- single-product.  This function is asked per group (``half_mode_oracle`` splits)."""
+    lean = k == 3 and G + k <= 8
+    return (lean and fin > 32 and fout % 128 != 0, lean and fout <= 64, lean)
+
+
+def coefficient_groups(n_coef):
+    """[(first coefficient, count)]: how ops.kan_linear cuts a layer of more than 16 coefficients into consecutive groups of <= 16 under
+    the split-like modes (one group otherwise)"""
+    groups = -(-n_coef // 16)
+    size, extra = divmod(n_coef, groups)
+    out, c0 = [], 0
+    for g in range(groups):
+        cg = size + (1 if g < extra else 0)
+        out.append((c0, cg))
+        c0 += cg
+    return out
+
+
 class _HalfKanLinear(torch.autograd.Function):
-    """what KAGNN_PREC_HALF computes for one KANLinear, in fp64: every GEMM of the layer (forward, input gradient, weight gradient)
-    on operands that were evaluated exactly and rounded ONCE -- bases, SiLU, the scaled spline weight (formed in fp32 like the pack
-    kernel forms it), the base weight, gy.  The basis DERIVATIVES and SiLU' of the input gradient, the chain rule through
-    spline_scaler and all accumulation stay exact.  This is not the gradient of the rounded forward; it is the mode's definition."""
+    """what KAGNN_PREC_HALF computes for one KANLinear, in fp64: every GEMM of the layer that ``flags`` = (forward, input gradient,
+    weight gradient) marks as single-product, on operands that were evaluated exactly and rounded ONCE -- bases, SiLU, the scaled
+    spline weight (formed in fp32 like the pack kernel forms it), the base weight, gy.  The basis DERIVATIVES and SiLU' of the input
+    gradient, the chain rule through spline_scaler and all accumulation stay exact; a GEMM whose flag is down is the plain fp64
+    one.  This is not the gradient of the rounded forward; it is the mode's definition."""
 
     @staticmethod
-    def forward(ctx, x, base_weight, spline_weight, spline_scaler, knots, spline_order):
+    def forward(ctx, x, base_weight, spline_weight, spline_scaler, knots, spline_order, flags=(True, True, True)):
         ctx.save_for_backward(x, base_weight, spline_weight, spline_scaler, knots)
-        ctx.k = spline_order
+        ctx.k, ctx.flags = spline_order, flags
         n, out = x.size(0), base_weight.size(0)
+        if not flags[0]:
+            return orc_kan_linear_forward(x, base_weight, spline_weight, spline_scaler, knots, spline_order)
         wcat = spline_weight if spline_scaler is None else (spline_weight.float() * spline_scaler.float().unsqueeze(-1)).to(x.dtype)
         br = round11(orc.bspline_bases(x, knots, spline_order))
         return (torch.nn.functional.linear(round11(torch.nn.functional.silu(x)), round11(base_weight))
@@ -286,35 +330,62 @@ class _HalfKanLinear(torch.autograd.Function):
     def backward(ctx, gy):
         x, bw, sw, sc, knots = ctx.saved_tensors
         k = ctx.k
+        _, rdx, rdw = ctx.flags
         n, out = x.size(0), bw.size(0)
-        wcat = sw if sc is None else (sw.float() * sc.float().unsqueeze(-1)).to(x.dtype)
-        gyr = round11(gy)
         # input gradient: D[n, f, c] = sum_o gyr[n, o] Wr[o, f, c], contracted with the exact basis derivatives; base branch likewise
-        d = (gyr @ round11(wcat).view(out, -1)).view(n, x.size(1), -1)
+        if rdx:
+            wcat = sw if sc is None else (sw.float() * sc.float().unsqueeze(-1)).to(x.dtype)
+            ga, wa, ba = round11(gy), round11(wcat), round11(bw)
+        else:
+            ga, wa, ba = gy, (sw if sc is None else sw * sc.unsqueeze(-1)).detach(), bw.detach()   # (constants of the graphs built below)
+        d = (ga @ wa.view(out, -1)).view(n, x.size(1), -1)
         with torch.enable_grad():
             xx = x.detach().requires_grad_(True)
             (orc.bspline_bases(xx, knots, k) * d).sum().backward()
             gx = xx.grad
             xs = x.detach().requires_grad_(True)
-            (torch.nn.functional.silu(xs) * (gyr @ round11(bw))).sum().backward()
+            (torch.nn.functional.silu(xs) * (ga @ ba)).sum().backward()
             gx = gx + xs.grad
         # weight gradient
-        br = round11(orc.bspline_bases(x, knots, k))
-        gcat = (gyr.t() @ br.view(n, -1)).view(out, x.size(1), -1)
-        g_bw = gyr.t() @ round11(torch.nn.functional.silu(x))
+        r = round11 if rdw else (lambda t: t)
+        gb = r(gy)
+        br = r(orc.bspline_bases(x, knots, k))
+        gcat = (gb.t() @ br.view(n, -1)).view(out, x.size(1), -1)
+        g_bw = gb.t() @ r(torch.nn.functional.silu(x))
         if sc is None:
-            return gx, g_bw, gcat, None, None, None
-        return gx, g_bw, gcat * sc.unsqueeze(-1), (gcat * sw).sum(-1), None, None
+            return gx, g_bw, gcat, None, None, None, None
+        return gx, g_bw, gcat * sc.unsqueeze(-1), (gcat * sw).sum(-1), None, None, None
+
+
+orc_kan_linear_forward = orc.kan_linear_forward      # the plain layer, whatever a context manager below has put in its place
 
 
 class half_mode_oracle:
     """context manager: inside it ``oracle.kan_linear_forward`` is the restatement of KAGNN_PREC_HALF above (every KANLinear of every
-    chain / conv / model the oracle evaluates).  The HIP path must agree with THIS oracle at the fp32 contract (parity proper); its
-    distance from the unrounded oracle is a property of the mode, reported separately (README: numerical contract)."""
+    chain / conv / model the oracle evaluates).  ``route``: (in, out, G, k) -> which of the layer's three GEMMs are rounded; the
+    default is the device's routing (``half_routing``), so the three-product GEMMs of a mixed layer stay plain fp64 and chains,
+    convolutions and models get the right expectation per layer.  The HIP path must agree with THIS oracle at the fp32 contract
+    (parity proper); its distance from the unrounded oracle is a property of the mode, reported separately (README: numerical
+    contract)."""
+
+    def __init__(self, route=half_routing):
+        self.route = route
 
     def __enter__(self):
         self._orig = orc.kan_linear_forward
-        orc.kan_linear_forward = lambda x, bw, sw, sc, knots, k: _HalfKanLinear.apply(x, bw, sw, sc, knots, k)
+        route = self.route
+
+        def kan_linear_forward(x, bw, sw, sc, knots, k):
+            y = None
+            for g, (c0, cg) in enumerate(coefficient_groups(sw.size(2))):
+                flags = tuple(bool(f) for f in route(x.size(1), bw.size(0), cg - k, k))
+                # a uniform B-spline basis function depends on its own k + 2 knots only: the group's layer on its slice of the knots; the
+                # SiLU branch rides with the first group (a zero base weight elsewhere: it rounds to zero and its gradient is dropped)
+                part = _HalfKanLinear.apply(x, bw if g == 0 else torch.zeros_like(bw).detach(), sw[:, :, c0:c0 + cg], sc,
+                                            knots[:, c0:c0 + cg + k + 1], k, flags)
+                y = part if y is None else y + part
+            return y
+        orc.kan_linear_forward = kan_linear_forward
         return self
 
     def __exit__(self, *exc):
@@ -346,6 +417,93 @@ def half_parity(got, rounded, plain, what, l2_tol=HALF_L2_TOL, flip_tol=HALF_FLI
     lp = l2_rel(got, plain)
     check(5.0 * lr <= lp, what + ": the rounding oracle must explain the result at least 5x better than the unrounded one", (lr, lp))
     return lr, lp
+
+
+# A layer's distance from the UNROUNDED oracle, relative to the tensor's maximum: above the three-product kernels' 1e-6 by construction
+# (the floor proves that the single-product instantiation ran), below ~6 x 2^-11 (operand roundings add up over two operands and the
+# two branches)
+HALF_MODE_FLOOR, HALF_MODE_CEIL = 3e-5, 3e-3
+SINGLE, THREE = "single-product", "three-product"
+KAN_GRADS = ("base_weight", "spline_weight", "spline_scaler")
+HALF_REPORT = {}     # case -> tensor -> class and distances; tests/test_gpu_half.py: test_zz_half_mode_report writes it out
+
+
+def half_classes(code):
+    """'STS' -> the class of y, gx and the three weight gradients of one KANLinear case (S: single-product, T: three-product), as the
+    case tables of tests/test_gpu_half*.py write it down"""
+    c = {"S": SINGLE, "T": THREE}
+    return {"y": c[code[0]], "gx": c[code[1]], **{k: c[code[2]] for k in KAN_GRADS}}
+
+
+def half_layer_oracles(x, gy, p, k, code, chunk=None):
+    """(plain, rounded): y, gx and the weight gradients of one KANLinear from the unrounded fp64 oracle and from the rounding oracle
+    that rounds exactly the GEMMs ``code`` marks single-product"""
+    flags = tuple(ch == "S" for ch in code)
+    y, gx, g = oracle_kan_linear_fwd_bwd(x, gy, p, k, chunk=chunk)
+    with half_mode_oracle(lambda *a: flags):
+        yr, gxr, gr = oracle_kan_linear_fwd_bwd(x, gy, p, k, chunk=chunk)
+    return {"y": y, "gx": gx, **g}, {"y": yr, "gx": gxr, **gr}
+
+
+def kanlinear_on_device(p, G, k, mode, device="cuda:0"):
+    """a ``kagnn_amd.KANLinear`` with state ``p`` on the device, at precision ``mode``"""
+    import kagnn_amd
+    fo, fi = p["base_weight"].shape
+    layer = kagnn_amd.KANLinear(fi, fo, grid_size=G, spline_order=k)
+    layer.load_state_dict(p)
+    layer = layer.to(device)
+    layer.precision = mode
+    return layer
+
+
+def kanlinear_fwd_bwd(p, x, gy, G, k, mode, device="cuda:0"):
+    """y, gx and the three weight gradients of that layer on the device under precision ``mode``"""
+    layer = kanlinear_on_device(p, G, k, mode, device)
+    xd = x.to(device).requires_grad_(True)
+    y = layer(xd)
+    y.backward(gy.to(device))
+    return {"y": y.detach(), "gx": xd.grad, **{k_: getattr(layer, k_).grad for k_ in KAN_GRADS}}
+
+
+def max_rel(a, b):
+    a, b = a.detach().double().cpu(), b.detach().double().cpu()
+    return float((a - b).abs().max() / b.abs().max())
+
+
+def half_statement(got, plain, rounded, classes, tag, split=None, l2_tol=HALF_L2_TOL, flip_tol=HALF_FLIP_TOL, rows=("gx",), floor=True,
+                   tol=TOL):
+    """The statement of KAGNN_PREC_HALF per output tensor.  ``classes[name]`` says which it is:
+    SINGLE -- ``half_parity`` against the rounding oracle (two norms and the 5x separation) and, with ``floor``, a max-norm distance
+              from the unrounded oracle in [HALF_MODE_FLOOR, HALF_MODE_CEIL]: the single-product kernel ran, and nothing worse;
+    THREE  -- the ordinary layer bound against the unrounded oracle and the very bits of ``split[name]``, the same operands under
+              PREC_SPLIT: it is the same kernel reading the same pack.
+    ``floor``: True / False, or the names of the tensors the floor is asked of.
+    ``rows``: tensors compared row-normalised (each row by the rounding oracle's maximum of that row) -- gx wherever the rows of gy
+    span decades, since every row is rounded at its own scale.  Distances go to HALF_REPORT[tag]."""
+    rep = HALF_REPORT.setdefault(tag, {})
+    for name, g in got.items():
+        g, r, p = (t.detach().double().cpu() for t in (g, rounded[name], plain[name]))
+        if name in rows:
+            rs = r.abs().amax(1, keepdim=True).clamp(min=1e-300)
+            g, r, p = g / rs, r / rs, p / rs
+        what = f"{tag}.{name}" + (" (per row)" if name in rows else "")
+        # the distance from the unrounded oracle is relative to the tensor's maximum, as HALF_MODE_FLOOR / _CEIL are defined (a row whose
+        # own maximum is a cancelling sum is further away on its own scale: recorded for the row-normalised tensors, not bounded)
+        rep[name] = {"class": classes[name], "max_norm_vs_unrounded": max_rel(got[name], plain[name]), "max_norm_vs_rounding_oracle": max_rel(g, r),
+                     "l2_vs_rounding_oracle": l2_rel(g, r), "l2_vs_unrounded": l2_rel(g, p)}
+        if name in rows:
+            rep[name]["max_norm_vs_unrounded (per row)"] = max_rel(g, p)
+        if classes[name] == SINGLE:
+            half_parity(g, r, p, what, l2_tol, flip_tol)
+            d = rep[name]["max_norm_vs_unrounded"]
+            if floor is True or (floor and name in floor):
+                check(HALF_MODE_FLOOR <= d <= HALF_MODE_CEIL, what + ": distance from the unrounded oracle", d)
+        else:
+            assert classes[name] == THREE, classes[name]
+            assert_close(got[name], plain[name], tol, what=f"{tag}.{name} (three-product) vs the unrounded oracle")
+            check(split is not None and torch.equal(got[name], split[name]), f"{tag}.{name}: the bits of PREC_SPLIT on the same operands",
+                  None if split is None else float((got[name] - split[name]).abs().max()))
+    return rep
 
 
 # ---------------------------------------------------------------------------------- feature-sharded FastKAN layer, restated

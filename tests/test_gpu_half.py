@@ -3,6 +3,10 @@ the split-precision kernels with ONE fp16 product per fp32 product.  Parity stat
 SAME once-rounded operands (tests/helpers.py: half_mode_oracle) -- 5e-5 in L2, 3e-4 in the max norm (isolated rounding-tie flips), and at least
 5x closer than the unrounded oracle (observed: 20-60x); its distance from the unrounded fp64
 oracle (~3e-4, fp16's 2^-11 per operand) is a property of the mode, bounded and reported here (gpurun_out/half_mode_errors.json)."""
+# The mode is not one kernel: which of a layer's three GEMMs has a single-product instantiation is a routing table
+# (tests/helpers.py: half_routing), and every case below writes down the class it expects of each tensor -- single-product tensors
+# meet the statement above, three-product tensors the ordinary fp64 bound AND the bits of PREC_SPLIT (helpers.half_statement).
+# tests/test_gpu_half_variants.py: one case per single-product instantiation, edge inputs, and the graph-level one-call paths.
 import json
 import os
 
@@ -12,16 +16,14 @@ import torch
 import kagnn_amd
 from kagnn_amd import ops
 from oracle import kan_oracle as orc
-from helpers import (CONTRACT, HALF_FLIP_TOL as FLIP_TOL, HALF_L2_TOL as L2_TOL, assert_close, check, half_mode_oracle,
-                     half_parity as _parity, oracle_kan_linear_fwd_bwd, oracle_node_model_fwd_bwd, prenorm_bias_noise)
+from helpers import (HALF_FLIP_TOL as FLIP_TOL, HALF_L2_TOL as L2_TOL, HALF_MODE_CEIL as MODE_CEIL, HALF_MODE_FLOOR as MODE_FLOOR,
+                     HALF_REPORT as REPORT, check, half_classes, half_layer_oracles, half_mode_oracle, half_parity as _parity, half_routing,
+                     half_statement, kanlinear_fwd_bwd, oracle_node_model_fwd_bwd, prenorm_bias_noise)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-# L2_TOL / FLIP_TOL: the mode's two-norm parity statement, tests/helpers.py (half_parity)
-MODE_FLOOR, MODE_CEIL = 3e-5, 3e-3      # a layer's distance from the UNROUNDED oracle, relative to the tensor's maximum: above the
-                                        # three-product kernels' 1e-6 by construction (proves the single-product instantiation ran),
-                                        # below ~6 x 2^-11 (operand roundings add up over two operands and the two branches)
-REPORT = {}
+# L2_TOL / FLIP_TOL: the mode's two-norm parity statement, tests/helpers.py (half_parity); MODE_FLOOR / MODE_CEIL: a layer's distance
+# from the UNROUNDED oracle (tests/helpers.py, beside half_statement)
 
 
 def _rel(a, b):
@@ -34,49 +36,30 @@ def _set_precision(module, mode):
             m.precision = mode
 
 
-@pytest.mark.parametrize("n,fi,fo,G,covered", [(4096, 64, 64, 5, True), (5000, 128, 64, 5, True), (3001, 64, 40, 5, True),
-                                                (1037, 33, 17, 4, True), (777, 320, 40, 5, True), (2000, 64, 32, 3, True),
-                                                (999, 24, 40, 5, False), (1500, 64, 64, 8, False), (800, 64, 256, 5, False)],
-                         ids=lambda v: str(v))
-def test_half_mode_kanlinear_vs_rounding_oracle(n, fi, fo, G, covered):
-    """one KANLinear, forward and all gradients.  ``covered``: shapes with a HALF instantiation of all three kernels (cubic,
-    <= 8 coefficients, > 32 inputs for the forward, <= 64 outputs for the input gradient); the others run the three-product
-    kernels (narrow first layers, two-window layers, > 64 outputs) -- more accurate, so they must meet the UNROUNDED oracle."""
+# classes of (y, gx, weight gradients): S single-product, T three-product.  999x24x40: a narrow forward (<= 32 inputs) beside the
+# single-product Q2 = 2 input gradient and the RS = 2 weight gradient; 1500x64x64 G=8: 11 coefficients, the two-window kernels
+# throughout; 800x64x256: the wide (128-output) forward block, an input gradient over two accumulating 128-output blocks, and the
+# single-product weight gradient over four 64-output chunks
+KANLINEAR_CASES = [(4096, 64, 64, 5, "SSS"), (5000, 128, 64, 5, "SSS"), (3001, 64, 40, 5, "SSS"), (1037, 33, 17, 4, "SSS"), (777, 320, 40, 5, "SSS"),
+                   (2000, 64, 32, 3, "SSS"), (999, 24, 40, 5, "TSS"), (1500, 64, 64, 8, "TTT"), (800, 64, 256, 5, "TTS")]
+
+
+# (the ids these cases had while a ``covered`` flag stood where the classes stand now: True = single-product throughout)
+@pytest.mark.parametrize("n,fi,fo,G,code", KANLINEAR_CASES, ids=[f"{c[0]}-{c[1]}-{c[2]}-{c[3]}-{c[4] == 'SSS'}" for c in KANLINEAR_CASES])
+def test_half_mode_kanlinear_vs_rounding_oracle(n, fi, fo, G, code):
+    """one KANLinear, forward and all gradients, every tensor at the statement of the class the table gives it (and the table is the
+    routing the host code implements: helpers.half_routing)."""
+    assert tuple(c == "S" for c in code) == half_routing(fi, fo, G, 3), (code, half_routing(fi, fo, G, 3))
     gen = torch.Generator().manual_seed(n + fi)
     p = orc.init_kan_linear(fi, fo, G, 3, gen)
     x = torch.randn(n, fi, generator=gen) * 0.8
     x[::7, 0] = 3.0                                        # outside the spline support
     gy = torch.randn(n, fo, generator=gen) * torch.logspace(-3, 2, n).unsqueeze(1)      # row scales over five decades
-    layer = kagnn_amd.KANLinear(fi, fo, grid_size=G, spline_order=3)
-    layer.load_state_dict(p)
-    layer = layer.to(DEV)
-    layer.precision = ops.PREC_HALF
-    xd = x.to(DEV).requires_grad_(True)
-    y = layer(xd)
-    y.backward(gy.to(DEV))
-    got = {"y": y, "gx": xd.grad, **{k: getattr(layer, k).grad for k in ("base_weight", "spline_weight", "spline_scaler")}}
-    y64, gx64, g64 = oracle_kan_linear_fwd_bwd(x, gy, p, 3)
-    plain = {"y": y64, "gx": gx64, **g64}
-    tag = f"half.kanlinear({n},{fi},{fo},G={G})"
-    if covered:
-        with half_mode_oracle():
-            yr, gxr, gr = oracle_kan_linear_fwd_bwd(x, gy, p, 3)
-        rounded = {"y": yr, "gx": gxr, **gr}
-        # gx: the rows' scales span five decades and each row is rounded at its own scale -> compare row-wise
-        l2 = {}
-        for k in got:
-            if k == "gx":       # the rows' scales span five decades and each row is rounded at its own scale -> compare row-normalised
-                rs = rounded[k].abs().amax(1, keepdim=True).clamp(min=1e-300)
-                l2[k] = _parity(got[k].detach().cpu().double() / rs, rounded[k] / rs, plain[k] / rs, f"{tag}.{k} (per row)")
-            else:
-                l2[k] = _parity(got[k], rounded[k], plain[k], f"{tag}.{k}")
-        dist = {k: _rel(got[k], plain[k]) for k in ("y", "base_weight", "spline_weight", "spline_scaler")}
-        REPORT[tag] = {"max_norm_vs_unrounded": dist, "l2_vs_rounding_oracle__vs_unrounded": l2}
-        for k, v in dist.items():
-            check(MODE_FLOOR <= v <= MODE_CEIL, f"{tag}.{k}: distance from the unrounded oracle", v)
-    else:
-        for k in ("y", "base_weight", "spline_weight", "spline_scaler"):
-            check(_rel(got[k], plain[k]) <= MODE_CEIL, f"{tag}.{k}: a shape without a single-product instantiation", _rel(got[k], plain[k]))
+    got = kanlinear_fwd_bwd(p, x, gy, G, 3, ops.PREC_HALF)
+    split = kanlinear_fwd_bwd(p, x, gy, G, 3, ops.PREC_SPLIT) if "T" in code else None
+    plain, rounded = half_layer_oracles(x, gy, p, 3, code)
+    # gx: the rows' scales span five decades and each row is rounded at its own scale -> compared row-normalised (half_statement)
+    half_statement(got, plain, rounded, half_classes(code), f"half.kanlinear({n},{fi},{fo},G={G})", split)
 
 
 def test_half_mode_is_a_switch_not_a_fallback():

@@ -376,6 +376,68 @@ def test_assert_close_scales_by_the_reference_itself_and_can_fail():
     helpers.assert_close(z + 1e-9, z, 1e-4, what="zero reference with a noise estimate", noise=1e-4)
 
 
+def test_half_mode_statement_can_fail_and_the_routing_table_is_the_documented_one():
+    """tests/helpers.half_statement, with the oracles alone: (a) a tensor that was never rounded -- the unrounded oracle's own, i.e. what
+    a three-product kernel would deliver where a single-product one is expected -- fails the floor; (b) the rounding oracle with ONE
+    GEMM left unrounded (the weight gradient's) fails the L2 bound or the 5x separation for every weight gradient at (1000, 24, 40),
+    while its y and gx pass; (c) the routing table of helpers.half_routing at the shapes the GPU cases are built around."""
+    import helpers
+    from oracle import kan_oracle as orc
+    if helpers.SOFT:
+        pytest.skip("KAGNN_TEST_SOFT=1 records instead of raising")
+    n, fi, fo, G, k = 1000, 24, 40, 5, 3
+    assert helpers.half_routing(fi, fo, G, k) == (False, True, True)
+    gen = torch.Generator().manual_seed(n + fi)
+    p = orc.init_kan_linear(fi, fo, G, k, gen)
+    x = torch.randn(n, fi, generator=gen) * 0.8
+    gy = torch.randn(n, fo, generator=gen) * torch.logspace(-3, 2, n).unsqueeze(1)
+    plain, rounded = helpers.half_layer_oracles(x, gy, p, k, "TSS")
+    cls = helpers.half_classes("TSS")
+    try:
+        assert torch.equal(rounded["y"], plain["y"])                     # the narrow forward is three-product: left alone
+        helpers.half_statement({"gx": rounded["gx"]}, plain, rounded, cls, "teeth")       # the right answer passes, floor included
+        for name in ("gx",) + helpers.KAN_GRADS:
+            # (a) never rounded, judged by a rounding oracle that agrees with it: only the floor can object
+            with pytest.raises(AssertionError, match="distance from the unrounded oracle"):
+                helpers.half_statement({name: plain[name]}, plain, plain, cls, "teeth")
+            with pytest.raises(AssertionError):                           # ... and against the real rounding oracle it fails parity too
+                helpers.half_statement({name: plain[name]}, plain, rounded, cls, "teeth")
+        # a GEMM whose flag is down is the plain oracle's, and leaves the other two as they are
+        none = helpers.half_layer_oracles(x, gy, p, k, "TTT")[1]
+        for name in plain:
+            helpers.assert_close(none[name], plain[name], 1e-12, what="unflagged oracle " + name)
+        assert all(torch.equal(rounded[name], helpers.half_layer_oracles(x, gy, p, k, "SSS")[1][name]) for name in ("gx",) + helpers.KAN_GRADS)
+        # (b) one operand left unrounded
+        _, mutant = helpers.half_layer_oracles(x, gy, p, k, "TST")
+        helpers.half_statement({"gx": mutant["gx"]}, plain, rounded, cls, "teeth")
+        for name in helpers.KAN_GRADS:
+            helpers.assert_close(mutant[name], plain[name], 1e-12, what="weight gradients beside a rounded input gradient: " + name)
+        _, beside = helpers.half_layer_oracles(x, gy, p, k, "TTS")
+        for name in helpers.KAN_GRADS:                      # ... and rounded weight gradients beside an unrounded input gradient
+            assert torch.equal(beside[name], rounded[name]), name
+        for name in helpers.KAN_GRADS:
+            with pytest.raises(AssertionError):
+                helpers.half_statement({name: mutant[name]}, plain, rounded, cls, "teeth")
+            # ... by the L2 bound AND the separation, not only by the max norm (which objects first, at 3.4e-4 against 3e-4)
+            lr, lp = helpers.l2_rel(mutant[name], rounded[name]), helpers.l2_rel(mutant[name], plain[name])
+            assert lr > 4 * helpers.HALF_L2_TOL and 5.0 * lr > lp, (name, lr, lp)
+            with pytest.raises(AssertionError, match="L2 distance from the rounding oracle"):
+                helpers.half_parity(mutant[name], rounded[name], plain[name], "teeth", flip_tol=1.0)
+        # a three-product tensor that is not the bits of PREC_SPLIT, or that misses the fp64 bound
+        with pytest.raises(AssertionError, match="the bits of PREC_SPLIT"):
+            helpers.half_statement({"y": plain["y"]}, plain, rounded, cls, "teeth", split={"y": plain["y"] * (1 + 1e-7)})
+        with pytest.raises(AssertionError, match="three-product"):
+            helpers.half_statement({"y": plain["y"] * (1 + 1e-4)}, plain, rounded, cls, "teeth", split={"y": plain["y"] * (1 + 1e-4)})
+    finally:
+        helpers.HALF_REPORT.pop("teeth", None)
+    # (c) (in, out, G, k) -> single-product (forward, input gradient, weight gradients)
+    for shape, want in {(64, 64, 5, 3): (True, True, True), (33, 17, 4, 3): (True, True, True), (32, 64, 5, 3): (False, True, True),
+                        (64, 128, 5, 3): (False, False, True), (64, 100, 5, 3): (True, False, True), (72, 192, 5, 3): (True, False, True),
+                        (64, 256, 5, 3): (False, False, True), (64, 65, 5, 3): (True, False, True), (64, 64, 6, 3): (False, False, False),
+                        (64, 64, 5, 2): (False, False, False), (40, 70, 20, 3): (False, False, False)}.items():
+        assert helpers.half_routing(*shape) == want, (shape, helpers.half_routing(*shape), want)
+
+
 def test_norm_sums_side_channel_drops_sums_when_the_parked_gradient_was_accumulated_into_in_place():
     """ops.NormSums: the parked column sums describe the gradient tensor AS IT WAS when the next layer's aggregation
     wrote it.  Identity of storage is not enough -- an engine that accumulates a second consumer's gradient into the same tensor
