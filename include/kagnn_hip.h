@@ -55,7 +55,7 @@ extern "C" {
 #define KAGNN_DTYPE_F32 0
 #define KAGNN_DTYPE_BF16 1
 
-int kagnn_version(void);          /* 273 = 272 with kagnn_kan_grid_refit on kagnn_kan_grid_resize's kernels (up to 46 coefficients; its bits and its workspace size change); 272 = 271 + kagnn_kan_grid_resize (+ _workspace_bytes); 271 = 270 + kagnn_attention_fwd, kagnn_attention_bwd (+ _workspace_bytes); 270 = 269 + kagnn_fastkan_edge_abs_sum, kagnn_fastkan_edge_abs_sum_bwd (+ _workspace_bytes), kagnn_fastkan_edge_curves; 269 = 268 + kagnn_kan_edge_abs_sum, kagnn_kan_edge_abs_sum_bwd (+ _workspace_bytes), kagnn_kan_edge_curves; 268 = 267 + spline orders 5..KAGNN_MAX_SPLINE_ORDER in the per-operation KANLinear calls (no new entry point); 267 = 266 + kagnn_linear_fwd, kagnn_linear_bwd_input, kagnn_linear_bwd_weight (+ _workspace_bytes); 266 = 265 + kagnn_l1_loss_meter_fwd, kagnn_regression_epoch_update; 265 = 264 + kagnn_node_eval, kagnn_early_stop_update, kagnn_copy_if; 264 = 263 + kagnn_degree_one_hot, kagnn_nll_loss_fwd / _bwd; 263 = 262 + kagnn_batch_assemble; 262 = 261 - the fields edge_src, edge_dst, csr_flags of kagnn_kagin_model_t; 261 = 260 + kagnn_fastkan_fwd_stats_in_kernel; 260 = round 6: + the feature-sharded FastKAN entry points kagnn_fastkan_row_moments .. _shard_bwd_finish, + kagnn_kagin_model_*; 250 = 240 + KAGNN_PREC_HALF; 240 = 230 + kagnn_gin_kan_layer_bwd_bn_sums; 230 = 220 + the *_affine entry points of a folded BatchNorm1d; 220 = 210 + the stage timer) */
+int kagnn_version(void);          /* 276 = 275 + kagnn_k_hop_mark, kagnn_subgraph_count, kagnn_subgraph_fill (+ kagnn_subgraph_workspace_bytes); 273 = 272 with kagnn_kan_grid_refit on kagnn_kan_grid_resize's kernels (up to 46 coefficients; its bits and its workspace size change); 272 = 271 + kagnn_kan_grid_resize (+ _workspace_bytes); 271 = 270 + kagnn_attention_fwd, kagnn_attention_bwd (+ _workspace_bytes); 270 = 269 + kagnn_fastkan_edge_abs_sum, kagnn_fastkan_edge_abs_sum_bwd (+ _workspace_bytes), kagnn_fastkan_edge_curves; 269 = 268 + kagnn_kan_edge_abs_sum, kagnn_kan_edge_abs_sum_bwd (+ _workspace_bytes), kagnn_kan_edge_curves; 268 = 267 + spline orders 5..KAGNN_MAX_SPLINE_ORDER in the per-operation KANLinear calls (no new entry point); 267 = 266 + kagnn_linear_fwd, kagnn_linear_bwd_input, kagnn_linear_bwd_weight (+ _workspace_bytes); 266 = 265 + kagnn_l1_loss_meter_fwd, kagnn_regression_epoch_update; 265 = 264 + kagnn_node_eval, kagnn_early_stop_update, kagnn_copy_if; 264 = 263 + kagnn_degree_one_hot, kagnn_nll_loss_fwd / _bwd; 263 = 262 + kagnn_batch_assemble; 262 = 261 - the fields edge_src, edge_dst, csr_flags of kagnn_kagin_model_t; 261 = 260 + kagnn_fastkan_fwd_stats_in_kernel; 260 = round 6: + the feature-sharded FastKAN entry points kagnn_fastkan_row_moments .. _shard_bwd_finish, + kagnn_kagin_model_*; 250 = 240 + KAGNN_PREC_HALF; 240 = 230 + kagnn_gin_kan_layer_bwd_bn_sums; 230 = 220 + the *_affine entry points of a folded BatchNorm1d; 220 = 210 + the stage timer) */
 const char* kagnn_last_error(void);
 
 /* Stage timer -- a measurement aid, off by default (no reference counterpart: the reference times whole epochs with
@@ -104,6 +104,40 @@ int kagnn_csr_small_workspace_bytes(int64_t num_edges, size_t* bytes_host);
 int kagnn_csr_build_small(const int64_t* src, const int64_t* dst, int64_t num_edges, int64_t num_nodes, int32_t* rowptr,
                           int32_t* col, int32_t* perm, int32_t* rowptr_t, int32_t* col_t, int32_t* perm_t, int32_t* flags,
                           void* workspace, size_t workspace_bytes, void* stream);
+
+/* k-hop neighbourhoods and induced subgraphs of an indexed graph (torch_geometric.utils.k_hop_subgraph / subgraph with
+ * relabel_nodes=True, flow='source_to_target'; no counterpart in the reference, which explains nothing).  Three calls, in this
+ * order, and ONE read-back between the second and the third; nothing here synchronises the stream.  All indices int32.  Every
+ * result is a pure function of the inputs (no float, no atomic read-modify-write): two calls return the same bits.
+ *
+ * kagnn_k_hop_mark: (rowptr, col) = the parent's by-destination CSR.  hop[num_nodes]: the least number of hops from node i to any
+ *   seed ALONG edge direction (seeds: 0; not reached within num_hops: -1).  Level-synchronous, one launch per level; a frontier row
+ *   is walked by the 64 lanes of a wave.  A seed outside [0, num_nodes) sets the DEVICE int flags[0] = 1 (else 0) and is skipped:
+ *   nothing is read or written out of bounds.  num_seeds == 0, num_nodes == 0 or num_hops == 0 launch no level kernel.  num_hops == 0
+ *   turns a list of node ids (duplicates allowed) into the selection of an induced subgraph.
+ * kagnn_subgraph_count: node i is selected iff hop[i] >= 0 (any int32 array will do); an edge is kept iff both endpoints are
+ *   selected (self loops and duplicates as they are).  Takes both structures of the parent (perm_t is not read here) and leaves in
+ *   the workspace -- which BEGINS with relabel[num_nodes], the position of node i among the selected nodes in ascending id order
+ *   or -1 -- the rank of every kept edge among kept edges in ORIGINAL edge order and where each parent row starts in the subgraph
+ *   on both sides.  counts: DEVICE int32[2] = {n_sub, e_sub}, which the caller reads to size the outputs of
+ * kagnn_subgraph_fill: nodes[n_sub] int64 (ascending original ids), edge_ids[e_sub] int64 (ascending original edge ids),
+ *   edge_index_sub[2, e_sub] int64 (relabelled, in original edge order), and (rowptr, col, perm) / (rowptr_t, col_t, perm_t) of the
+ *   subgraph: bit for bit what kagnn_csr_build / kagnn_csr_build_small make from edge_index_sub -- a parent row with entries
+ *   dropped is already in stable-sort order, so nothing is sorted.  No hub segments are produced.  n_sub / e_sub must be the count
+ *   call's figures; with other figures the contents are meaningless, but nothing is written beyond n_sub + 1 row pointers, n_sub
+ *   nodes and e_sub entries.  Arrays of zero length may be NULL.
+ * Workspace of both calls (the same memory, untouched in between): kagnn_subgraph_workspace_bytes(num_nodes, num_edges). */
+int kagnn_subgraph_workspace_bytes(int64_t num_nodes, int64_t num_edges, size_t* bytes_host);
+int kagnn_k_hop_mark(const int32_t* rowptr, const int32_t* col, int64_t num_nodes, const int64_t* seeds, int64_t num_seeds,
+                     int32_t num_hops, int32_t* hop, int32_t* flags, void* stream);
+int kagnn_subgraph_count(const int32_t* hop, const int32_t* rowptr, const int32_t* col, const int32_t* perm,
+                         const int32_t* rowptr_t, const int32_t* col_t, const int32_t* perm_t, int64_t num_nodes, int64_t num_edges,
+                         void* workspace, size_t workspace_bytes, int32_t* counts, void* stream);
+int kagnn_subgraph_fill(const void* workspace, size_t workspace_bytes, const int32_t* rowptr, const int32_t* col, const int32_t* perm,
+                        const int32_t* rowptr_t, const int32_t* col_t, const int32_t* perm_t, int64_t num_nodes, int64_t num_edges,
+                        int64_t n_sub, int64_t e_sub, int64_t* nodes, int64_t* edge_ids, int64_t* edge_index_sub,
+                        int32_t* rowptr_sub, int32_t* col_sub, int32_t* perm_sub, int32_t* rowptr_t_sub, int32_t* col_t_sub,
+                        int32_t* perm_t_sub, void* stream);
 
 /* in-degree normalisation of GCN (torch_geometric gcn_norm as used by KAGCNConv,
  * node_classification_clean/models.py:31-37): dis[i] = (1 + #non-loop in-edges of i)^-1/2.

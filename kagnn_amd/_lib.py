@@ -37,6 +37,11 @@ _SIGNATURES = {
     "kagnn_csr_small_ok": (c_int32, [c_int64, c_int64]),
     "kagnn_csr_small_workspace_bytes": (c_int32, [c_int64, POINTER(c_size_t)]),
     "kagnn_csr_build_small": (c_int32, [_P, _P, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "kagnn_subgraph_workspace_bytes": (c_int32, [c_int64, c_int64, POINTER(c_size_t)]),
+    "kagnn_k_hop_mark": (c_int32, [_P, _P, c_int64, _P, c_int64, c_int32, _P, _P, _P]),
+    "kagnn_subgraph_count": (c_int32, [_P, _P, _P, _P, _P, _P, _P, c_int64, c_int64, _P, c_size_t, _P, _P]),
+    "kagnn_subgraph_fill": (c_int32, [_P, c_size_t, _P, _P, _P, _P, _P, _P, c_int64, c_int64, c_int64, c_int64,
+                                      _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "kagnn_gcn_deg_inv_sqrt": (c_int32, [_P, _P, c_int64, _P, _P]),
     "kagnn_aggregate_workspace_bytes": (c_int32, [c_int64, c_int32, POINTER(c_size_t)]),
     "kagnn_aggregate_sum": (c_int32, [_P, c_int64, _P, c_int64, _P, _P, _P, c_int64, c_int32, c_float,

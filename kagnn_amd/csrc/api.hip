@@ -84,7 +84,7 @@ using namespace kagnn;
 #pragma GCC visibility push(default)
 extern "C" {
 
-int kagnn_version(void) { return 275; }
+int kagnn_version(void) { return 276; }
 const char* kagnn_last_error(void) { return g_err; }
 
 int kagnn_stage_timer_enable(const char* only) {
@@ -160,6 +160,47 @@ int kagnn_csr_build_small(const int64_t* src, const int64_t* dst, int64_t E, int
                           int32_t* rowptr_t, int32_t* col_t, int32_t* perm_t, int32_t* flags, void* ws, size_t ws_bytes, void* stream) {
     KAGNN_CHECK_ARG(src && dst && rowptr && col && perm && rowptr_t && col_t && perm_t && flags && ws, "null array");
     return csr_build_small(src, dst, E, N, rowptr, col, perm, rowptr_t, col_t, perm_t, flags, ws, ws_bytes, as_stream(stream));
+}
+
+int kagnn_subgraph_workspace_bytes(int64_t N, int64_t E, size_t* bytes) {
+    KAGNN_CHECK_ARG(bytes != nullptr && E >= 0 && N >= 0, "null output or negative size");
+    KAGNN_CHECK_ARG(E < 2147483647LL && N < 2147483647LL, "N and E must fit int32");
+    return subgraph_workspace_bytes(N, E, bytes);
+}
+
+int kagnn_k_hop_mark(const int32_t* rowptr, const int32_t* col, int64_t N, const int64_t* seeds, int64_t num_seeds, int32_t num_hops,
+                     int32_t* hop, int32_t* flags, void* stream) {
+    KAGNN_CHECK_ARG(N >= 0 && N < 2147483647LL && num_seeds >= 0 && num_seeds < 2147483647LL, "num_nodes and num_seeds must fit int32");
+    KAGNN_CHECK_ARG(num_hops >= 0, "num_hops is negative");
+    KAGNN_CHECK_ARG(flags != nullptr && (N == 0 || hop) && (num_seeds == 0 || seeds), "null array");
+    KAGNN_CHECK_ARG(N == 0 || num_seeds == 0 || num_hops == 0 || rowptr, "null CSR array");      // (col: NULL for a graph without edges)
+    return k_hop_mark(rowptr, col, N, seeds, num_seeds, num_hops, hop, flags, as_stream(stream));
+}
+
+int kagnn_subgraph_count(const int32_t* hop, const int32_t* rowptr, const int32_t* col, const int32_t* perm, const int32_t* rowptr_t,
+                         const int32_t* col_t, const int32_t* perm_t, int64_t N, int64_t E, void* ws, size_t ws_bytes, int32_t* counts,
+                         void* stream) {
+    (void)perm_t;                                              // (the kept edges in original order come from the by-destination side)
+    KAGNN_CHECK_ARG(N >= 0 && E >= 0 && E < 2147483647LL && N < 2147483647LL, "N and E must fit int32");
+    KAGNN_CHECK_ARG(E == 0 || N > 0, "edges without nodes");
+    KAGNN_CHECK_ARG(counts != nullptr && ws != nullptr, "null array");
+    KAGNN_CHECK_ARG(N == 0 || (hop && rowptr && rowptr_t), "null array");
+    KAGNN_CHECK_ARG(E == 0 || (col && perm && col_t), "null CSR array");
+    return subgraph_count(hop, rowptr, col, perm, rowptr_t, col_t, N, E, ws, ws_bytes, counts, as_stream(stream));
+}
+
+int kagnn_subgraph_fill(const void* ws, size_t ws_bytes, const int32_t* rowptr, const int32_t* col, const int32_t* perm,
+                        const int32_t* rowptr_t, const int32_t* col_t, const int32_t* perm_t, int64_t N, int64_t E, int64_t n_sub,
+                        int64_t e_sub, int64_t* nodes, int64_t* edge_ids, int64_t* edge_index_sub, int32_t* rowptr_sub, int32_t* col_sub,
+                        int32_t* perm_sub, int32_t* rowptr_t_sub, int32_t* col_t_sub, int32_t* perm_t_sub, void* stream) {
+    KAGNN_CHECK_ARG(N >= 0 && E >= 0 && E < 2147483647LL && N < 2147483647LL, "N and E must fit int32");
+    KAGNN_CHECK_ARG(n_sub >= 0 && n_sub <= N && e_sub >= 0 && e_sub <= E && (e_sub == 0 || n_sub > 0), "n_sub / e_sub outside the parent's sizes");
+    KAGNN_CHECK_ARG(ws != nullptr && rowptr_sub && rowptr_t_sub, "null array");
+    KAGNN_CHECK_ARG(n_sub == 0 || (rowptr && rowptr_t && nodes), "null array");
+    KAGNN_CHECK_ARG(n_sub == 0 || E == 0 || (col && perm && col_t && perm_t), "null CSR array");
+    KAGNN_CHECK_ARG(e_sub == 0 || (edge_ids && edge_index_sub && col_sub && perm_sub && col_t_sub && perm_t_sub), "null output");
+    return subgraph_fill(ws, ws_bytes, rowptr, col, perm, rowptr_t, col_t, perm_t, N, E, n_sub, e_sub, nodes, edge_ids, edge_index_sub,
+                         rowptr_sub, col_sub, perm_sub, rowptr_t_sub, col_t_sub, perm_t_sub, as_stream(stream));
 }
 
 int kagnn_gcn_deg_inv_sqrt(const int32_t* rowptr, const int32_t* col, int64_t N, float* dis, void* stream) {

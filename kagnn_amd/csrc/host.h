@@ -110,6 +110,15 @@ size_t csr_small_workspace_bytes(long E);
 int csr_build_small(const int64_t* src, const int64_t* dst, long E, long N, int* rowptr, int* col, int* perm, int* rowptr_t, int*
                     col_t, int* perm_t, int* flags, void* ws, size_t ws_bytes, hipStream_t st);
 
+// ---- subgraph.hip
+int subgraph_workspace_bytes(long N, long E, size_t* bytes);
+int k_hop_mark(const int* rowptr, const int* col, long N, const int64_t* seeds, long S, int num_hops, int* hop, int* flags, hipStream_t st);
+int subgraph_count(const int* hop, const int* rowptr, const int* col, const int* perm, const int* rowptr_t, const int* col_t, long N, long E,
+                   void* ws, size_t ws_bytes, int* counts, hipStream_t st);
+int subgraph_fill(const void* ws, size_t ws_bytes, const int* rowptr, const int* col, const int* perm, const int* rowptr_t, const int* col_t,
+                  const int* perm_t, long N, long E, long n_sub, long e_sub, int64_t* nodes, int64_t* edge_ids, int64_t* ei, int* rowptr_o,
+                  int* col_o, int* perm_o, int* rowptr_to, int* col_to, int* perm_to, hipStream_t st);
+
 // ---- kan_fp32.hip
 size_t kan_f32_pack_fwd_bytes(int in, int out, int C);
 size_t kan_f32_pack_dx_bytes(int in, int out, int C);

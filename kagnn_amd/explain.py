@@ -64,9 +64,23 @@ def explainer_loss(logits, target, edge_m, feat_m, node_idx=None, edge_size=0.00
     return loss
 
 
+def receptive_hops(model: nn.Module) -> int:
+    """How many hops of in-neighbourhood a node's prediction under ``model`` rests on: the number of message-passing convolutions
+    under it (GIN, GCN, GAT and GINE flavoured: KAN, FastKAN and MLP baselines), plus ONE if any of them is GCN-normalised -- a
+    node ``L`` hops out enters with ``deg^-1/2``, and its degree counts in-neighbours ``L + 1`` hops out, which a subgraph of
+    ``L`` hops truncates.  The ``num_hops`` at which ``ops.k_hop_subgraph`` keeps the prediction at the seeds what it is on the full
+    graph (eval mode).  ``ValueError`` for a model without convolutions."""
+    from .graph_models import GINEKANLayer
+    from .models import _AttentionConv, _NormalisedConv, _SumAggregateConv
+    convs = [m for m in model.modules() if isinstance(m, (_SumAggregateConv, _NormalisedConv, _AttentionConv, GINEKANLayer))]
+    if not convs:
+        raise ValueError("receptive_hops: the model holds no message-passing convolution")
+    return len(convs) + (1 if any(isinstance(m, _NormalisedConv) for m in convs) else 0)
+
+
 def explain_edges(model: nn.Module, x: torch.Tensor, edge_index: torch.Tensor, *, node_idx=None, target: Optional[torch.Tensor] = None,
                   epochs: int = 100, lr: float = 0.01, edge_size: float = 0.005, edge_ent: float = 1.0, feat_size: float = 1.0,
-                  feat_ent: float = 0.1, feature_mask: bool = True, generator: Optional[torch.Generator] = None) -> dict:
+                  feat_ent: float = 0.1, feature_mask: bool = True, generator: Optional[torch.Generator] = None, num_hops=None) -> dict:
     """GNNExplainer for a full-batch node model ``model(x, edge_index) -> [N, classes]``: learns a soft edge mask (and a soft feature
     mask shared by all nodes) under which the model keeps predicting ``target`` -- by default its own argmax prediction on the
     unmasked graph -- for node ``node_idx`` (``None``: for every node), while the masks are pushed towards few, decided entries.
@@ -78,9 +92,32 @@ def explain_edges(model: nn.Module, x: torch.Tensor, edge_index: torch.Tensor, *
     changes.  Every kernel on the way is deterministic, so two calls with equally seeded generators return the same bits.
 
     Returns ``{"edge_mask": sigmoid(em) [E], "feature_mask": sigmoid(fm) [F] or None, "losses": [epochs]}`` on the device; the one
-    host read, at the end, is the check that every loss was finite (``FloatingPointError`` otherwise)."""
+    host read, at the end, is the check that every loss was finite (``FloatingPointError`` otherwise).
+
+    ``num_hops`` (an int, or ``"auto"`` = ``receptive_hops(model)``; needs ``node_idx``, ``ValueError`` otherwise): explain the node
+    LOCALLY.  ``sub = ops.k_hop_subgraph(node_idx, num_hops, ops.graph_index(edge_index, N))`` is extracted on the device and the
+    same loop runs on ``(x[sub.nodes], sub.index)`` with ``node_idx = sub.mapping``: the standard deviation of the edge logits
+    uses the subgraph's node count, ``randn`` draws ``sub.num_edges`` values from ``generator``, the default target is the model's
+    argmax on the subgraph, a ``target`` of length N is gathered at ``sub.nodes``.  With ``num_hops >= receptive_hops(model)`` the
+    logits at ``node_idx`` are those of the full graph IN EVAL MODE, which is the mode this function runs the model in; the
+    training-mode BatchNorm of a subgraph normalises with the subgraph's statistics and is a different function.  The result gains
+    ``"nodes"`` and ``"edge_ids"`` (``sub.nodes``, ``sub.edge_ids``) and its ``"edge_mask"`` is scattered back to length E: exactly 0
+    on every edge outside the subgraph.  ``None`` (the default) explains on the whole graph."""
+    sub = None
+    if num_hops is not None:
+        if node_idx is None:
+            raise ValueError("explain_edges: num_hops explains one node's neighbourhood and needs node_idx")
+        hops = receptive_hops(model) if isinstance(num_hops, str) and num_hops == "auto" else num_hops
+        if isinstance(hops, (str, bool)) or int(hops) != hops or hops < 0:
+            raise ValueError(f"explain_edges: num_hops must be None, 'auto' or a non-negative integer, got {num_hops!r}")
+        num_edges_full = edge_index.size(1)
+        seeds = node_idx.to(x.device) if isinstance(node_idx, torch.Tensor) else node_idx
+        sub = ops.k_hop_subgraph(seeds, int(hops), ops.graph_index(edge_index, x.size(0)))
+        if target is not None and target.size(0) == x.size(0):
+            target = target[sub.nodes]
+        x, edge_index, node_idx = x[sub.nodes], sub.index, sub.mapping
     n, f = x.shape
-    e = edge_index.size(1)
+    e = edge_index.size(1) if sub is None else sub.num_edges
     dev = x.device
 
     def randn(*shape):
@@ -115,5 +152,9 @@ def explain_edges(model: nn.Module, x: torch.Tensor, edge_index: torch.Tensor, *
             m.training = flag
     if not bool(torch.isfinite(losses).all()):
         raise FloatingPointError("explain_edges: the loss became non-finite")
-    return {"edge_mask": torch.sigmoid(em).detach(), "feature_mask": None if fm is None else torch.sigmoid(fm).detach().reshape(-1),
-            "losses": losses}
+    out = {"edge_mask": torch.sigmoid(em).detach(), "feature_mask": None if fm is None else torch.sigmoid(fm).detach().reshape(-1),
+           "losses": losses}
+    if sub is not None:
+        out["edge_mask"] = torch.zeros(num_edges_full, dtype=torch.float32, device=dev).index_copy_(0, sub.edge_ids, out["edge_mask"])
+        out["nodes"], out["edge_ids"] = sub.nodes, sub.edge_ids
+    return out

@@ -470,6 +470,108 @@ def clear_graph_cache() -> None:
     _gcn_cache.clear()
 
 
+class Subgraph(NamedTuple):
+    """What ``k_hop_subgraph`` / ``induced_subgraph`` return: the subgraph of a parent ``GraphIndex`` induced by a node selection,
+    relabelled to ``0 .. num_nodes - 1`` in ascending order of the original ids (torch_geometric's ``relabel_nodes=True``)."""
+    nodes: torch.Tensor                  # int64 [num_nodes]: original node ids, ascending
+    edge_index: torch.Tensor             # int64 [2, num_edges]: relabelled edge list, in original edge order
+    edge_ids: torch.Tensor               # int64 [num_edges]: original edge ids, ascending (the set bits of torch_geometric's edge_mask)
+    mapping: Optional[torch.Tensor]      # int64, one entry per entry of the node ids handed in: its position in ``nodes`` (None: a bool mask)
+    hops: Optional[torch.Tensor]         # int32 [num_nodes]: hops from each node to the nearest seed (None: an induced subgraph)
+    index: GraphIndex                    # both CSR structures of ``edge_index``, the bits a build would give; nothing was sorted; no hub segments
+    num_nodes: int
+    num_edges: int
+
+
+def _subgraph_operands(what, ids, g):
+    """the refusals ``k_hop_subgraph`` and ``induced_subgraph`` share, before anything is launched; returns the ids as an int64
+    device vector, or a bool mask of length N as it is"""
+    if not isinstance(g, GraphIndex):
+        raise TypeError(f"{what}: the graph must be an ops.GraphIndex (ops.graph_index(edge_index, num_nodes))")
+    if isinstance(ids, torch.Tensor) and ids.dtype == torch.bool:
+        if ids.dim() != 1 or ids.numel() != g.num_nodes:
+            raise ValueError(f"{what}: a node mask must have shape [{g.num_nodes}], got {tuple(ids.shape)}")
+    elif isinstance(ids, torch.Tensor):
+        if ids.dtype != torch.int64 or ids.dim() > 1:
+            raise ValueError(f"{what}: node ids must be an int64 scalar or vector (or a bool mask of length num_nodes)")
+        ids = ids.reshape(-1)
+    _need_cuda(g.rowptr, ids if isinstance(ids, torch.Tensor) else None)
+    if not isinstance(ids, torch.Tensor):
+        ids = torch.tensor([ids] if isinstance(ids, int) else list(ids), dtype=torch.int64, device=g.device).reshape(-1)
+    return ids.contiguous()
+
+
+def _subgraph_extract(what, hop, rec, g: GraphIndex, ids, keep_hops: bool) -> Subgraph:
+    """``hop`` [N] int32 selects the nodes (>= 0); ``rec`` = device int32 [n_sub, e_sub, bad-seed flag]: count, the ONE read-back
+    (pinned memory), fill with exact sizes"""
+    n, e, dev = g.num_nodes, g.num_edges, g.device
+    i32, i64 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.int64, device=dev)
+    ws = _ws(_sizes("kagnn_subgraph_workspace_bytes", n, e), dev)
+    parent = [_ptr(t) for t in (g.rowptr, g.col, g.perm, g.rowptr_t, g.col_t, g.perm_t)]
+    _call("kagnn_subgraph_count", _ptr(hop), *parent, n, e, _ptr(ws), ws.numel(), _ptr(rec), _stream())
+    host = torch.empty(3, dtype=torch.int32, pin_memory=True)
+    host.copy_(rec, non_blocking=True)
+    ev = torch.cuda.Event()
+    ev.record(torch.cuda.current_stream(dev))
+    ev.synchronize()
+    n_sub, e_sub, bad = (int(v) for v in host)
+    if bad:
+        raise ValueError(f"{what}: node ids outside [0, {n})")
+    nodes, edge_ids, ei = torch.empty(n_sub, **i64), torch.empty(e_sub, **i64), torch.empty((2, e_sub), **i64)
+    rowptr, col, perm = torch.empty(n_sub + 1, **i32), torch.empty(e_sub, **i32), torch.empty(e_sub, **i32)
+    rowptr_t, col_t, perm_t = torch.empty(n_sub + 1, **i32), torch.empty(e_sub, **i32), torch.empty(e_sub, **i32)
+    _call("kagnn_subgraph_fill", _ptr(ws), ws.numel(), *parent, n, e, n_sub, e_sub, _ptr(nodes), _ptr(edge_ids), _ptr(ei),
+          _ptr(rowptr), _ptr(col), _ptr(perm), _ptr(rowptr_t), _ptr(col_t), _ptr(perm_t), _stream())
+    mapping = None
+    if ids is not None:
+        relabel = ws[:4 * n].view(torch.int32)             # (the workspace begins with relabel[N]: kagnn_hip.h)
+        mapping = relabel.index_select(0, ids).to(torch.int64) if ids.numel() else torch.empty(0, **i64)
+    hops = hop.index_select(0, nodes) if keep_hops else None
+    index = GraphIndex.from_arrays(rowptr, col, perm, rowptr_t, col_t, perm_t, n_sub, e_sub)
+    return Subgraph(nodes, ei, edge_ids, mapping, hops, index, n_sub, e_sub)
+
+
+def _mark_hops(ids, num_hops: int, g: GraphIndex):
+    n, dev = g.num_nodes, g.device
+    hop = torch.empty(n, dtype=torch.int32, device=dev)
+    rec = torch.empty(3, dtype=torch.int32, device=dev)
+    _call("kagnn_k_hop_mark", _ptr(g.rowptr), _ptr(g.col), n, _ptr(ids), ids.numel(), int(num_hops), _ptr(hop), _ptr(rec[2:]), _stream())
+    return hop, rec
+
+
+def k_hop_subgraph(node_idx, num_hops: int, g: GraphIndex) -> Subgraph:
+    """torch_geometric's ``k_hop_subgraph(node_idx, num_hops, edge_index, relabel_nodes=True)`` (``flow='source_to_target'``) on
+    the parent's index ``g``: the nodes from which some node of ``node_idx`` (an int, a sequence or an int64 device vector;
+    duplicates allowed) is reached along at most ``num_hops`` edges, and every edge between two of them -- what the prediction of
+    a ``num_hops``-layer message-passing model at ``node_idx`` rests on (``kagnn_amd.receptive_hops``: a GCN-normalised model needs
+    one hop more than it has layers).  ``kagnn_k_hop_mark`` -> ``kagnn_subgraph_count`` -> one read of the two counts and the
+    bad-seed flag from pinned memory -> ``kagnn_subgraph_fill``; the parent's rows are compacted in place of a sort, so
+    ``.index`` holds the bits ``GraphIndex(sub.edge_index, sub.num_nodes)`` would, without hub segments.  Raises ``ValueError``
+    for a seed outside ``[0, N)`` (after the read) and for ``num_hops < 0``; empty seeds give an empty subgraph."""
+    if isinstance(num_hops, bool) or int(num_hops) != num_hops or num_hops < 0:
+        raise ValueError(f"k_hop_subgraph: num_hops must be a non-negative integer, got {num_hops!r}")
+    if isinstance(node_idx, torch.Tensor) and node_idx.dtype == torch.bool:
+        raise ValueError("k_hop_subgraph: node_idx must be node ids, not a mask")
+    ids = _subgraph_operands("k_hop_subgraph", node_idx, g)
+    with _device_of(g.rowptr):
+        hop, rec = _mark_hops(ids, int(num_hops), g)
+        return _subgraph_extract("k_hop_subgraph", hop, rec, g, ids, True)
+
+
+def induced_subgraph(nodes, g: GraphIndex) -> Subgraph:
+    """torch_geometric's ``subgraph(nodes, edge_index, relabel_nodes=True, return_edge_mask=True)`` on the parent's index ``g``:
+    ``nodes`` is a sequence / int64 device vector of ids (duplicates allowed) or a bool mask ``[N]``.  The same calls and the same
+    single read as ``k_hop_subgraph`` (the mark call with ``num_hops = 0``; a mask needs no mark call); ``.hops`` is ``None``."""
+    ids = _subgraph_operands("induced_subgraph", nodes, g)
+    with _device_of(g.rowptr):
+        if ids.dtype == torch.bool:
+            hop = ids.to(torch.int32) - 1                                   # selected: 0, else -1
+            rec = torch.zeros(3, dtype=torch.int32, device=g.device)
+            return _subgraph_extract("induced_subgraph", hop, rec, g, None, False)
+        hop, rec = _mark_hops(ids, 0, g)
+        return _subgraph_extract("induced_subgraph", hop, rec, g, ids, False)
+
+
 class WeightedGcnGraph:
     """``gcn_norm`` with edge weights (torch_geometric 2.5.3 semantics, restated in oracle/kan_oracle.py).
 
