@@ -55,7 +55,7 @@ extern "C" {
 #define KAGNN_DTYPE_F32 0
 #define KAGNN_DTYPE_BF16 1
 
-int kagnn_version(void);          /* 276 = 275 + kagnn_k_hop_mark, kagnn_subgraph_count, kagnn_subgraph_fill (+ kagnn_subgraph_workspace_bytes); 273 = 272 with kagnn_kan_grid_refit on kagnn_kan_grid_resize's kernels (up to 46 coefficients; its bits and its workspace size change); 272 = 271 + kagnn_kan_grid_resize (+ _workspace_bytes); 271 = 270 + kagnn_attention_fwd, kagnn_attention_bwd (+ _workspace_bytes); 270 = 269 + kagnn_fastkan_edge_abs_sum, kagnn_fastkan_edge_abs_sum_bwd (+ _workspace_bytes), kagnn_fastkan_edge_curves; 269 = 268 + kagnn_kan_edge_abs_sum, kagnn_kan_edge_abs_sum_bwd (+ _workspace_bytes), kagnn_kan_edge_curves; 268 = 267 + spline orders 5..KAGNN_MAX_SPLINE_ORDER in the per-operation KANLinear calls (no new entry point); 267 = 266 + kagnn_linear_fwd, kagnn_linear_bwd_input, kagnn_linear_bwd_weight (+ _workspace_bytes); 266 = 265 + kagnn_l1_loss_meter_fwd, kagnn_regression_epoch_update; 265 = 264 + kagnn_node_eval, kagnn_early_stop_update, kagnn_copy_if; 264 = 263 + kagnn_degree_one_hot, kagnn_nll_loss_fwd / _bwd; 263 = 262 + kagnn_batch_assemble; 262 = 261 - the fields edge_src, edge_dst, csr_flags of kagnn_kagin_model_t; 261 = 260 + kagnn_fastkan_fwd_stats_in_kernel; 260 = round 6: + the feature-sharded FastKAN entry points kagnn_fastkan_row_moments .. _shard_bwd_finish, + kagnn_kagin_model_*; 250 = 240 + KAGNN_PREC_HALF; 240 = 230 + kagnn_gin_kan_layer_bwd_bn_sums; 230 = 220 + the *_affine entry points of a folded BatchNorm1d; 220 = 210 + the stage timer) */
+int kagnn_version(void);          /* 277 = 276 + kagnn_neighbor_sample_mark, kagnn_edge_subgraph_count, kagnn_edge_subgraph_fill; 276 = 275 + kagnn_k_hop_mark, kagnn_subgraph_count, kagnn_subgraph_fill (+ kagnn_subgraph_workspace_bytes); 273 = 272 with kagnn_kan_grid_refit on kagnn_kan_grid_resize's kernels (up to 46 coefficients; its bits and its workspace size change); 272 = 271 + kagnn_kan_grid_resize (+ _workspace_bytes); 271 = 270 + kagnn_attention_fwd, kagnn_attention_bwd (+ _workspace_bytes); 270 = 269 + kagnn_fastkan_edge_abs_sum, kagnn_fastkan_edge_abs_sum_bwd (+ _workspace_bytes), kagnn_fastkan_edge_curves; 269 = 268 + kagnn_kan_edge_abs_sum, kagnn_kan_edge_abs_sum_bwd (+ _workspace_bytes), kagnn_kan_edge_curves; 268 = 267 + spline orders 5..KAGNN_MAX_SPLINE_ORDER in the per-operation KANLinear calls (no new entry point); 267 = 266 + kagnn_linear_fwd, kagnn_linear_bwd_input, kagnn_linear_bwd_weight (+ _workspace_bytes); 266 = 265 + kagnn_l1_loss_meter_fwd, kagnn_regression_epoch_update; 265 = 264 + kagnn_node_eval, kagnn_early_stop_update, kagnn_copy_if; 264 = 263 + kagnn_degree_one_hot, kagnn_nll_loss_fwd / _bwd; 263 = 262 + kagnn_batch_assemble; 262 = 261 - the fields edge_src, edge_dst, csr_flags of kagnn_kagin_model_t; 261 = 260 + kagnn_fastkan_fwd_stats_in_kernel; 260 = round 6: + the feature-sharded FastKAN entry points kagnn_fastkan_row_moments .. _shard_bwd_finish, + kagnn_kagin_model_*; 250 = 240 + KAGNN_PREC_HALF; 240 = 230 + kagnn_gin_kan_layer_bwd_bn_sums; 230 = 220 + the *_affine entry points of a folded BatchNorm1d; 220 = 210 + the stage timer) */
 const char* kagnn_last_error(void);
 
 /* Stage timer -- a measurement aid, off by default (no reference counterpart: the reference times whole epochs with
@@ -138,6 +138,44 @@ int kagnn_subgraph_fill(const void* workspace, size_t workspace_bytes, const int
                         int64_t n_sub, int64_t e_sub, int64_t* nodes, int64_t* edge_ids, int64_t* edge_index_sub,
                         int32_t* rowptr_sub, int32_t* col_sub, int32_t* perm_sub, int32_t* rowptr_t_sub, int32_t* col_t_sub,
                         int32_t* perm_t_sub, void* stream);
+
+/* Fan-out-limited neighbour sampling (GraphSAGE; torch_geometric's NeighborLoader / NeighborSampler, directed, without
+ * replacement; no counterpart in the reference, whose node-level scripts are full batch).  The same three calls and the same ONE
+ * read-back as above, with an edge selection between the first and the second; all indices int32; no float, no atomic
+ * read-modify-write on global memory; every result is a pure function of (graph, seeds as a SET, fanout, seed).
+ *
+ * kagnn_neighbor_sample_mark: (rowptr, col, perm) = the parent's by-destination CSR.  hop[num_nodes] is filled with -1 and
+ *   keep[num_edges] (bytes) with 0; seeds get hop 0, a seed outside [0, num_nodes) sets the DEVICE int flags[0] = 1 (else 0) and is
+ *   skipped.  Then one launch per level d = 0 .. num_levels - 1 (1 <= num_levels <= KAGNN_SAMPLE_MAX_LEVELS; fanout_host[d]: a HOST
+ *   array, >= 0 a count, -1 all): every row with hop == d selects min(deg, fanout[d]) of its in-edges, sets keep[perm[p]] = 1 for
+ *   them and stores d + 1 into hop[col[p]] where it still reads -1 -- a node is expanded once, at the level it is first reached.
+ *   WHICH edges a row selects is part of this ABI: the k entries of the row with the smallest pair (key32(seed, e), e), e = perm[p]
+ *   the ORIGINAL edge id, where with  mix32(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16  (uint32
+ *   arithmetic) and lo = (uint32)seed, hi = (uint32)(seed >> 32):
+ *       h1 = mix32(lo + 0x9e3779b9),  h2 = mix32(hi ^ h1 ^ 0x85ebca6b),  key32(seed, e) = mix32(mix32((uint32)e ^ h1) + h2).
+ *   The k smallest keys of a row are a uniform k-subset without replacement, independent across rows, and do not depend on the
+ *   order of the seeds or on the launch geometry.  Rows of at most 64 entries rank one key per lane by comparison across the wave;
+ *   longer rows find the k-th smallest key by a byte-digit radix select (256 bins per wave in LDS, four passes) and resolve ties
+ *   at the threshold to the lowest edge ids -- nothing of a row is staged, so a row of any length works at any fan-out.  A fan-out
+ *   >= deg takes the whole row without computing a key.
+ * kagnn_edge_subgraph_count / kagnn_edge_subgraph_fill: kagnn_subgraph_count / kagnn_subgraph_fill for the subgraph given by an
+ *   EDGE selection: the nodes are hop[i] >= 0, the edges exactly keep[e] != 0, in original edge order.  By contract both endpoints
+ *   of a kept edge are selected (the mark call's output is such a pair); an edge whose endpoint is not is dropped from the rows, and
+ *   every store stays guarded by relabel, n_sub and e_sub as above.  Same outputs, same workspace (size query, layout -- it BEGINS
+ *   with relabel[num_nodes] -- and the single read of counts); the by-source side is compacted from (rowptr_t, col_t, perm_t) with
+ *   keep[perm_t[p]], so perm_t IS read by the count call here.  keep must be the same array in both calls. */
+#define KAGNN_SAMPLE_MAX_LEVELS 16
+int kagnn_neighbor_sample_mark(const int32_t* rowptr, const int32_t* col, const int32_t* perm, int64_t num_nodes, int64_t num_edges,
+                               const int64_t* seeds, int64_t num_seeds, const int32_t* fanout_host, int32_t num_levels, uint64_t seed,
+                               int32_t* hop, uint8_t* keep, int32_t* flags, void* stream);
+int kagnn_edge_subgraph_count(const int32_t* hop, const uint8_t* keep, const int32_t* rowptr, const int32_t* col, const int32_t* perm,
+                              const int32_t* rowptr_t, const int32_t* col_t, const int32_t* perm_t, int64_t num_nodes,
+                              int64_t num_edges, void* workspace, size_t workspace_bytes, int32_t* counts, void* stream);
+int kagnn_edge_subgraph_fill(const void* workspace, size_t workspace_bytes, const uint8_t* keep, const int32_t* rowptr,
+                             const int32_t* col, const int32_t* perm, const int32_t* rowptr_t, const int32_t* col_t,
+                             const int32_t* perm_t, int64_t num_nodes, int64_t num_edges, int64_t n_sub, int64_t e_sub, int64_t* nodes,
+                             int64_t* edge_ids, int64_t* edge_index_sub, int32_t* rowptr_sub, int32_t* col_sub, int32_t* perm_sub,
+                             int32_t* rowptr_t_sub, int32_t* col_t_sub, int32_t* perm_t_sub, void* stream);
 
 /* in-degree normalisation of GCN (torch_geometric gcn_norm as used by KAGCNConv,
  * node_classification_clean/models.py:31-37): dis[i] = (1 + #non-loop in-edges of i)^-1/2.

@@ -19,6 +19,6 @@ from . import baselines                                                         
 from .baselines import (GAT, GCN, GIN, GATConv, GCNConv, GCNRegression, GINConv, GINEConv, GINRegression, GNN_Nodes,   # noqa: F401
                         Linear, LinearReLU, make_mlp, make_mlp_nodes)
 from .explain import edge_mask, explain_edges, receptive_hops                    # noqa: F401
-from .data import DeviceBatch, DeviceBatchLoader, DeviceGraphDataset             # noqa: F401
+from .data import DeviceBatch, DeviceBatchLoader, DeviceGraphDataset, NeighborLoader, NodeBatch   # noqa: F401
 
 __version__ = "0.1.0"

@@ -42,6 +42,11 @@ _SIGNATURES = {
     "kagnn_subgraph_count": (c_int32, [_P, _P, _P, _P, _P, _P, _P, c_int64, c_int64, _P, c_size_t, _P, _P]),
     "kagnn_subgraph_fill": (c_int32, [_P, c_size_t, _P, _P, _P, _P, _P, _P, c_int64, c_int64, c_int64, c_int64,
                                       _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    # rowptr col perm N E seeds S fanout(host int32) L seed hop keep flags stream
+    "kagnn_neighbor_sample_mark": (c_int32, [_P, _P, _P, c_int64, c_int64, _P, c_int64, POINTER(c_int32), c_int32, c_uint64, _P, _P, _P, _P]),
+    "kagnn_edge_subgraph_count": (c_int32, [_P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int64, _P, c_size_t, _P, _P]),
+    "kagnn_edge_subgraph_fill": (c_int32, [_P, c_size_t, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int64, c_int64, c_int64,
+                                           _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "kagnn_gcn_deg_inv_sqrt": (c_int32, [_P, _P, c_int64, _P, _P]),
     "kagnn_aggregate_workspace_bytes": (c_int32, [c_int64, c_int32, POINTER(c_size_t)]),
     "kagnn_aggregate_sum": (c_int32, [_P, c_int64, _P, c_int64, _P, _P, _P, c_int64, c_int32, c_float,
@@ -263,6 +268,7 @@ class KaginModel(ctypes.Structure):
 
 BATCH_MAX_GRAPHS = 4096      # KAGNN_BATCH_MAX_GRAPHS
 REGRESSION_MAX_TARGETS = 32  # KAGNN_REGRESSION_MAX_TARGETS
+SAMPLE_MAX_LEVELS = 16       # KAGNN_SAMPLE_MAX_LEVELS
 
 
 class BatchAssemble(ctypes.Structure):

@@ -84,7 +84,7 @@ using namespace kagnn;
 #pragma GCC visibility push(default)
 extern "C" {
 
-int kagnn_version(void) { return 276; }
+int kagnn_version(void) { return 277; }
 const char* kagnn_last_error(void) { return g_err; }
 
 int kagnn_stage_timer_enable(const char* only) {
@@ -201,6 +201,48 @@ int kagnn_subgraph_fill(const void* ws, size_t ws_bytes, const int32_t* rowptr, 
     KAGNN_CHECK_ARG(e_sub == 0 || (edge_ids && edge_index_sub && col_sub && perm_sub && col_t_sub && perm_t_sub), "null output");
     return subgraph_fill(ws, ws_bytes, rowptr, col, perm, rowptr_t, col_t, perm_t, N, E, n_sub, e_sub, nodes, edge_ids, edge_index_sub,
                          rowptr_sub, col_sub, perm_sub, rowptr_t_sub, col_t_sub, perm_t_sub, as_stream(stream));
+}
+
+int kagnn_neighbor_sample_mark(const int32_t* rowptr, const int32_t* col, const int32_t* perm, int64_t N, int64_t E, const int64_t* seeds,
+                               int64_t num_seeds, const int32_t* fanout_host, int32_t num_levels, uint64_t seed, int32_t* hop, uint8_t* keep,
+                               int32_t* flags, void* stream) {
+    KAGNN_CHECK_ARG(N >= 0 && N < 2147483647LL && E >= 0 && E < 2147483647LL && num_seeds >= 0 && num_seeds < 2147483647LL,
+                    "num_nodes, num_edges and num_seeds must fit int32");
+    KAGNN_CHECK_ARG(E == 0 || N > 0, "edges without nodes");
+    KAGNN_CHECK_ARG(num_levels >= 1 && num_levels <= KAGNN_SAMPLE_MAX_LEVELS && fanout_host, "num_levels outside 1..16, or no fan-outs");
+    for (int d = 0; d < num_levels; ++d) KAGNN_CHECK_ARG(fanout_host[d] >= -1, "a fanout below -1");
+    KAGNN_CHECK_ARG(flags != nullptr && (N == 0 || hop) && (E == 0 || keep) && (num_seeds == 0 || seeds), "null array");
+    KAGNN_CHECK_ARG(E == 0 || num_seeds == 0 || (rowptr && col && perm), "null CSR array");
+    return neighbor_sample_mark(rowptr, col, perm, N, E, seeds, num_seeds, fanout_host, num_levels, seed, hop, keep, flags, as_stream(stream));
+}
+
+int kagnn_edge_subgraph_count(const int32_t* hop, const uint8_t* keep, const int32_t* rowptr, const int32_t* col, const int32_t* perm,
+                              const int32_t* rowptr_t, const int32_t* col_t, const int32_t* perm_t, int64_t N, int64_t E, void* ws,
+                              size_t ws_bytes, int32_t* counts, void* stream) {
+    KAGNN_CHECK_ARG(N >= 0 && E >= 0 && E < 2147483647LL && N < 2147483647LL, "N and E must fit int32");
+    KAGNN_CHECK_ARG(E == 0 || N > 0, "edges without nodes");
+    KAGNN_CHECK_ARG(counts != nullptr && ws != nullptr, "null array");
+    KAGNN_CHECK_ARG(N == 0 || (hop && rowptr && rowptr_t), "null array");
+    KAGNN_CHECK_ARG(E == 0 || (keep && col && perm && col_t && perm_t), "null CSR array");
+    // (keep may be NULL at E == 0, where both forms of the subgraph agree)
+    return edge_subgraph_count(hop, keep, rowptr, col, perm, rowptr_t, col_t, perm_t, N, E, ws, ws_bytes, counts,
+                               as_stream(stream));
+}
+
+int kagnn_edge_subgraph_fill(const void* ws, size_t ws_bytes, const uint8_t* keep, const int32_t* rowptr, const int32_t* col,
+                             const int32_t* perm, const int32_t* rowptr_t, const int32_t* col_t, const int32_t* perm_t, int64_t N, int64_t E,
+                             int64_t n_sub, int64_t e_sub, int64_t* nodes, int64_t* edge_ids, int64_t* edge_index_sub, int32_t* rowptr_sub,
+                             int32_t* col_sub, int32_t* perm_sub, int32_t* rowptr_t_sub, int32_t* col_t_sub, int32_t* perm_t_sub,
+                             void* stream) {
+    KAGNN_CHECK_ARG(N >= 0 && E >= 0 && E < 2147483647LL && N < 2147483647LL, "N and E must fit int32");
+    KAGNN_CHECK_ARG(n_sub >= 0 && n_sub <= N && e_sub >= 0 && e_sub <= E && (e_sub == 0 || n_sub > 0), "n_sub / e_sub outside the parent's sizes");
+    KAGNN_CHECK_ARG(ws != nullptr && rowptr_sub && rowptr_t_sub, "null array");
+    KAGNN_CHECK_ARG(n_sub == 0 || (rowptr && rowptr_t && nodes), "null array");
+    KAGNN_CHECK_ARG(n_sub == 0 || E == 0 || (keep && col && perm && col_t && perm_t), "null CSR array");
+    KAGNN_CHECK_ARG(e_sub == 0 || (edge_ids && edge_index_sub && col_sub && perm_sub && col_t_sub && perm_t_sub), "null output");
+    return edge_subgraph_fill(ws, ws_bytes, keep, rowptr, col, perm, rowptr_t, col_t, perm_t, N, E, n_sub, e_sub, nodes,
+                              edge_ids, edge_index_sub, rowptr_sub, col_sub, perm_sub, rowptr_t_sub, col_t_sub, perm_t_sub,
+                              as_stream(stream));
 }
 
 int kagnn_gcn_deg_inv_sqrt(const int32_t* rowptr, const int32_t* col, int64_t N, float* dis, void* stream) {

@@ -37,10 +37,6 @@ __device__ __forceinline__ void st4c(float* row, int c, int F, bool vec, const f
 
 // keep-and-scale factors of elements (n, c..c+3): two 32-bit hashes -> four 16-bit uniforms, keep when u < thr
 struct DropArgs { unsigned lo, hi, thr; float scale; };          // thr = round((1-p) * 65536); thr >= 65536: no dropout
-__device__ __forceinline__ unsigned mix32(unsigned x) {
-    x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16;
-    return x;
-}
 __device__ __forceinline__ void keep4(const DropArgs& d, long n, int c, float (&k)[4]) {
     const unsigned a = mix32(mix32((unsigned)n ^ d.lo) + (unsigned)(n >> 32) + (unsigned)(c >> 2) * 0x9e3779b9U + d.hi);
     const unsigned b = mix32(a ^ 0x85ebca6bU);

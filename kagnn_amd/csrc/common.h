@@ -95,6 +95,13 @@ __device__ __forceinline__ float silu_gradf(float x) {
     return s * (1.0f + x * (1.0f - s));
 }
 
+// The 32-bit finaliser of the counter-based hashes: dropout's keep bits (bn.hip: keep4) and the sampling keys of
+// kagnn_neighbor_sample_mark (subgraph.hip: sample_key32).  Both are restated bit for bit by the tests.
+__device__ __forceinline__ unsigned mix32(unsigned x) {
+    x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16;
+    return x;
+}
+
 // Gaussian RBF of the FastKAN layer, exp(-((z - c) / denominator)^2): the one form its layer kernels (fastkan.hip) and its edge
 // kernels (fastkan_edge.hip) evaluate, so that the layer's output is the sum of its edge functions to rounding
 __device__ __forceinline__ float rbf_val(float z, float c, float inv_den) {

@@ -118,6 +118,14 @@ int subgraph_count(const int* hop, const int* rowptr, const int* col, const int*
 int subgraph_fill(const void* ws, size_t ws_bytes, const int* rowptr, const int* col, const int* perm, const int* rowptr_t, const int* col_t,
                   const int* perm_t, long N, long E, long n_sub, long e_sub, int64_t* nodes, int64_t* edge_ids, int64_t* ei, int* rowptr_o,
                   int* col_o, int* perm_o, int* rowptr_to, int* col_to, int* perm_to, hipStream_t st);
+int neighbor_sample_mark(const int* rowptr, const int* col, const int* perm, long N, long E, const int64_t* seeds, long S, const int* fanout,
+                         int num_levels, unsigned long long seed, int* hop, unsigned char* keep, int* flags, hipStream_t st);
+int edge_subgraph_count(const int* hop, const unsigned char* keep, const int* rowptr, const int* col, const int* perm, const int* rowptr_t,
+                        const int* col_t, const int* perm_t, long N, long E, void* ws, size_t ws_bytes, int* counts, hipStream_t st);
+int edge_subgraph_fill(const void* ws, size_t ws_bytes, const unsigned char* keep, const int* rowptr, const int* col, const int* perm,
+                       const int* rowptr_t, const int* col_t, const int* perm_t, long N, long E, long n_sub, long e_sub, int64_t* nodes,
+                       int64_t* edge_ids, int64_t* ei, int* rowptr_o, int* col_o, int* perm_o, int* rowptr_to, int* col_to, int* perm_to,
+                       hipStream_t st);
 
 // ---- kan_fp32.hip
 size_t kan_f32_pack_fwd_bytes(int in, int out, int C);

@@ -9,6 +9,10 @@ ptr`` and both CSR structures the convolutions need -- is per-graph slices of th
 
 torch_geometric is not imported: ``DeviceGraphDataset.from_graphs`` takes any objects with ``x / edge_index / edge_attr / y``.
 CPU tensors as the place to keep the dataset are refused like everywhere else in this package.
+
+The node-level side: ``NeighborLoader`` cuts the input nodes of ONE graph into mini-batches and samples a fan-out-limited
+neighbourhood around each on the device (``ops.sample_neighbors``, ``csrc/subgraph.hip``) -- a ``NodeBatch`` per step for the node
+models, again without host collation.
 """
 from __future__ import annotations
 
@@ -447,3 +451,99 @@ class DeviceBatchLoader:
             # one deferred check for the epoch's batches (also when the consumer stops early: rows of batches never assembled are 0)
             with ops._device_of(st.x):
                 ops._defer_flag_check(flags, _ASSEMBLE_FLAG_MESSAGE)
+
+
+# ------------------------------------------------------------------------------------------------ neighbour-sampled node batches
+_SEED_STRIDE = 0x9E3779B97F4A7C15      # 2^64 / golden ratio, odd: the multiples i * stride mod 2^64 are distinct for i < 2^64
+
+
+class NodeBatch:
+    """What ``NeighborLoader`` yields: the sampled subgraph around ``seeds`` (``ops.sample_neighbors``) -- ``nodes`` (int64, original
+    ids, ascending), ``edge_index`` (int64 ``[2, num_edges]``, relabelled), ``edge_ids`` (original edge ids), ``index`` (the
+    ``GraphIndex`` of ``edge_index``: ``model(batch.x, batch.index)``), ``hops`` (int32: the level at which a node was first
+    reached) -- and the batch's own rows: ``seeds`` (original ids, in the epoch's order), ``seed_rows`` (their positions in
+    ``nodes``: the loss is taken on ``out[batch.seed_rows]``), ``num_seeds``, ``x = x[nodes]`` and ``y = y[seeds]`` where the loader
+    was given ``x`` / ``y`` (else ``None``)."""
+    __slots__ = ("nodes", "edge_index", "edge_ids", "index", "hops", "seed_rows", "seeds", "num_seeds", "num_nodes", "num_edges", "x", "y")
+
+
+class NeighborLoader:
+    """torch_geometric's ``NeighborLoader(data, num_neighbors=fanouts, input_nodes=..., batch_size=..., shuffle=...)`` on the device:
+    re-iterable, ``len()`` = batches per epoch.  ``graph``: an ``ops.GraphIndex`` or ``(edge_index, num_nodes)``; ``input_nodes``:
+    int64 ids or a bool mask ``[N]``.  Every ``__iter__`` draws the epoch's order on the host (``epoch_order``, applied to the
+    input nodes), sends it to the device in ONE non-blocking copy, and per batch calls ``ops.sample_neighbors`` on a slice of it
+    (whose read of the two counts is the batch's only synchronisation) and gathers ``x[nodes]`` / ``y[seeds]``.  No host
+    collation, no sort.
+
+    Sampling seeds: batch ``b`` of epoch ``t`` (``t`` counts the orders drawn from this loader, from 0) samples under
+    ``(seed + 0x9E3779B97F4A7C15 * (1 + t * len(loader) + b)) mod 2^64`` -- ``sampling_seed(t, b)``.  One ``seed`` therefore
+    reproduces a run (together with ``generator`` when ``shuffle``), and no two batches of a run share a sampling seed: the stride
+    is odd, so its multiples are distinct mod 2^64.  Which edges a seed keeps: ``kagnn_neighbor_sample_mark`` (kagnn_hip.h)."""
+
+    def __init__(self, graph, input_nodes, fanouts, batch_size: int, shuffle: bool = False, drop_last: bool = False,
+                 generator: Optional[torch.Generator] = None, seed: int = 0, x=None, y=None):
+        self.fanouts = ops._fanouts("NeighborLoader", fanouts)
+        if isinstance(batch_size, bool) or int(batch_size) != batch_size or batch_size < 1:
+            raise ValueError(f"NeighborLoader: batch_size must be a positive integer, got {batch_size!r}")
+        if isinstance(seed, bool) or not isinstance(seed, int):
+            raise ValueError(f"NeighborLoader: seed must be an int, got {seed!r}")
+        if isinstance(graph, (tuple, list)) and len(graph) == 2 and isinstance(graph[0], torch.Tensor):
+            graph = ops.graph_index(graph[0], int(graph[1]))
+        if not isinstance(graph, ops.GraphIndex):
+            raise TypeError("NeighborLoader: the graph must be an ops.GraphIndex or (edge_index, num_nodes)")
+        n = graph.num_nodes
+        if not isinstance(input_nodes, torch.Tensor):
+            input_nodes = torch.as_tensor(input_nodes)
+        if input_nodes.dtype == torch.bool:
+            if input_nodes.dim() != 1 or input_nodes.numel() != n:
+                raise ValueError(f"NeighborLoader: a node mask must have shape [{n}], got {tuple(input_nodes.shape)}")
+            input_nodes = input_nodes.nonzero().flatten()
+        elif input_nodes.dtype != torch.int64 or input_nodes.dim() != 1:
+            raise ValueError("NeighborLoader: input_nodes must be an int64 vector of node ids or a bool mask of length num_nodes")
+        for name, t in (("x", x), ("y", y)):
+            if t is not None and (not isinstance(t, torch.Tensor) or t.dim() < 1 or t.size(0) != n):
+                raise ValueError(f"NeighborLoader: {name} must have {n} rows, one per node of the graph")
+        self.graph, self.input_nodes = graph, input_nodes.cpu().contiguous()        # (the order is drawn on the host)
+        self.batch_size, self.shuffle, self.drop_last, self.generator = int(batch_size), bool(shuffle), bool(drop_last), generator
+        self.seed, self.x, self.y = seed, x, y
+        self.epoch = 0                                    # the number of epoch orders drawn so far: the `t` of the seed formula
+
+    def __len__(self) -> int:
+        return num_batches(int(self.input_nodes.numel()), self.batch_size, self.drop_last)
+
+    def sampling_seed(self, epoch: int, batch: int) -> int:
+        """the 64-bit seed under which batch ``batch`` of epoch ``epoch`` is sampled (the class docstring's formula)"""
+        return (self.seed + _SEED_STRIDE * (1 + int(epoch) * len(self) + int(batch))) & 0xFFFFFFFFFFFFFFFF
+
+    def order(self) -> torch.Tensor:
+        """draw one epoch's order -- the input nodes in the sequence the epoch visits them (int64, CPU) -- and count the epoch"""
+        self.epoch += 1
+        return self.input_nodes[epoch_order(int(self.input_nodes.numel()), self.shuffle, self.generator)]
+
+    def __iter__(self):
+        epoch = self.epoch
+        return self.batches_of(self.order(), epoch)
+
+    def batches_of(self, ids: torch.Tensor, epoch: int):
+        """the mini-batches that cut ``ids`` (node ids, int64, CPU) into runs of ``batch_size``, sampled under ``epoch``'s seeds"""
+        g = self.graph
+        ops._need_cuda(g.rowptr, self.x, self.y)
+        ids = torch.as_tensor(ids, dtype=torch.int64).reshape(-1)
+        nb = num_batches(int(ids.numel()), self.batch_size, self.drop_last)
+        if nb == 0:
+            return
+        pinned = torch.empty(ids.numel(), dtype=torch.int64, pin_memory=True)
+        pinned.copy_(ids)
+        with ops._device_of(g.rowptr):
+            ids_dev = pinned.to(g.device, non_blocking=True)
+        for b in range(nb):
+            seeds = ids_dev[b * self.batch_size:(b + 1) * self.batch_size]
+            sub = ops.sample_neighbors(seeds, self.fanouts, g, seed=self.sampling_seed(epoch, b))
+            out = NodeBatch()
+            out.nodes, out.edge_index, out.edge_ids, out.index, out.hops = sub.nodes, sub.edge_index, sub.edge_ids, sub.index, sub.hops
+            out.seed_rows, out.seeds, out.num_seeds = sub.mapping, seeds, int(seeds.numel())
+            out.num_nodes, out.num_edges = sub.num_nodes, sub.num_edges
+            with ops._device_of(g.rowptr):
+                out.x = None if self.x is None else self.x.index_select(0, sub.nodes)
+                out.y = None if self.y is None else self.y.index_select(0, seeds)
+            yield out

@@ -713,6 +713,67 @@ def train_node_classification(model, x, edge_index, y, train_mask, val_mask, tes
                                     best_epoch=st.best_epoch, stopped=st.stopped, history=st.history)
 
 
+def train_node_classification_sampled(model, x, edge_index, y, train_mask, val_mask, test_mask=None, fanouts=None, batch_size: int = 1024,
+                                      seed: int = 0, epochs: int = 1000, lr: float = 1e-2, patience: int = 100, min_delta: float = 0.0,
+                                      poll_every: int = 16, optimizer=None, loss_fn=None):
+    """``train_node_classification`` with neighbour-sampled mini-batches (GraphSAGE training; no counterpart in the reference, whose
+    node-level scripts are full batch).  Per epoch every batch of a ``kagnn_amd.NeighborLoader`` over the ``train_mask`` ids
+    (``fanouts``, ``batch_size``, ``seed``; reshuffled per epoch from a ``torch.Generator`` seeded with ``seed``, so that one
+    ``seed`` fixes both the order and the sampling) takes one training step on its sampled subgraph, ``model(batch.x, batch.index)``, with the
+    loss on ``out[batch.seed_rows]`` against ``batch.y`` (``ops.softmax_cross_entropy`` unless ``loss_fn`` is given).  Then ONE
+    full-graph forward under ``no_grad`` in EVAL mode (running statistics, no dropout: a sampled batch's statistics say nothing about
+    the full graph's) and the device bookkeeping of ``train_node_classification``, unchanged: ``ops.node_eval`` over the three
+    splits, ``ops.EarlyStop.update``, the predicated best-weights copy, a poll of the 32-byte record every ``poll_every`` epochs.
+    The per-batch read of the two subgraph counts (``ops.sample_neighbors``) is the loop's only synchronisation between polls.
+    Returns a ``NodeClassificationResult`` with the figures of the last counted epoch; the best weights are loaded back and the
+    model is left in training mode.  ``fanouts`` is required (one entry per hop, ``kagnn_amd.receptive_hops(model)`` of them for
+    the model's full depth)."""
+    from . import ops as ops_mod
+    from .data import NeighborLoader
+    if fanouts is None:
+        raise ValueError("train_node_classification_sampled: fanouts is required (one fan-out per hop, -1 for all neighbours)")
+    fan = ops_mod._fanouts("train_node_classification_sampled", fanouts)
+    epochs, poll_every = int(epochs), max(1, int(poll_every))
+    ops_mod._need_cuda(x, y, train_mask, val_mask, test_mask, *model.parameters())
+    if test_mask is None:
+        test_mask = val_mask
+    g = edge_index if isinstance(edge_index, ops_mod.GraphIndex) else ops_mod.graph_index(edge_index, x.size(0))
+    bits = ops_mod.split_bits(train_mask, val_mask, test_mask)
+    generator = torch.Generator().manual_seed(int(seed) & 0x7FFFFFFFFFFFFFFF)
+    loader = NeighborLoader(g, train_mask, fan, batch_size, shuffle=True, generator=generator, seed=seed, x=x, y=y)
+    if optimizer is None:
+        optimizer = Adam(model.parameters(), lr=lr)
+    best = _BestWeights(model, "train_node_classification_sampled")
+    stop = ops_mod.EarlyStop(patience, min_delta, max_epochs=epochs, num_splits=3, device=x.device)
+    records = torch.empty((3, 3), dtype=torch.int64, device=x.device)
+    step = _training_step(optimizer)
+
+    def batch_loss(batch):
+        out = model(batch.x, batch.index)[batch.seed_rows]
+        return ops_mod.softmax_cross_entropy(out, batch.y) if loss_fn is None else loss_fn(out, batch.y)
+
+    def one_epoch():
+        model.train()
+        for batch in loader:
+            step(batch_loss, batch)
+        model.eval()
+        with torch.no_grad():
+            out = model(x, g)
+        ops_mod.node_eval(out, y, bits, 3, out=records)
+        stop.update(records, 1)
+
+    _run_until_stopped(one_epoch, epochs, poll_every, stop, best)
+    model.train()
+    ops_mod.flush_graph_checks(x.device)
+    st = stop.read()
+    best.restore()
+    at = st.epochs - 1
+    nan = float("nan")
+    (_, train_acc), (val_loss, val_acc), (_, test_acc) = [_split_figures(st.history[at, s]) for s in range(3)] if at >= 0 else [(nan, nan)] * 3
+    return NodeClassificationResult(train_acc=train_acc, val_acc=val_acc, val_loss=val_loss, test_acc=test_acc, epochs_run=st.epochs,
+                                    best_epoch=st.best_epoch, stopped=st.stopped, history=st.history)
+
+
 def node_classification_splits(params: dict, x, edge_index, y, train_masks, val_masks, test_masks, **train_kw):
     """``all_splits`` of the reference (``node_classification_clean/utils.py:195-211``): a fresh ``make_model(params)`` trained by
     ``train_node_classification`` for every row of the ``[splits, N]`` mask tensors, with ``epochs``, ``lr`` and ``patience`` taken

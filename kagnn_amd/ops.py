@@ -501,14 +501,18 @@ def _subgraph_operands(what, ids, g):
     return ids.contiguous()
 
 
-def _subgraph_extract(what, hop, rec, g: GraphIndex, ids, keep_hops: bool) -> Subgraph:
+def _subgraph_extract(what, hop, rec, g: GraphIndex, ids, keep_hops: bool, keep=None) -> Subgraph:
     """``hop`` [N] int32 selects the nodes (>= 0); ``rec`` = device int32 [n_sub, e_sub, bad-seed flag]: count, the ONE read-back
-    (pinned memory), fill with exact sizes"""
+    (pinned memory), fill with exact sizes.  ``keep`` [E] uint8: the subgraph of that edge selection (the ``kagnn_edge_subgraph_*``
+    pair) in place of the induced one"""
     n, e, dev = g.num_nodes, g.num_edges, g.device
     i32, i64 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.int64, device=dev)
     ws = _ws(_sizes("kagnn_subgraph_workspace_bytes", n, e), dev)
     parent = [_ptr(t) for t in (g.rowptr, g.col, g.perm, g.rowptr_t, g.col_t, g.perm_t)]
-    _call("kagnn_subgraph_count", _ptr(hop), *parent, n, e, _ptr(ws), ws.numel(), _ptr(rec), _stream())
+    if keep is None:
+        _call("kagnn_subgraph_count", _ptr(hop), *parent, n, e, _ptr(ws), ws.numel(), _ptr(rec), _stream())
+    else:
+        _call("kagnn_edge_subgraph_count", _ptr(hop), _ptr(keep), *parent, n, e, _ptr(ws), ws.numel(), _ptr(rec), _stream())
     host = torch.empty(3, dtype=torch.int32, pin_memory=True)
     host.copy_(rec, non_blocking=True)
     ev = torch.cuda.Event()
@@ -520,8 +524,11 @@ def _subgraph_extract(what, hop, rec, g: GraphIndex, ids, keep_hops: bool) -> Su
     nodes, edge_ids, ei = torch.empty(n_sub, **i64), torch.empty(e_sub, **i64), torch.empty((2, e_sub), **i64)
     rowptr, col, perm = torch.empty(n_sub + 1, **i32), torch.empty(e_sub, **i32), torch.empty(e_sub, **i32)
     rowptr_t, col_t, perm_t = torch.empty(n_sub + 1, **i32), torch.empty(e_sub, **i32), torch.empty(e_sub, **i32)
-    _call("kagnn_subgraph_fill", _ptr(ws), ws.numel(), *parent, n, e, n_sub, e_sub, _ptr(nodes), _ptr(edge_ids), _ptr(ei),
-          _ptr(rowptr), _ptr(col), _ptr(perm), _ptr(rowptr_t), _ptr(col_t), _ptr(perm_t), _stream())
+    outs = [_ptr(t) for t in (nodes, edge_ids, ei, rowptr, col, perm, rowptr_t, col_t, perm_t)]
+    if keep is None:
+        _call("kagnn_subgraph_fill", _ptr(ws), ws.numel(), *parent, n, e, n_sub, e_sub, *outs, _stream())
+    else:
+        _call("kagnn_edge_subgraph_fill", _ptr(ws), ws.numel(), _ptr(keep), *parent, n, e, n_sub, e_sub, *outs, _stream())
     mapping = None
     if ids is not None:
         relabel = ws[:4 * n].view(torch.int32)             # (the workspace begins with relabel[N]: kagnn_hip.h)
@@ -570,6 +577,57 @@ def induced_subgraph(nodes, g: GraphIndex) -> Subgraph:
             return _subgraph_extract("induced_subgraph", hop, rec, g, None, False)
         hop, rec = _mark_hops(ids, 0, g)
         return _subgraph_extract("induced_subgraph", hop, rec, g, ids, False)
+
+
+def _fanouts(what, fanouts) -> list:
+    """the fan-outs of ``sample_neighbors`` as a list of ints: 1 .. 16 integers, each a count (>= 0) or -1 (all)"""
+    if isinstance(fanouts, torch.Tensor):
+        fanouts = fanouts.tolist() if fanouts.dim() == 1 and not fanouts.is_cuda else None
+    try:
+        out = list(fanouts)
+    except TypeError:
+        out = None
+    if out is None or not 1 <= len(out) <= _lib.SAMPLE_MAX_LEVELS:
+        raise ValueError(f"{what}: fanouts must be a sequence of 1 to {_lib.SAMPLE_MAX_LEVELS} integers, got {fanouts!r}")
+    for k in out:
+        if isinstance(k, bool) or not isinstance(k, (int, float)) or int(k) != k or k < -1 or k > 2147483647:
+            raise ValueError(f"{what}: every fan-out must be an integer >= 0, or -1 for all neighbours; got {k!r}")
+    return [int(k) for k in out]
+
+
+def sample_neighbors(node_idx, fanouts, g: GraphIndex, seed: int = 0) -> Subgraph:
+    """Fan-out-limited neighbour sampling on the parent's index ``g`` (GraphSAGE; what torch_geometric's ``NeighborLoader`` draws
+    per batch, directed and without replacement): level ``d`` of a backward BFS from ``node_idx`` (an int, a sequence or an int64
+    device vector; duplicates allowed) keeps, for every node first reached at level ``d``, ``min(in-degree, fanouts[d])`` of its
+    in-edges -- ``-1``: all of them -- and reaches their sources.  Returns the ``Subgraph`` of the kept EDGES (not the induced
+    one): ``nodes`` ascending, ``edge_ids`` the kept edges in original order, ``hops`` the level at which a node was first reached,
+    ``mapping`` the seeds' rows, ``index`` the bits ``GraphIndex(sub.edge_index, sub.num_nodes)`` would hold, nothing sorted.
+    Which edges a row keeps is a pure function of ``(seed, original edge id)`` (``kagnn_hip.h``: the ``k`` smallest ``(key32, e)``
+    of the row): the result does not depend on the order or duplication of the seeds, and two calls return the same bits.
+    ``kagnn_neighbor_sample_mark`` -> ``kagnn_edge_subgraph_count`` -> one read of the two counts and the bad-seed flag ->
+    ``kagnn_edge_subgraph_fill``.  ``seed``: any int, taken mod 2^64.  Raises ``ValueError`` for a mask as seeds, ``len(fanouts)``
+    outside 1..16, an entry below -1 or not an integer (all before any launch) and for a seed outside ``[0, N)`` (after the read);
+    empty seeds give an empty subgraph."""
+    fan = _fanouts("sample_neighbors", fanouts)
+    if isinstance(seed, bool) or not isinstance(seed, int):
+        raise ValueError(f"sample_neighbors: seed must be an int, got {seed!r}")
+    if isinstance(node_idx, torch.Tensor) and node_idx.dtype == torch.bool:
+        raise ValueError("sample_neighbors: node_idx must be node ids, not a mask")
+    ids = _subgraph_operands("sample_neighbors", node_idx, g)
+    with _device_of(g.rowptr):
+        hop, keep, rec = _mark_sampled(ids, fan, g, seed)
+        return _subgraph_extract("sample_neighbors", hop, rec, g, ids, True, keep)
+
+
+def _mark_sampled(ids, fan, g: GraphIndex, seed: int):
+    n, e, dev = g.num_nodes, g.num_edges, g.device
+    hop = torch.empty(n, dtype=torch.int32, device=dev)
+    keep = torch.empty(e, dtype=torch.uint8, device=dev)
+    rec = torch.empty(3, dtype=torch.int32, device=dev)
+    fan_host = (ctypes.c_int32 * len(fan))(*fan)
+    _call("kagnn_neighbor_sample_mark", _ptr(g.rowptr), _ptr(g.col), _ptr(g.perm), n, e, _ptr(ids), ids.numel(), fan_host, len(fan),
+          int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(hop), _ptr(keep), _ptr(rec[2:]), _stream())
+    return hop, keep, rec
 
 
 class WeightedGcnGraph:
