@@ -32,6 +32,51 @@ __device__ __forceinline__ void stats_products(const AggArgs& a, long row, int c
     pb = make_float4(o.x * ((y.x - m.x) * q.x), o.y * ((y.y - m.y) * q.y), o.z * ((y.z - m.z) * q.z), o.w * ((y.w - m.w) * q.w));
 }
 
+// The gather loop of the LEAN row kernel (unit weights): acc += x[col[e]] for e = s .. t-1, in that order -- acc + v is what
+// fmaf(1.0f, v, acc) rounds to, so the bits are those of the loop in agg_rows_v4_body.  That loop walks a row as a chain of
+// dependent memory latencies, two per step of four edges (the indices, then the rows they name) and two more per edge of the row's
+// last 1..3; at the four waves per SIMD the co-run launch is held to, the chain and not the bandwidth sets the pace.  Here the
+// indices of the NEXT step -- four edges, or the row's last 1..3 -- are loaded while this step's rows are in flight, and the last
+// edges are one step of their own (a lane without the edge adds -0.0f, which changes no value: x + -0.0f == x, also for
+// x = -0.0f and +0.0f): one latency per step.  The address is one 32 x 32 -> 64 bit multiply-add (xc + j * ldb; ldb = the row
+// stride in bytes, aggregate_corun_ok holds it below 2^32) instead of a 64 x 64 bit product.  Measured: 0.467 -> 0.411 ms per pass
+// at the headline graph under the cap, but 0.406 -> 0.427 at eight waves per SIMD (profiles/bwd_corun_priority.md), so only the
+// co-run kernel has it.
+__device__ __forceinline__ void add4(float4& a, const float4& v) { a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w; }
+__device__ __forceinline__ void lean_gather(float4& acc, const float* xc, unsigned ldb, const int* __restrict__ col, int s, int t) {
+    auto row = [&](int j) { return *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(xc) + (unsigned long)(unsigned)j * ldb); };
+    if (s >= t) return;
+    const int* cp = col + s;
+    int n = (t - s) >> 2;                          // whole steps
+    const int r = (t - s) & 3;                     // and the last 0..3 edges, a step of their own
+    int j0 = 0, j1 = 0, j2 = 0, j3 = 0;
+    if (n > 0) { j0 = cp[0]; j1 = cp[1]; j2 = cp[2]; j3 = cp[3]; }
+    else { j0 = cp[0]; if (r > 1) j1 = cp[1]; if (r > 2) j2 = cp[2]; }
+    while (n > 0) {
+        // (the empty statements pin each address computation behind the load before it -- one address alive at a time: the
+        // kernel has 40 registers, host.h: kAggCorunVgprs -- and emit nothing)
+        const float4 v0 = row(j0);
+        asm volatile("" : "+v"(j1) : : "memory");
+        const float4 v1 = row(j1);
+        asm volatile("" : "+v"(j2) : : "memory");
+        const float4 v2 = row(j2);
+        asm volatile("" : "+v"(j3) : : "memory");
+        const float4 v3 = row(j3);
+        asm volatile("" : : : "memory");
+        cp += 4;
+        --n;
+        if (n > 0) { j0 = cp[0]; j1 = cp[1]; j2 = cp[2]; j3 = cp[3]; }
+        else if (r > 0) { j0 = cp[0]; if (r > 1) j1 = cp[1]; if (r > 2) j2 = cp[2]; }
+        add4(acc, v0); add4(acc, v1); add4(acc, v2); add4(acc, v3);
+    }
+    const float4 none = make_float4(-0.0f, -0.0f, -0.0f, -0.0f);
+    float4 v0 = none, v1 = none, v2 = none;
+    if (r > 0) v0 = row(j0);
+    if (r > 1) v1 = row(j1);
+    if (r > 2) v2 = row(j2);
+    add4(acc, v0); add4(acc, v1); add4(acc, v2);
+}
+
 // STATS: also leave the workgroup's column sums of the rows it stores (and of their products with xhat) in
 // a.st_partial[row group][2][F] -- rows of one workgroup meet in LDS and are added in row order (deterministic); hub rows
 // contribute nothing here (their final value exists only in agg_hub_merge_kernel, which adds their share)
@@ -61,7 +106,9 @@ __device__ __forceinline__ void agg_rows_v4_body(const AggArgs& args) {
         float4 acc = ld4(a.x + gid * a.ldx + c4);
         const float sw = a.self_scale * (a.in_scale ? a.in_scale[gid] : 1.0f);
         acc.x *= sw; acc.y *= sw; acc.z *= sw; acc.w *= sw;
-        if (!hub) {
+        if constexpr (LEAN) {
+            if (!hub) lean_gather(acc, a.x + c4, (unsigned)a.ldx * 4u, a.col, s, t);
+        } else if (!hub) {
             int e = s;
             for (; e + 4 <= t; e += 4) {
                 const int j0 = a.col[e], j1 = a.col[e + 1], j2 = a.col[e + 2], j3 = a.col[e + 3];
@@ -121,7 +168,7 @@ __global__ __launch_bounds__(256) void agg_rows_v4_kernel(AggArgs a) { agg_rows_
 // The row kernel of the backward's transposed aggregation when the layer's deferred weight gradients run beside it (layer_bwd_impl,
 // fused_calls.hip; host.h: AggCorun).  A weight-gradient wave holds 352 of a SIMD's 512 registers, so what runs beside it has 160:
 // this instantiation must stay at or below kAggCorunVgprs = 40 allocated registers, four waves per SIMD
-// (tests/test_bwd_overlap_cpu.py reads the compiler's metadata).  It covers the row groups from a.wg0 on.
+// (tests/test_bwd_overlap_cpu.py reads the compiler's metadata; it has 33 with lean_gather).  It covers the row groups from a.wg0 on.
 template <int LPR>
 __global__ __launch_bounds__(256) void agg_rows_v4_corun_kernel(AggArgs a) { agg_rows_v4_body<LPR, false, true>(a); }
 
@@ -571,14 +618,16 @@ long aggregate_stats_rows(long N, int F, long num_hub_seg) { return (long)cdiv(N
 // The co-run launch (fused_calls.hip: the backward's transposed aggregation beside the deferred weight gradients) exists for the
 // shape it was measured at (profiles/bwd_overlap.md): 16 lanes per row, what agg_rows_v4_corun_kernel leaves out not asked for
 bool aggregate_corun_ok(const AggArgs& a) {
-    return vec4_ok(a) && a.F > 32 && a.F <= 64 && !a.ew && !a.in_scale && !a.out_scale && !a.bias && !a.skip_self && !a.col_scale && !a.st_partial;
+    return vec4_ok(a) && a.F > 32 && a.F <= 64 && !a.ew && !a.in_scale && !a.out_scale && !a.bias && !a.skip_self && !a.col_scale && !a.st_partial &&
+           a.ldx < (1L << 30);          // (lean_gather multiplies by the row stride in BYTES as a 32-bit number)
 }
 
-// corun (only where aggregate_corun_ok): the rows go through agg_rows_v4_corun_kernel in two launches (host.h: AggCorun); the hub
-// kernels are short and stay as they are, behind both.  Every row is computed as in the plain launch: same bits.
+// corun (only where aggregate_corun_ok): the rows go through agg_rows_v4_corun_kernel in two launches, or in one when the head is
+// all of them (host.h: AggCorun); the hub kernels are short and stay as they are, behind the join.  Every row is computed as in the
+// plain launch: same bits.
 int aggregate_sum(const AggArgs& a, const int* hub_seg, long num_hub_seg, float* ws, size_t ws_bytes, hipStream_t st, const AggCorun* corun) {
     if (a.N == 0) return KAGNN_OK;
-    if (corun && !(aggregate_corun_ok(a) && corun->head_pct >= 0 && corun->head_pct < 100 && corun->side_done))
+    if (corun && !(aggregate_corun_ok(a) && corun->head_pct >= 0 && corun->head_pct <= 100 && corun->side_done))
         return fail(KAGNN_ERR_ARG, "%s: the co-run launch does not cover this call", "aggregate_sum");
     const bool stats = a.st_partial != nullptr;
     if (stats && !aggregate_stats_ok(a)) return fail(KAGNN_ERR_UNSUPPORTED, "%s: column statistics need 16-byte aligned fp32 rows of 17..256 columns", "aggregate_sum");
@@ -618,9 +667,11 @@ int aggregate_sum(const AggArgs& a, const int* hub_seg, long num_hub_seg, float*
                     KAGNN_LAUNCH_CHECK();                                             \
                 }                                                                     \
                 KAGNN_HIP(hipStreamWaitEvent(st, corun->side_done, 0));               \
-                AggArgs t = b;                                                        \
-                t.wg0 = head;                                                         \
-                agg_rows_v4_corun_kernel<16><<<total - head, 256, 0, st>>>(t);        \
+                if (head < total) {          /* (a head of 100 per cent leaves no tail) */ \
+                    AggArgs t = b;                                                    \
+                    t.wg0 = head;                                                     \
+                    agg_rows_v4_corun_kernel<16><<<total - head, 256, 0, st>>>(t);    \
+                }                                                                     \
             } else                                                                    \
                 agg_rows_v4_kernel<LPR><<<AGG_ROWS_GRID(a.N * LPR), 256, 0, st>>>(b);   \
             KAGNN_LAUNCH_CHECK();                                                     \

@@ -3,6 +3,7 @@
 // and launchers (same kernels, same order, same bits as composing them), on ONE caller-provided workspace whose layout is written
 // down once per call family (LayerLayout, StackLayout, KmLayout) and read by the size query and by both directions.
 #include "host.h"
+#include <algorithm>
 #include <mutex>
 
 using namespace kagnn;
@@ -267,12 +268,13 @@ public:
 
 // the weight gradient whose footprint the co-run launch of the aggregation was sized for (host.h: kAggCorunLds): the cubic
 // kan_split_dw_kernel of one 64 x 64 role, one workgroup per CU.  Other shapes run other kernels; they keep their place.
-// kAggCorunHeadPct: the share of the aggregation's row groups that runs beside ONE such weight gradient -- at the headline shape
-// (N = 1M, E = 10M, 64 features) two of them take 0.61 ms and the held-back row kernel covers 55-60 % of its rows meanwhile; a
-// head of 70 % measured best and 55-80 % within the run-to-run spread of it (profiles/bwd_overlap.md).  A graph with other degrees
-// moves the balance, not the result: the head that outlasts the weight gradients runs on with four waves per SIMD, the tail
-// of a head that ends early waits for them.
-constexpr int kAggCorunHeadPct = 35;
+// kAggCorunHeadPct: the share of the aggregation's row groups that runs beside ONE such weight gradient.  At the headline shape
+// (N = 1M, E = 10M, 64 features) the held-back row kernel needs 0.41 ms alone and two weight gradients 0.60 ms: with both deferred
+// the head is the whole aggregation, launched once, and no tail follows the join (measured best of 35 / 40 / 45 / 50,
+// profiles/bwd_corun_priority.md); with one deferred (the node models) half of the rows run beside it.  A graph with other degrees
+// moves the balance, not the result: the head that outlasts the weight gradients runs on with four waves per SIMD, the tail of
+// a head that ends early waits for them.
+constexpr int kAggCorunHeadPct = 50;
 bool dw_corun_ok(int in, int out, int G, int K, int mode) {
     return use_split_dw(in, out, G, K, mode) && !g_half_products && K == 3 && G + K <= 8 && in > 32 && in <= 64 && out <= 64;
 }
@@ -430,9 +432,9 @@ int layer_bwd_impl(const GraphSide& gr, const KanChain& c, const LayerGrads& io,
         const AggArgs a{g, ldg, static_cast<float*>(gx), io.ldgx, gr.rowptr, gr.col, nullptr, N, f0, gr.self_scale, nullptr, nullptr, nullptr,
                         0, gr.hub_threshold > 0 ? gr.hub_threshold : 0x7fffffff, io.gx_addend, io.ld_addend};
         // the join sits INSIDE the aggregation: kAggCorunHeadPct of the row groups per deferred weight gradient run beside them, held
-        // to what a weight-gradient wave leaves free; then this stream waits for the side stream and the rest of the rows have the
-        // machine to themselves (host.h: AggCorun)
-        AggCorun corun{kAggCorunHeadPct * n_deferred, nullptr};
+        // to what a weight-gradient wave leaves free; then this stream waits for the side stream and the rest of the rows, if any,
+        // have the machine to themselves (host.h: AggCorun)
+        AggCorun corun{std::min(100, kAggCorunHeadPct * n_deferred), nullptr};
         rc = side.side_done(&corun.side_done);
         if (rc) return rc;
         KAGNN_STAGE_AS("kagnn_aggregate_sum", stream);

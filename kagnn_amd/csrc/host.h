@@ -12,8 +12,9 @@ struct RbfArgs;                                     // split_common.h (device-si
 // ---- aggregate.hip
 size_t aggregate_ws_bytes(long num_hub_seg, int F);
 // The co-run launch of the row kernel: the backward's transposed aggregation while the layer's deferred weight gradients run on
-// a side stream (fused_calls.hip: layer_bwd_impl; measurements: profiles/bwd_overlap.md).  The row groups go in two launches of
-// agg_rows_v4_corun_kernel.  The HEAD -- the first head_pct per cent of them -- runs beside the weight gradients and must never keep
+// a side stream (fused_calls.hip: layer_bwd_impl; measurements: profiles/bwd_overlap.md, profiles/bwd_corun_priority.md).  The row
+// groups go in two launches of agg_rows_v4_corun_kernel, or in one when head_pct is 100 (then there is no tail: the head, the wait
+// for side_done, the hub kernels).  The HEAD -- the first head_pct per cent of them -- runs beside the weight gradients and must never keep
 // one of their workgroups from being placed: a weight-gradient wave holds 352 of a SIMD's 512 registers and its workgroup 2.5 KB of
 // a CU's 160 KiB of LDS, so the head asks for kAggCorunLds bytes of dynamic LDS it never touches -- four such requests fit beside
 // that workgroup, five do not even alone -- which holds it to four 256-thread workgroups per CU = four waves per SIMD of at most
