@@ -55,7 +55,7 @@ extern "C" {
 #define KAGNN_DTYPE_F32 0
 #define KAGNN_DTYPE_BF16 1
 
-int kagnn_version(void);          /* 277 = 276 + kagnn_neighbor_sample_mark, kagnn_edge_subgraph_count, kagnn_edge_subgraph_fill; 276 = 275 + kagnn_k_hop_mark, kagnn_subgraph_count, kagnn_subgraph_fill (+ kagnn_subgraph_workspace_bytes); 273 = 272 with kagnn_kan_grid_refit on kagnn_kan_grid_resize's kernels (up to 46 coefficients; its bits and its workspace size change); 272 = 271 + kagnn_kan_grid_resize (+ _workspace_bytes); 271 = 270 + kagnn_attention_fwd, kagnn_attention_bwd (+ _workspace_bytes); 270 = 269 + kagnn_fastkan_edge_abs_sum, kagnn_fastkan_edge_abs_sum_bwd (+ _workspace_bytes), kagnn_fastkan_edge_curves; 269 = 268 + kagnn_kan_edge_abs_sum, kagnn_kan_edge_abs_sum_bwd (+ _workspace_bytes), kagnn_kan_edge_curves; 268 = 267 + spline orders 5..KAGNN_MAX_SPLINE_ORDER in the per-operation KANLinear calls (no new entry point); 267 = 266 + kagnn_linear_fwd, kagnn_linear_bwd_input, kagnn_linear_bwd_weight (+ _workspace_bytes); 266 = 265 + kagnn_l1_loss_meter_fwd, kagnn_regression_epoch_update; 265 = 264 + kagnn_node_eval, kagnn_early_stop_update, kagnn_copy_if; 264 = 263 + kagnn_degree_one_hot, kagnn_nll_loss_fwd / _bwd; 263 = 262 + kagnn_batch_assemble; 262 = 261 - the fields edge_src, edge_dst, csr_flags of kagnn_kagin_model_t; 261 = 260 + kagnn_fastkan_fwd_stats_in_kernel; 260 = round 6: + the feature-sharded FastKAN entry points kagnn_fastkan_row_moments .. _shard_bwd_finish, + kagnn_kagin_model_*; 250 = 240 + KAGNN_PREC_HALF; 240 = 230 + kagnn_gin_kan_layer_bwd_bn_sums; 230 = 220 + the *_affine entry points of a folded BatchNorm1d; 220 = 210 + the stage timer) */
+int kagnn_version(void);          /* 278 = 277 + kagnn_edge_keys_build (+ _workspace_bytes), kagnn_negative_sample, kagnn_bce_logits_fwd / _bwd, kagnn_link_rank (+ _workspace_bytes); 277 = 276 + kagnn_neighbor_sample_mark, kagnn_edge_subgraph_count, kagnn_edge_subgraph_fill; 276 = 275 + kagnn_k_hop_mark, kagnn_subgraph_count, kagnn_subgraph_fill (+ kagnn_subgraph_workspace_bytes); 273 = 272 with kagnn_kan_grid_refit on kagnn_kan_grid_resize's kernels (up to 46 coefficients; its bits and its workspace size change); 272 = 271 + kagnn_kan_grid_resize (+ _workspace_bytes); 271 = 270 + kagnn_attention_fwd, kagnn_attention_bwd (+ _workspace_bytes); 270 = 269 + kagnn_fastkan_edge_abs_sum, kagnn_fastkan_edge_abs_sum_bwd (+ _workspace_bytes), kagnn_fastkan_edge_curves; 269 = 268 + kagnn_kan_edge_abs_sum, kagnn_kan_edge_abs_sum_bwd (+ _workspace_bytes), kagnn_kan_edge_curves; 268 = 267 + spline orders 5..KAGNN_MAX_SPLINE_ORDER in the per-operation KANLinear calls (no new entry point); 267 = 266 + kagnn_linear_fwd, kagnn_linear_bwd_input, kagnn_linear_bwd_weight (+ _workspace_bytes); 266 = 265 + kagnn_l1_loss_meter_fwd, kagnn_regression_epoch_update; 265 = 264 + kagnn_node_eval, kagnn_early_stop_update, kagnn_copy_if; 264 = 263 + kagnn_degree_one_hot, kagnn_nll_loss_fwd / _bwd; 263 = 262 + kagnn_batch_assemble; 262 = 261 - the fields edge_src, edge_dst, csr_flags of kagnn_kagin_model_t; 261 = 260 + kagnn_fastkan_fwd_stats_in_kernel; 260 = round 6: + the feature-sharded FastKAN entry points kagnn_fastkan_row_moments .. _shard_bwd_finish, + kagnn_kagin_model_*; 250 = 240 + KAGNN_PREC_HALF; 240 = 230 + kagnn_gin_kan_layer_bwd_bn_sums; 230 = 220 + the *_affine entry points of a folded BatchNorm1d; 220 = 210 + the stage timer) */
 const char* kagnn_last_error(void);
 
 /* Stage timer -- a measurement aid, off by default (no reference counterpart: the reference times whole epochs with
@@ -176,6 +176,53 @@ int kagnn_edge_subgraph_fill(const void* workspace, size_t workspace_bytes, cons
                              const int32_t* perm_t, int64_t num_nodes, int64_t num_edges, int64_t n_sub, int64_t e_sub, int64_t* nodes,
                              int64_t* edge_ids, int64_t* edge_index_sub, int32_t* rowptr_sub, int32_t* col_sub, int32_t* perm_sub,
                              int32_t* rowptr_t_sub, int32_t* col_t_sub, int32_t* perm_t_sub, void* stream);
+
+/* Link prediction around an encoder (torch_geometric's recipe: RandomLinkSplit, uniform negative_sampling, a dot-product decoder,
+ * BCEWithLogitsLoss, ROC-AUC; no counterpart in the reference snapshot, which has no link-prediction script).  The decoder needs no
+ * entry point of its own: the score <z[u], z[v]> of every pair is kagnn_aggregate_edge_grad with x = gout = z over the pair list's
+ * by-destination structure, its gradient kagnn_aggregate_sum + kagnn_aggregate_sum_add with the upstream gradient as edge weights.
+ * Every result below is a pure function of its inputs -- no float atomics, two calls return the same bits -- and nothing
+ * synchronises the stream.  Indices the caller sees are int64.
+ *
+ * kagnn_edge_keys_build: the edge set of (src, dst) = edge_index[0], edge_index[1] as keys[0 .. *num_keys) = the ascending,
+ *   duplicate-free values src * num_nodes + dst (int64; a rocPRIM radix sort and a unique pass); `keys` holds num_edges elements,
+ *   num_keys is a DEVICE word.  Ids outside [0, num_nodes) are clamped to 0.  num_edges == 0: only *num_keys = 0 is written.
+ *   Workspace: kagnn_edge_keys_workspace_bytes(num_edges).
+ * kagnn_negative_sample: `num` slots of uniform negative pairs.  Slot p tries the attempts t = 0 .. attempts - 1 with the counter
+ *   c = p * attempts + t:  u = ((uint64)key32(seed, 2c) * num_nodes) >> 32,  v = ((uint64)key32(seed, 2c + 1) * num_nodes) >> 32
+ *   (key32: kagnn_neighbor_sample_mark above).  An attempt is valid iff u != v and u * num_nodes + v is not among keys[0 .. num_keys)
+ *   (a binary search); the slot takes its FIRST valid attempt: pairs[p] = u, pairs[num + p] = v, valid[p] = 1.  A slot without one
+ *   is EMPTY: the pair (0, 0) and valid[p] = 0.  pairs: int64 [2, num]; valid: bytes [num]; a fixed size, so nothing is compacted
+ *   or read back.  Refused before any launch: attempts outside 1..KAGNN_NEGATIVE_MAX_ATTEMPTS, 2 * num * attempts >= 2^32,
+ *   num_nodes >= 2^31.  num == 0 or num_nodes == 0: nothing is launched.
+ * kagnn_bce_logits_fwd: F.binary_cross_entropy_with_logits over the rows of weight 1 (weight NULL: all): loss[0] = the mean of
+ *   max(s, 0) - s y + log1p(exp(-|s|)), y = (labels[p] != 0), the term in fp32, the sum in fp64 partials added in a fixed order
+ *   (a thread's rows ascending, a fixed tree, the workgroups in index order), divided by divisor[0] = max(rows, 1) -- a DEVICE
+ *   int64 the backward reads -- and rounded once.  `record` (NULL: none): one row of kagnn_node_eval's format, WRITTEN in the same
+ *   call: {double loss sum; int64 rows with (s > 0) == y; int64 rows}.  A NaN score makes the sum NaN and counts like any other
+ *   score.  Up to 4096 rows: one launch, no workspace; above: KAGNN_BCE_WORKSPACE_BYTES of 8-byte aligned workspace.
+ * kagnn_bce_logits_bwd: g_scores[p] = (sigmoid(s) - y) * g_loss[0] / divisor[0] on rows of weight 1, exactly 0 elsewhere.
+ * kagnn_link_rank: record = int64[8] = {2U, n_pos, n_neg, nan_rows, hits[k0], hits[k1], hits[k2], 0} over the rows of weight 1
+ *   whose score is not NaN (those are counted in nan_rows):  2U = sum over positives i and negatives j of (2 if s_i > s_j, 1 if
+ *   s_i == s_j), so ROC-AUC = 2U / (2 n_pos n_neg);  hits[k] = the positives STRICTLY above the k-th largest negative score (all
+ *   of them when there are fewer than k negatives; 0 for the k's not given).  -0.0 and +0.0 tie, +-Inf are ordinary values.  Exact:
+ *   an order-preserving 32-bit key per score, one radix sort with the label as value, an exclusive scan of the negatives, two
+ *   binary searches per positive, int64 sums (integer atomics).  ks_host: a HOST array of num_ks <= 3 values >= 1.  Workspace:
+ *   kagnn_link_rank_workspace_bytes(num_rows). */
+#define KAGNN_NEGATIVE_MAX_ATTEMPTS 32
+#define KAGNN_BCE_WORKSPACE_BYTES 6144
+int kagnn_edge_keys_workspace_bytes(int64_t num_edges, size_t* bytes_host);
+int kagnn_edge_keys_build(const int64_t* src, const int64_t* dst, int64_t num_edges, int64_t num_nodes, int64_t* keys,
+                          int64_t* num_keys, void* workspace, size_t workspace_bytes, void* stream);
+int kagnn_negative_sample(const int64_t* keys, int64_t num_keys, int64_t num_nodes, int64_t num, uint64_t seed, int32_t attempts,
+                          int64_t* pairs, uint8_t* valid, void* stream);
+int kagnn_bce_logits_fwd(const float* scores, const uint8_t* labels, const uint8_t* weight, int64_t num_rows, float* loss,
+                         int64_t* divisor, void* record, void* workspace, size_t workspace_bytes, void* stream);
+int kagnn_bce_logits_bwd(const float* scores, const uint8_t* labels, const uint8_t* weight, int64_t num_rows, const int64_t* divisor,
+                         const float* g_loss, float* g_scores, void* stream);
+int kagnn_link_rank_workspace_bytes(int64_t num_rows, size_t* bytes_host);
+int kagnn_link_rank(const float* scores, const uint8_t* labels, const uint8_t* weight, int64_t num_rows, const int32_t* ks_host,
+                    int32_t num_ks, int64_t* record, void* workspace, size_t workspace_bytes, void* stream);
 
 /* in-degree normalisation of GCN (torch_geometric gcn_norm as used by KAGCNConv,
  * node_classification_clean/models.py:31-37): dis[i] = (1 + #non-loop in-edges of i)^-1/2.

@@ -9,7 +9,7 @@ from .ekan import KAN, KANLinear, collect_edge_l1, refine_grids                 
 from .fastkan import (AttentionWithFastKANTransform, FastKAN, FastKANLayer, RadialBasisFunction,   # noqa: F401
                       SplineLinear)
 from .models import (FASTKAGATConv, FASTKAGCNConv, FKANLayer, GFASTKAN_Nodes,        # noqa: F401
-                     GIFASTKANLayer, GIKANLayer, GKAN_Nodes, KAGATConv, KAGCNConv, KANLayer)
+                     GIFASTKANLayer, GIKANLayer, GKAN_Nodes, KAGATConv, KAGCNConv, KANLayer, LinkPredictor)
 
 from .norm import BatchNorm1d                                                    # noqa: F401
 from .graph_models import (AtomEncoder, BondEncoder, FASTKAGAT, FASTKAGCN, FASTKAGCNRegression, FASTKAGIN, GINEKANLayer,   # noqa: F401
@@ -19,6 +19,7 @@ from . import baselines                                                         
 from .baselines import (GAT, GCN, GIN, GATConv, GCNConv, GCNRegression, GINConv, GINEConv, GINRegression, GNN_Nodes,   # noqa: F401
                         Linear, LinearReLU, make_mlp, make_mlp_nodes)
 from .explain import edge_mask, explain_edges, receptive_hops                    # noqa: F401
-from .data import DeviceBatch, DeviceBatchLoader, DeviceGraphDataset, NeighborLoader, NodeBatch   # noqa: F401
+from .data import (DeviceBatch, DeviceBatchLoader, DeviceGraphDataset, LinkSplit, NeighborLoader, NodeBatch,   # noqa: F401
+                   random_link_split)
 
 __version__ = "0.1.0"

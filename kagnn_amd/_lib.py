@@ -47,6 +47,18 @@ _SIGNATURES = {
     "kagnn_edge_subgraph_count": (c_int32, [_P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int64, _P, c_size_t, _P, _P]),
     "kagnn_edge_subgraph_fill": (c_int32, [_P, c_size_t, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int64, c_int64, c_int64,
                                            _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "kagnn_edge_keys_workspace_bytes": (c_int32, [c_int64, POINTER(c_size_t)]),
+    # src dst E N keys num_keys ws bytes stream
+    "kagnn_edge_keys_build": (c_int32, [_P, _P, c_int64, c_int64, _P, _P, _P, c_size_t, _P]),
+    # keys num_keys N num seed attempts pairs valid stream
+    "kagnn_negative_sample": (c_int32, [_P, c_int64, c_int64, c_int64, c_uint64, c_int32, _P, _P, _P]),
+    # scores labels weight P loss divisor record ws bytes stream
+    "kagnn_bce_logits_fwd": (c_int32, [_P, _P, _P, c_int64, _P, _P, _P, _P, c_size_t, _P]),
+    # scores labels weight P divisor g_loss g_scores stream
+    "kagnn_bce_logits_bwd": (c_int32, [_P, _P, _P, c_int64, _P, _P, _P, _P]),
+    "kagnn_link_rank_workspace_bytes": (c_int32, [c_int64, POINTER(c_size_t)]),
+    # scores labels weight P ks(host int32) num_ks record ws bytes stream
+    "kagnn_link_rank": (c_int32, [_P, _P, _P, c_int64, POINTER(c_int32), c_int32, _P, _P, c_size_t, _P]),
     "kagnn_gcn_deg_inv_sqrt": (c_int32, [_P, _P, c_int64, _P, _P]),
     "kagnn_aggregate_workspace_bytes": (c_int32, [c_int64, c_int32, POINTER(c_size_t)]),
     "kagnn_aggregate_sum": (c_int32, [_P, c_int64, _P, c_int64, _P, _P, _P, c_int64, c_int32, c_float,
@@ -269,6 +281,8 @@ class KaginModel(ctypes.Structure):
 BATCH_MAX_GRAPHS = 4096      # KAGNN_BATCH_MAX_GRAPHS
 REGRESSION_MAX_TARGETS = 32  # KAGNN_REGRESSION_MAX_TARGETS
 SAMPLE_MAX_LEVELS = 16       # KAGNN_SAMPLE_MAX_LEVELS
+NEGATIVE_MAX_ATTEMPTS = 32   # KAGNN_NEGATIVE_MAX_ATTEMPTS
+BCE_WORKSPACE_BYTES = 6144   # KAGNN_BCE_WORKSPACE_BYTES
 
 
 class BatchAssemble(ctypes.Structure):

@@ -84,7 +84,7 @@ using namespace kagnn;
 #pragma GCC visibility push(default)
 extern "C" {
 
-int kagnn_version(void) { return 277; }
+int kagnn_version(void) { return 278; }
 const char* kagnn_last_error(void) { return g_err; }
 
 int kagnn_stage_timer_enable(const char* only) {
@@ -243,6 +243,64 @@ int kagnn_edge_subgraph_fill(const void* ws, size_t ws_bytes, const uint8_t* kee
     return edge_subgraph_fill(ws, ws_bytes, keep, rowptr, col, perm, rowptr_t, col_t, perm_t, N, E, n_sub, e_sub, nodes,
                               edge_ids, edge_index_sub, rowptr_sub, col_sub, perm_sub, rowptr_t_sub, col_t_sub, perm_t_sub,
                               as_stream(stream));
+}
+
+// link prediction around an encoder (linkpred.hip)
+int kagnn_edge_keys_workspace_bytes(int64_t E, size_t* bytes) {
+    KAGNN_CHECK_ARG(bytes != nullptr && E >= 0 && E < 2147483647LL, "null output, or num_edges outside [0, 2^31)");
+    *bytes = edge_keys_ws_bytes(E);
+    return KAGNN_OK;
+}
+
+int kagnn_edge_keys_build(const int64_t* src, const int64_t* dst, int64_t E, int64_t N, int64_t* keys, int64_t* num_keys, void* ws,
+                          size_t ws_bytes, void* stream) {
+    KAGNN_STAGE(stream);
+    KAGNN_CHECK_ARG(E >= 0 && E < 2147483647LL && N >= 0 && N < 2147483648LL, "num_edges and num_nodes must lie below 2^31");
+    KAGNN_CHECK_ARG(E == 0 || N > 0, "edges without nodes");
+    KAGNN_CHECK_ARG(num_keys != nullptr && (E == 0 || (src && dst && keys && ws)), "null array");
+    return edge_keys_build(src, dst, E, N, keys, num_keys, ws, ws_bytes, as_stream(stream));
+}
+
+int kagnn_negative_sample(const int64_t* keys, int64_t num_keys, int64_t N, int64_t num, uint64_t seed, int32_t attempts, int64_t* pairs,
+                          uint8_t* valid, void* stream) {
+    KAGNN_STAGE(stream);
+    KAGNN_CHECK_ARG(attempts >= 1 && attempts <= KAGNN_NEGATIVE_MAX_ATTEMPTS, "attempts must be 1..32");
+    KAGNN_CHECK_ARG(num >= 0 && num < (1LL << 32) && 2 * num * (int64_t)attempts < (1LL << 32), "2 * num * attempts must lie below 2^32");
+    KAGNN_CHECK_ARG(N >= 0 && N < 2147483648LL && num_keys >= 0, "num_nodes must lie in [0, 2^31), num_keys >= 0");
+    if (num == 0 || N == 0) return KAGNN_OK;
+    KAGNN_CHECK_ARG(pairs && valid && (num_keys == 0 || keys), "null array");
+    return negative_sample(keys, num_keys, N, num, seed, attempts, pairs, valid, as_stream(stream));
+}
+
+int kagnn_bce_logits_fwd(const float* scores, const uint8_t* labels, const uint8_t* weight, int64_t P, float* loss, int64_t* divisor,
+                         void* record, void* ws, size_t ws_bytes, void* stream) {
+    KAGNN_STAGE(stream);
+    KAGNN_CHECK_ARG(P >= 0 && loss && divisor && (P == 0 || (scores && labels)), "null array or negative size");
+    KAGNN_CHECK_ARG((((uintptr_t)record | (uintptr_t)divisor) & 7) == 0, "the record and the divisor must be 8-byte aligned");
+    return bce_logits_fwd(scores, labels, weight, P, loss, divisor, record, ws, ws_bytes, as_stream(stream));
+}
+
+int kagnn_bce_logits_bwd(const float* scores, const uint8_t* labels, const uint8_t* weight, int64_t P, const int64_t* divisor,
+                         const float* g_loss, float* g_scores, void* stream) {
+    KAGNN_STAGE(stream);
+    KAGNN_CHECK_ARG(P >= 0 && (P == 0 || (scores && labels && divisor && g_loss && g_scores)), "null array or negative size");
+    return bce_logits_bwd(scores, labels, weight, P, divisor, g_loss, g_scores, as_stream(stream));
+}
+
+int kagnn_link_rank_workspace_bytes(int64_t P, size_t* bytes) {
+    KAGNN_CHECK_ARG(bytes != nullptr && P >= 0 && P < 2147483647LL, "null output, or num_rows outside [0, 2^31 - 1)");
+    *bytes = link_rank_ws_bytes(P);
+    return KAGNN_OK;
+}
+
+int kagnn_link_rank(const float* scores, const uint8_t* labels, const uint8_t* weight, int64_t P, const int32_t* ks_host, int32_t num_ks,
+                    int64_t* record, void* ws, size_t ws_bytes, void* stream) {
+    KAGNN_STAGE(stream);
+    KAGNN_CHECK_ARG(P >= 0 && P < 2147483647LL, "num_rows outside [0, 2^31 - 1)");
+    KAGNN_CHECK_ARG(num_ks >= 0 && num_ks <= 3 && (num_ks == 0 || ks_host), "at most 3 values of k, in a host array");
+    for (int j = 0; j < num_ks; ++j) KAGNN_CHECK_ARG(ks_host[j] >= 1, "a k below 1");
+    KAGNN_CHECK_ARG(record && ((uintptr_t)record & 7) == 0 && (P == 0 || (scores && labels)), "null array or misaligned record");
+    return link_rank(scores, labels, weight, P, ks_host, num_ks, record, ws, ws_bytes, as_stream(stream));
 }
 
 int kagnn_gcn_deg_inv_sqrt(const int32_t* rowptr, const int32_t* col, int64_t N, float* dis, void* stream) {

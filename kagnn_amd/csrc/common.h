@@ -96,11 +96,22 @@ __device__ __forceinline__ float silu_gradf(float x) {
 }
 
 // The 32-bit finaliser of the counter-based hashes: dropout's keep bits (bn.hip: keep4) and the sampling keys of
-// kagnn_neighbor_sample_mark (subgraph.hip: sample_key32).  Both are restated bit for bit by the tests.
+// kagnn_neighbor_sample_mark (sample_key32 below).  Both are restated bit for bit by the tests.
 __device__ __forceinline__ unsigned mix32(unsigned x) {
     x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16;
     return x;
 }
+
+// key32 of the ABI (include/kagnn_hip.h): h1, h2 are the two words of the 64-bit seed, hashed once per thread.  The sampling key of
+// kagnn_neighbor_sample_mark (subgraph.hip) and the draw of kagnn_negative_sample (linkpred.hip).
+struct SampleSeed { unsigned h1, h2; };
+__device__ __forceinline__ SampleSeed sample_seed(unsigned lo, unsigned hi) {
+    SampleSeed s;
+    s.h1 = mix32(lo + 0x9e3779b9U);
+    s.h2 = mix32(hi ^ s.h1 ^ 0x85ebca6bU);
+    return s;
+}
+__device__ __forceinline__ unsigned sample_key32(const SampleSeed& s, int e) { return mix32(mix32((unsigned)e ^ s.h1) + s.h2); }
 
 // Gaussian RBF of the FastKAN layer, exp(-((z - c) / denominator)^2): the one form its layer kernels (fastkan.hip) and its edge
 // kernels (fastkan_edge.hip) evaluate, so that the layer's output is the sum of its edge functions to rounding

@@ -128,6 +128,20 @@ int edge_subgraph_fill(const void* ws, size_t ws_bytes, const unsigned char* kee
                        int64_t* edge_ids, int64_t* ei, int* rowptr_o, int* col_o, int* perm_o, int* rowptr_to, int* col_to, int* perm_to,
                        hipStream_t st);
 
+// ---- linkpred.hip
+size_t edge_keys_ws_bytes(long E);
+int edge_keys_build(const int64_t* src, const int64_t* dst, long E, long N, int64_t* keys, int64_t* num_keys, void* ws, size_t ws_bytes,
+                    hipStream_t st);
+int negative_sample(const int64_t* keys, long K, long N, long num, unsigned long long seed, int T, int64_t* pairs, unsigned char* valid,
+                    hipStream_t st);
+int bce_logits_fwd(const float* s, const unsigned char* y, const unsigned char* w, long P, float* loss, int64_t* divisor, void* record,
+                   void* ws, size_t ws_bytes, hipStream_t st);
+int bce_logits_bwd(const float* s, const unsigned char* y, const unsigned char* w, long P, const int64_t* divisor, const float* g_loss,
+                   float* g, hipStream_t st);
+size_t link_rank_ws_bytes(long P);
+int link_rank(const float* s, const unsigned char* y, const unsigned char* wgt, long P, const int* ks_host, int num_ks, int64_t* record,
+              void* ws, size_t ws_bytes, hipStream_t st);
+
 // ---- kan_fp32.hip
 size_t kan_f32_pack_fwd_bytes(int in, int out, int C);
 size_t kan_f32_pack_dx_bytes(int in, int out, int C);

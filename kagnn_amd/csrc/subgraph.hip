@@ -59,15 +59,7 @@ __global__ __launch_bounds__(kSubThreads) void khop_level_kernel(const int* __re
 }
 
 // ------------------------------------------------------------------------------------------------- neighbour sampling
-// key32 of the ABI (include/kagnn_hip.h): h1, h2 are the two words of the 64-bit seed, hashed once per thread
-struct SampleSeed { unsigned h1, h2; };
-__device__ __forceinline__ SampleSeed sample_seed(unsigned lo, unsigned hi) {
-    SampleSeed s;
-    s.h1 = mix32(lo + 0x9e3779b9U);
-    s.h2 = mix32(hi ^ s.h1 ^ 0x85ebca6bU);
-    return s;
-}
-__device__ __forceinline__ unsigned sample_key32(const SampleSeed& s, int e) { return mix32(mix32((unsigned)e ^ s.h1) + s.h2); }
+// (key32 of the ABI -- sample_seed, sample_key32 -- lives in common.h: linkpred.hip draws its negatives from the same function)
 
 // entry p of an expanding row is selected: its edge is kept, its source joins level d + 1 if nobody reached it before
 __device__ __forceinline__ void sample_take(const int* __restrict__ col, int p, int e, long N, long E, int d, int* hop,

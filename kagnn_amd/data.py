@@ -13,6 +13,10 @@ CPU tensors as the place to keep the dataset are refused like everywhere else in
 The node-level side: ``NeighborLoader`` cuts the input nodes of ONE graph into mini-batches and samples a fan-out-limited
 neighbourhood around each on the device (``ops.sample_neighbors``, ``csrc/subgraph.hip``) -- a ``NodeBatch`` per step for the node
 models, again without host collation.
+
+The edge-level side: ``random_link_split`` cuts ONE graph's edges into training / validation / test positives with the
+message-passing graph each split may see (torch_geometric's ``RandomLinkSplit``, plain torch ops), and ``LinkSplit.with_negatives``
+draws the fixed evaluation negatives on the device (``ops.negative_sample``, ``csrc/linkpred.hip``).
 """
 from __future__ import annotations
 
@@ -547,3 +551,64 @@ class NeighborLoader:
                 out.x = None if self.x is None else self.x.index_select(0, sub.nodes)
                 out.y = None if self.y is None else self.y.index_select(0, seeds)
             yield out
+
+
+# ------------------------------------------------------------------------------------------------ link prediction: the edge split
+class LinkSplit:
+    """What ``random_link_split`` returns.  Per split a message-passing graph (int64 ``[2, E]``) and the positive pairs it is
+    scored on (int64 ``[2, P]``, ``u`` = row 0, ``v`` = row 1; with ``is_undirected`` the ``u < v`` representative of each edge):
+    ``train_edge_index / val_edge_index / test_edge_index`` and ``train_pos / val_pos / test_pos``.  ``edge_index`` is the full edge
+    list the split was drawn from, ``num_nodes`` its node count.  ``with_negatives`` adds ``val_neg / test_neg`` (int64 ``[2, P]``)
+    and ``val_neg_valid / test_neg_valid`` (uint8 ``[P]``: 0 marks an EMPTY slot of ``ops.negative_sample``, to be given weight 0);
+    they are ``None`` before."""
+    _FIELDS = ("edge_index", "num_nodes", "is_undirected", "train_edge_index", "val_edge_index", "test_edge_index", "train_pos",
+               "val_pos", "test_pos", "val_neg", "val_neg_valid", "test_neg", "test_neg_valid")
+
+    def __init__(self, **kw):
+        for k in self._FIELDS:
+            setattr(self, k, kw.get(k))
+
+    def __repr__(self):
+        sizes = ", ".join(f"{k}={int(getattr(self, k).size(1))}" for k in ("train_pos", "val_pos", "test_pos"))
+        return f"LinkSplit(num_nodes={self.num_nodes}, is_undirected={self.is_undirected}, {sizes}, negatives={self.val_neg is not None})"
+
+    def with_negatives(self, seed: int, ratio: float = 1.0) -> "LinkSplit":
+        """a copy with FIXED evaluation negatives: ``round(ratio * P)`` slots per split from ``ops.negative_sample`` against the
+        FULL edge set (no validation or test edge can be drawn as a negative), seeds ``seed + 1`` (validation) and ``seed + 2``
+        (test); drawn once, on the device"""
+        if isinstance(seed, bool) or not isinstance(seed, int):
+            raise ValueError(f"LinkSplit.with_negatives: seed must be an int, got {seed!r}")
+        keys = ops.edge_keys(self.edge_index, self.num_nodes)
+        out = LinkSplit(**{k: getattr(self, k) for k in self._FIELDS})
+        out.val_neg, out.val_neg_valid = ops.negative_sample(round(ratio * self.val_pos.size(1)), keys, self.num_nodes, seed + 1)
+        out.test_neg, out.test_neg_valid = ops.negative_sample(round(ratio * self.test_pos.size(1)), keys, self.num_nodes, seed + 2)
+        return out
+
+
+def random_link_split(edge_index: torch.Tensor, num_nodes: int, val_ratio: float = 0.05, test_ratio: float = 0.1,
+                      is_undirected: bool = True, generator: Optional[torch.Generator] = None) -> LinkSplit:
+    """torch_geometric's ``RandomLinkSplit`` restated in plain torch ops on ``edge_index``'s device (CPU tensors work too, as for
+    ``random_split_ids``).  With ``is_undirected`` only the ``u < v`` representative of every edge is split (the list is taken to
+    hold both directions; self loops take no part), else every edge is its own representative.  Of the ``E_rep`` representatives,
+    in the order of one ``torch.randperm(E_rep, generator=generator)`` drawn on the HOST (the same split on every device),
+    ``int(val_ratio * E_rep)`` become validation positives, ``int(test_ratio * E_rep)`` test positives and the rest, which come
+    first, training positives.  Message passing: training and validation see the training edges (both directions when
+    undirected), the test split sees training plus validation edges -- no pair a split is scored on, nor its reverse, is in the
+    graph that split's encoder sees before its turn."""
+    if edge_index.dim() != 2 or edge_index.size(0) != 2 or edge_index.dtype != torch.int64:
+        raise ValueError("edge_index must be an int64 tensor of shape [2, E]")
+    if not (0.0 <= val_ratio and 0.0 <= test_ratio and val_ratio + test_ratio < 1.0):
+        raise ValueError(f"random_link_split: ratios are >= 0 and sum to less than 1; got {val_ratio} and {test_ratio}")
+    rep = edge_index[:, edge_index[0] < edge_index[1]] if is_undirected else edge_index
+    e_rep = int(rep.size(1))
+    n_val, n_test = int(val_ratio * e_rep), int(test_ratio * e_rep)
+    n_train = e_rep - n_val - n_test
+    order = (torch.randperm(e_rep, generator=generator) if generator is not None else torch.randperm(e_rep)).to(edge_index.device)
+    train, val, test = (rep[:, ids].contiguous() for ids in torch.split(order, [n_train, n_val, n_test]))
+
+    def graph(pairs):
+        return torch.cat([pairs, pairs.flip(0)], dim=1).contiguous() if is_undirected else pairs
+    train_graph = graph(train)
+    return LinkSplit(edge_index=edge_index, num_nodes=int(num_nodes), is_undirected=bool(is_undirected), train_edge_index=train_graph,
+                     val_edge_index=train_graph, test_edge_index=graph(torch.cat([train, val], dim=1)), train_pos=train, val_pos=val,
+                     test_pos=test)

@@ -774,6 +774,128 @@ def train_node_classification_sampled(model, x, edge_index, y, train_mask, val_m
                                     best_epoch=st.best_epoch, stopped=st.stopped, history=st.history)
 
 
+class LinkPredictionResult:
+    """what ``train_link_prediction`` returns.  ``val_*``: the figures of the BEST epoch (the weights that were loaded back),
+    ``test_*``: those weights on the test split, evaluated once -- ``loss`` (mean BCE rounded once to fp32), ``acc`` (rows with
+    ``(score > 0) == label``), ``auc`` (ROC-AUC), ``hits`` (``{k: share of positives above the k-th negative}``); NaN where a
+    split is empty.  ``epochs_run`` / ``best_epoch`` / ``stopped`` as the device record counted them.  ``history``: the validation
+    ``ops.bce_with_logits`` records of the counted epochs, a CPU int64 ``[epochs_run, 1, 3]`` tensor (loss sum as the bits of a
+    double, correct, rows); ``rank_history``: their ``ops.link_rank`` records, CPU int64 ``[epochs_run, 8]``."""
+    __slots__ = ("val_loss", "val_acc", "val_auc", "val_hits", "test_loss", "test_acc", "test_auc", "test_hits", "epochs_run",
+                 "best_epoch", "stopped", "history", "rank_history")
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw[k])
+
+    def __repr__(self):
+        return "LinkPredictionResult(" + ", ".join(f"{k}={getattr(self, k)!r}" for k in self.__slots__[:-2]) + ")"
+
+
+def _link_figures(record: torch.Tensor, rank: torch.Tensor, ks):
+    """(loss, accuracy, auc, hits) of one BCE record ``[3]`` and one rank record ``[8]`` on the host"""
+    from . import ops as ops_mod
+    loss, acc = _split_figures(record)
+    fig = ops_mod.link_rank_figures(rank, ks)
+    return loss, acc, fig["auc"], fig["hits"]
+
+
+def train_link_prediction(model, x, split, epochs: int = 200, lr: float = 0.01, patience: int = 50, min_delta: float = 0.0,
+                          poll_every: int = 16, neg_ratio: float = 1.0, seed: int = 0, optimizer=None, ks=(20, 50, 100)):
+    """Link prediction by torch_geometric's standard recipe, device-resident like the other experiments here: ``model`` is a
+    ``kagnn_amd.LinkPredictor``, ``x`` the node features, ``split`` a ``data.LinkSplit`` (``random_link_split``; evaluation
+    negatives are attached with ``split.with_negatives(seed, neg_ratio)`` when it has none).  Per epoch ``e`` = 0, 1, ...:
+
+    1. training negatives: ``ops.negative_sample(round(neg_ratio * P_train), keys of the training graph, N, seed + 16 * (e + 1))``
+       -- THE SEED RULE; the evaluation negatives use ``seed + 1`` and ``seed + 2``, so no two draws share a seed for any number
+       of epochs -- with ``attempts = 8``;
+    2. one training step in train mode: ``z = model.encode(x, training graph)``, scores ``cat(decode(z, positives), decode(z,
+       negatives))``, labels 1 / 0, weights 1 for the positives and ``valid`` for the negatives (an EMPTY slot weighs nothing),
+       loss ``ops.bce_with_logits``, ``harness.Adam(lr)`` unless ``optimizer`` is given;
+    3. an eval-mode ``no_grad`` forward on the validation split's graph, its positives and fixed negatives scored in one list;
+    4. ``ops.bce_with_logits(accumulate=record)`` and ``ops.link_rank(out=rank_history[e])`` on those scores;
+    5. ``ops.EarlyStop.update(record, 0)`` on the validation loss;
+    6. ``ops.copy_if(improved, snapshot, live)`` over the ``state_dict``.
+
+    Nothing is read back between polls (every ``poll_every`` epochs, 32 bytes): the positives and the evaluation pairs are
+    indexed once, the negatives' pair index is built per epoch without synchronising as long as it has at most 65 536 pairs
+    (``ops.pair_scores``).  Epochs run after the stop change neither the snapshot nor the counted histories.  At the end the best
+    weights are loaded back, the test split is evaluated once on its own graph (training plus validation edges), and the model is
+    left in training mode.  Returns a ``LinkPredictionResult``."""
+    from . import ops as ops_mod
+    epochs, poll_every = int(epochs), max(1, int(poll_every))
+    if isinstance(seed, bool) or not isinstance(seed, int):
+        raise ValueError(f"train_link_prediction: seed must be an int, got {seed!r}")
+    ks = [int(k) for k in ks]
+    if len(ks) > ops_mod.LINK_RANK_MAX_KS or any(k < 1 for k in ks):
+        raise ValueError(f"train_link_prediction: ks holds at most {ops_mod.LINK_RANK_MAX_KS} values >= 1, got {ks}")
+    ops_mod._need_cuda(x, split.edge_index, split.train_edge_index, split.train_pos, *model.parameters())
+    if split.val_neg is None:
+        split = split.with_negatives(seed, neg_ratio)
+    n, dev = split.num_nodes, x.device
+    u8 = dict(dtype=torch.uint8, device=dev)
+    g_train = ops_mod.graph_index(split.train_edge_index, n)
+    g_val = g_train if split.val_edge_index is split.train_edge_index else ops_mod.graph_index(split.val_edge_index, n)
+    train_keys = g_train.edge_keys
+    p_train = int(split.train_pos.size(1))
+    num_neg = round(neg_ratio * p_train)
+    pos_index = ops_mod.GraphIndex(split.train_pos, n) if p_train else split.train_pos
+    y_train = torch.cat([torch.ones(p_train, **u8), torch.zeros(num_neg, **u8)])
+    w_pos = torch.ones(p_train, **u8)
+
+    def eval_set(pos, neg, neg_valid):
+        pairs = torch.cat([pos, neg], dim=1).contiguous()
+        index = ops_mod.GraphIndex(pairs, n) if pairs.size(1) else pairs
+        y = torch.cat([torch.ones(pos.size(1), **u8), torch.zeros(neg.size(1), **u8)])
+        return index, y, torch.cat([torch.ones(pos.size(1), **u8), neg_valid])
+    val_index, y_val, w_val = eval_set(split.val_pos, split.val_neg, split.val_neg_valid)
+    if optimizer is None:
+        optimizer = Adam(model.parameters(), lr=lr)
+    best = _BestWeights(model, "train_link_prediction")
+    stop = ops_mod.EarlyStop(patience, min_delta, max_epochs=epochs, num_splits=1, device=dev)
+    record = torch.zeros((1, 3), dtype=torch.int64, device=dev)
+    rank_history = torch.zeros((max(epochs, 1), 8), dtype=torch.int64, device=dev)
+    step = _training_step(optimizer)
+    epoch = 0
+
+    def train_loss(neg, valid):
+        z = model.encode(x, g_train)
+        scores = torch.cat([model.decode(z, pos_index), model.decode(z, neg)])
+        return ops_mod.bce_with_logits(scores, y_train, torch.cat([w_pos, valid]))
+
+    def one_epoch():
+        nonlocal epoch
+        neg, valid = ops_mod.negative_sample(num_neg, train_keys, n, seed + 16 * (epoch + 1))
+        model.train()
+        step(train_loss, neg, valid)
+        model.eval()
+        with torch.no_grad():
+            scores = model.decode(model.encode(x, g_val), val_index)
+        ops_mod.bce_with_logits(scores, y_val, w_val, accumulate=record)
+        ops_mod.link_rank(scores, y_val, w_val, ks, out=rank_history[epoch])
+        stop.update(record, 0)
+        epoch += 1
+
+    _run_until_stopped(one_epoch, epochs, poll_every, stop, best)
+    ops_mod.flush_graph_checks(dev)
+    st = stop.read()
+    ranks = rank_history[:st.epochs].cpu()
+    best.restore()
+    nan = float("nan")
+    val = _link_figures(st.history[st.best_epoch, 0], ranks[st.best_epoch], ks) if st.best_epoch >= 0 else (nan, nan, nan, {k: nan for k in ks})
+    test_index, y_test, w_test = eval_set(split.test_pos, split.test_neg, split.test_neg_valid)
+    model.eval()
+    with torch.no_grad():
+        scores = model.decode(model.encode(x, ops_mod.graph_index(split.test_edge_index, n)), test_index)
+    test_record = torch.zeros(3, dtype=torch.int64, device=dev)
+    ops_mod.bce_with_logits(scores, y_test, w_test, accumulate=test_record)
+    test = _link_figures(test_record.cpu(), ops_mod.link_rank(scores, y_test, w_test, ks).cpu(), ks)
+    model.train()
+    return LinkPredictionResult(val_loss=val[0], val_acc=val[1], val_auc=val[2], val_hits=val[3], test_loss=test[0], test_acc=test[1],
+                                test_auc=test[2], test_hits=test[3], epochs_run=st.epochs, best_epoch=st.best_epoch, stopped=st.stopped,
+                                history=st.history, rank_history=ranks)
+
+
 def node_classification_splits(params: dict, x, edge_index, y, train_masks, val_masks, test_masks, **train_kw):
     """``all_splits`` of the reference (``node_classification_clean/utils.py:195-211``): a fresh ``make_model(params)`` trained by
     ``train_node_classification`` for every row of the ``[splits, N]`` mask tensors, with ``epochs``, ``lr`` and ``patience`` taken

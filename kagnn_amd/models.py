@@ -394,3 +394,25 @@ class GFASTKAN_Nodes(_NodeModel):
 
         dim = self._build(conv_type, mp_layers, num_features, hidden_channels, skip, dropout, make_conv, heads)
         self.lay_out = FastKANLayer(dim, num_classes, num_grids=grid_size)
+
+
+class LinkPredictor(nn.Module):
+    """Link prediction around any node model of this package (``GKAN_Nodes``, ``GFASTKAN_Nodes``, ``GNN_Nodes``; any module whose
+    forward is ``model(x, edge_index)``): the encoder's ``[N, d]`` output is the node embedding ``z`` (``d`` = its ``num_classes``),
+    the decoder the dot product of torch_geometric's link-prediction recipe.  ``encode(x, g)`` -- ``g``: an int64 ``edge_index`` or
+    an ``ops.GraphIndex``, the MESSAGE-PASSING graph of the split at hand; ``decode(z, pairs)`` = ``ops.pair_scores``: fp32 logits
+    ``[P]`` for an int64 ``[2, P]`` tensor or a ``GraphIndex`` built over it; ``forward(x, g, pairs)`` chains the two.  Training and
+    evaluation: ``harness.train_link_prediction``."""
+
+    def __init__(self, encoder: nn.Module):
+        super().__init__()
+        self.encoder = encoder
+
+    def encode(self, x: torch.Tensor, edge_index) -> torch.Tensor:
+        return self.encoder(x, edge_index)
+
+    def decode(self, z: torch.Tensor, pairs) -> torch.Tensor:
+        return ops.pair_scores(z, pairs)
+
+    def forward(self, x: torch.Tensor, edge_index, pairs) -> torch.Tensor:
+        return self.decode(self.encode(x, edge_index), pairs)

@@ -261,6 +261,7 @@ class GraphIndex:
                 self.rowptr, self.col, self.perm, self.hub_seg, self.num_hub_seg = self._build(dst, src)
                 self.rowptr_t, self.col_t, self.perm_t, self.hub_seg_t, self.num_hub_seg_t = self._build(src, dst)
         self._dis = None
+        self._edge_list, self._edge_keys = (src, dst), None
         if not defer_validation:
             self.validate()             # (small path: waits for its flags -- graphs that are indexed once pay one synchronisation, as
                                         # the rocPRIM path does; the per-batch graphs of the graph-level models defer it)
@@ -297,6 +298,7 @@ class GraphIndex:
         g.num_hub_seg = g.num_hub_seg_t = 0
         g._flags = None
         g._dis = None
+        g._edge_list = g._edge_keys = None
         return g
 
     def validate(self, wait: bool = True) -> None:
@@ -330,6 +332,17 @@ class GraphIndex:
                       _ptr(dis), _stream())
             self._dis = dis
         return self._dis
+
+    @property
+    def edge_keys(self) -> torch.Tensor:
+        """the edge set as ascending, duplicate-free int64 keys ``src * num_nodes + dst`` (``kagnn_edge_keys_build``): what
+        ``negative_sample`` searches.  Built at the first use and kept -- one read of the key count then, none afterwards."""
+        if self._edge_keys is None:
+            if self._edge_list is None:
+                raise RuntimeError("GraphIndex.edge_keys: an index made from arrays (from_arrays, a subgraph's index) carries no edge "
+                                   "list; build the keys with ops.edge_keys(edge_index, num_nodes)")
+            self._edge_keys = _edge_keys_raw(self._edge_list[0], self._edge_list[1], self.num_nodes)
+        return self._edge_keys
 
     def side(self, transposed: bool):
         if transposed:
@@ -375,9 +388,10 @@ def _check_flags(entry, wait: bool) -> bool:
     if entry[3]:
         return True
     host, ev = entry[0], entry[1]
-    if not wait and not ev.query():
-        return False
-    ev.synchronize()
+    if not ev.query():                # (an event that has completed is not waited for: a loop that indexes a pair list per epoch never waits)
+        if not wait:
+            return False
+        ev.synchronize()
     entry[3] = True
     if (int(host[0]) or int(host[1])) if host.dim() == 1 else bool(host.any()):
         raise RuntimeError(entry[4])
@@ -3050,6 +3064,233 @@ def copy_if(flag: torch.Tensor, dsts, srcs) -> None:
         tables = _COPY_IF_TABLES[key] = ((ctypes.c_void_p * n)(*key[0]), (ctypes.c_void_p * n)(*key[1]), (ctypes.c_int64 * n)(*key[2]))
     with _device_of(flag):
         _call("kagnn_copy_if", _ptr(flag), len(dsts), *tables, _stream())
+
+
+# ======================================================================== link prediction: edge keys, negatives, pair scores, BCE, ranking
+def _edge_keys_raw(src, dst, num_nodes: int) -> torch.Tensor:
+    e, dev = int(src.numel()), src.device
+    keys = torch.empty(e, dtype=torch.int64, device=dev)
+    count = torch.empty(1, dtype=torch.int64, device=dev)
+    ws = _ws(_sizes("kagnn_edge_keys_workspace_bytes", e), dev)
+    with _device_of(src):
+        _call("kagnn_edge_keys_build", _ptr(src), _ptr(dst), e, int(num_nodes), _ptr(keys), _ptr(count), _ptr(ws), ws.numel(), _stream())
+        return keys[:int(count.item())] if e else keys
+
+
+def edge_keys(edge_index: torch.Tensor, num_nodes: int) -> torch.Tensor:
+    """The edge set of an int64 ``[2, E]`` device ``edge_index`` as ascending, duplicate-free int64 keys ``src * num_nodes + dst``
+    (``kagnn_edge_keys_build``: a rocPRIM radix sort and a unique pass) -- what ``negative_sample`` tests membership against.  One
+    read of the number of keys; ``GraphIndex.edge_keys`` keeps the result per graph."""
+    if edge_index.dim() != 2 or edge_index.size(0) != 2 or edge_index.dtype != torch.int64:
+        raise ValueError("edge_index must be an int64 tensor of shape [2, E]")
+    num_nodes = int(num_nodes)
+    if not 0 <= num_nodes < 1 << 31 or (edge_index.size(1) and not num_nodes):
+        raise ValueError(f"edge_keys: num_nodes must lie in [0, 2^31) and be positive when there are edges, got {num_nodes}")
+    _need_cuda(edge_index)
+    return _edge_keys_raw(edge_index[0].contiguous(), edge_index[1].contiguous(), num_nodes)
+
+
+def negative_sample(num: int, g_or_keys, num_nodes: int, seed: int = 0, attempts: int = 8):
+    """``num`` uniform negative pairs of a graph of ``num_nodes`` nodes (torch_geometric's ``negative_sampling``, dense-free) as a
+    FIXED-SIZE result, on the device, without compaction or read-back: ``(pairs, valid)`` = int64 ``[2, num]`` and uint8 ``[num]``.
+    ``g_or_keys``: a ``GraphIndex`` (its ``edge_keys``) or the int64 key vector of ``edge_keys``.  Slot ``p`` tries the attempts
+    ``t = 0 .. attempts - 1`` with the counter ``c = p * attempts + t``: ``u = (key32(seed, 2c) * N) >> 32``, ``v = (key32(seed,
+    2c + 1) * N) >> 32`` (``key32``: the sampler's, ``kagnn_hip.h``); an attempt is valid iff ``u != v`` and ``(u, v)`` is not an
+    edge; the slot takes its first valid attempt.  A slot without one is EMPTY: the pair ``(0, 0)`` with ``valid = 0`` -- give it
+    weight 0 (``bce_with_logits(weight_u8=valid)``).  The share of empty slots is ``(1 - free / N^2) ** attempts``, ``free`` the
+    number of ordered non-edge, non-self pairs.  A pure function of ``(seed, keys, N, attempts)``: two calls return the same bits.
+    ``seed``: any int, taken mod 2^64.  Refused before any launch: ``attempts`` outside 1..32, ``2 * num * attempts >= 2^32``,
+    ``num_nodes >= 2^31``."""
+    if isinstance(seed, bool) or not isinstance(seed, int):
+        raise ValueError(f"negative_sample: seed must be an int, got {seed!r}")
+    num, num_nodes, attempts = int(num), int(num_nodes), int(attempts)
+    if not 1 <= attempts <= _lib.NEGATIVE_MAX_ATTEMPTS:
+        raise ValueError(f"negative_sample: attempts must be 1..{_lib.NEGATIVE_MAX_ATTEMPTS}, got {attempts}")
+    if num < 0 or 2 * num * attempts >= 1 << 32:
+        raise ValueError(f"negative_sample: num >= 0 and 2 * num * attempts below 2^32; got num = {num}, attempts = {attempts}")
+    if not 0 <= num_nodes < 1 << 31:
+        raise ValueError(f"negative_sample: num_nodes must lie in [0, 2^31), got {num_nodes}")
+    if isinstance(g_or_keys, GraphIndex):
+        if g_or_keys.num_nodes != num_nodes:
+            raise ValueError(f"negative_sample: the index describes {g_or_keys.num_nodes} nodes, not {num_nodes}")
+        _need_cuda(g_or_keys.rowptr)
+        keys = g_or_keys.edge_keys
+    else:
+        keys = g_or_keys
+        if not isinstance(keys, torch.Tensor) or keys.dtype != torch.int64 or keys.dim() != 1:
+            raise TypeError("negative_sample: a GraphIndex or the int64 key vector of ops.edge_keys")
+        _need_cuda(keys)
+        keys = keys.contiguous()
+    dev = keys.device
+    if num_nodes == 0:
+        return torch.zeros((2, num), dtype=torch.int64, device=dev), torch.zeros(num, dtype=torch.uint8, device=dev)
+    pairs = torch.empty((2, num), dtype=torch.int64, device=dev)
+    valid = torch.empty(num, dtype=torch.uint8, device=dev)
+    with _device_of(keys):
+        _call("kagnn_negative_sample", _ptr(keys), keys.numel(), num_nodes, num, int(seed) & 0xFFFFFFFFFFFFFFFF, attempts, _ptr(pairs),
+              _ptr(valid), _stream())
+    return pairs, valid
+
+
+class _PairScoresFn(Function):
+    """s[p] = <z[u_p], z[v_p]> over a pair index (u = source, v = destination): ``kagnn_aggregate_edge_grad`` with x = gout = z; the
+    backward is the two weighted aggregations of the upstream gradient, one over each structure of the index"""
+
+    @staticmethod
+    @_on_operand_device
+    def forward(ctx, z, g):
+        rows = _rows(z)
+        ctx.g = g
+        ctx.save_for_backward(rows)
+        if g is None or g.num_edges == 0:                              # (no pair: nothing is indexed and nothing launched)
+            return torch.empty(0, dtype=torch.float32, device=z.device)
+        return _aggregate_edge_grad_csr(rows, rows, g.rowptr, g.col, g.perm, g.hub_seg if g.num_hub_seg else None, g.num_hub_seg,
+                                        g.hub_threshold, g.num_edges, None, None, False)
+
+    @staticmethod
+    @once_differentiable
+    @_on_operand_device
+    def backward(ctx, gs):
+        rows, = ctx.saved_tensors
+        g = ctx.g
+        if g is None or g.num_edges == 0:
+            return torch.zeros(rows.shape, dtype=torch.float32, device=rows.device), None
+        gs = gs.to(torch.float32)
+        # d s_p / d z[v_p] = z[u_p]: rows = destinations gather their sources;  d s_p / d z[u_p] = z[v_p]: the transposed structure
+        by_dst = _aggregate_csr(rows, g.rowptr, g.col, g.hub_seg, g.num_hub_seg, g.hub_threshold, 0.0, gs[g.perm.long()].contiguous(),
+                                None, None, None, False)
+        return _aggregate_csr(rows, g.rowptr_t, g.col_t, g.hub_seg_t, g.num_hub_seg_t, g.hub_threshold, 0.0,
+                              gs[g.perm_t.long()].contiguous(), None, None, None, False, addend=by_dst), None
+
+
+def pair_index(pairs: torch.Tensor, num_nodes: int) -> GraphIndex:
+    """the ``GraphIndex`` of a pair list for ``pair_scores``: int64 ``[2, P]``, ``u = pairs[0]`` the source, ``v = pairs[1]`` the
+    destination.  Never cached and validated later (``flush_graph_checks``): index a fixed list once and keep the result."""
+    return graph_index(pairs, num_nodes, cache=False)
+
+
+def pair_scores(z, pairs) -> torch.Tensor:
+    """The dot-product decoder of link prediction: ``s[p] = <z[u_p], z[v_p]>`` as fp32 ``[P]``, with autograd.  ``pairs``: an int64
+    ``[2, P]`` device tensor or an ``ops.GraphIndex`` built over it for ``z.size(0)`` nodes (``u`` = source, ``v`` = destination;
+    duplicate and self pairs are fine).
+    No kernel of its own.  The forward is ``kagnn_aggregate_edge_grad`` with ``x = gout = z`` on the pairs' by-destination
+    structure, which writes the products in the pairs' original order.  The backward is one ``kagnn_aggregate_sum`` over the
+    by-destination structure plus one ``kagnn_aggregate_sum_add`` over the by-source structure, both with ``self_scale = 0`` and the
+    upstream gradient as edge weights -- deterministic, no atomics.
+    What it costs: one CSR build per NEW pair list.  On the small-graph path (up to 65 536 pairs and nodes) the build is one
+    launch and does not synchronise; above it the rocPRIM path synchronises the stream ONCE per structure's build call.  So pass a
+    ``GraphIndex`` (``pair_index``) for the lists that stay fixed -- the positives, the evaluation negatives -- and a tensor only for
+    pairs drawn anew, such as each epoch's training negatives."""
+    if z.dim() != 2:
+        raise ValueError(f"pair_scores: z is [N, d], got shape {tuple(z.shape)}")
+    if isinstance(pairs, GraphIndex):
+        g = pairs
+        if g.num_nodes != z.size(0):
+            raise ValueError(f"pair_scores: the pair index describes {g.num_nodes} nodes, z has {z.size(0)} rows")
+        _need_cuda(z, g.rowptr)
+    else:
+        if not isinstance(pairs, torch.Tensor) or pairs.dim() != 2 or pairs.size(0) != 2 or pairs.dtype != torch.int64:
+            raise ValueError("pair_scores: pairs must be an int64 tensor of shape [2, P] or a GraphIndex")
+        _need_cuda(z, pairs)
+        with _device_of(z):
+            g = pair_index(pairs, z.size(0)) if pairs.size(1) else None
+    return _PairScoresFn.apply(z, g)
+
+
+def _bce_operands(what, scores, labels_u8, weight_u8):
+    if scores.dim() != 1 or scores.dtype != torch.float32:
+        raise TypeError(f"{what}: scores are an fp32 vector [P], got {scores.dtype} of shape {tuple(scores.shape)}")
+    for name, t in (("labels_u8", labels_u8), ("weight_u8", weight_u8)):
+        if t is None and name == "weight_u8":
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 1:
+            raise TypeError(f"{what}: {name} is a uint8 vector [P]")
+        if t.numel() != scores.numel():
+            raise ValueError(f"{what}: {name} has {t.numel()} entries for {scores.numel()} scores")
+    _need_cuda(scores, labels_u8, weight_u8)
+
+
+class _BceLogitsFn(Function):
+    @staticmethod
+    @_on_operand_device
+    def forward(ctx, scores, labels, weight, record):
+        s = scores.contiguous()
+        p, dev = s.numel(), s.device
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        divisor = torch.empty(1, dtype=torch.int64, device=dev)
+        ws = _ws(_lib.BCE_WORKSPACE_BYTES, dev) if p > 4096 else None
+        _call("kagnn_bce_logits_fwd", _ptr(s), _ptr(labels), _ptr(weight), p, _ptr(loss), _ptr(divisor), _ptr(record), _ptr(ws),
+              ws.numel() if ws is not None else 0, _stream())
+        ctx.save_for_backward(s, labels, divisor)
+        ctx.weight = weight
+        return loss[0]
+
+    @staticmethod
+    @once_differentiable
+    @_on_operand_device
+    def backward(ctx, gloss):
+        s, labels, divisor = ctx.saved_tensors
+        g = gloss.to(torch.float32).contiguous()
+        gs = torch.empty_like(s)
+        _call("kagnn_bce_logits_bwd", _ptr(s), _ptr(labels), _ptr(ctx.weight), s.numel(), _ptr(divisor), _ptr(g), _ptr(gs), _stream())
+        return gs, None, None, None
+
+
+def bce_with_logits(scores, labels_u8, weight_u8=None, accumulate: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``F.binary_cross_entropy_with_logits(scores, labels)`` over the rows of weight 1 (``weight_u8=None``: all rows) as one call
+    each way: the mean of ``max(s, 0) - s * y + log1p(exp(-|s|))``, the term in fp32, the sum in fp64 partials added in a fixed
+    order, divided by the number of such rows (at least 1: no row gives 0) and rounded once; the gradient is ``(sigmoid(s) - y) * w /
+    rows``.  ``scores`` fp32 ``[P]``; ``labels_u8`` / ``weight_u8`` uint8 ``[P]`` (non-zero = 1) -- ``negative_sample``'s ``valid``
+    is a weight.  ``accumulate``: a contiguous int64 device tensor of 3 elements (``[3]`` or ``[1, 3]``) that the same call
+    OVERWRITES with one record of ``node_eval``'s format -- the loss sum as the bits of a double, the rows with ``(s > 0) == y``,
+    the rows -- so that ``EarlyStop.update(record.view(1, 3), 0)`` and ``copy_if`` serve a link-prediction loop as they are.  A
+    NaN score makes the sum NaN; it counts like any other score."""
+    if accumulate is not None and (not isinstance(accumulate, torch.Tensor) or accumulate.dtype != torch.int64 or accumulate.numel() != 3
+                                   or not accumulate.is_contiguous()):
+        raise ValueError("bce_with_logits: accumulate is a contiguous int64 tensor of 3 elements (one node_eval record)")
+    _bce_operands("bce_with_logits", scores, labels_u8, weight_u8)
+    _need_cuda(scores, accumulate)
+    return _BceLogitsFn.apply(scores, labels_u8.contiguous(), None if weight_u8 is None else weight_u8.contiguous(), accumulate)
+
+
+LINK_RANK_MAX_KS = 3
+
+
+def link_rank(scores, labels_u8, weight_u8=None, ks=(20, 50, 100), out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The ranking figures of a scored pair set as an int64 ``[8]`` device record ``{2U, n_pos, n_neg, nan_rows, hits[ks[0]],
+    hits[ks[1]], hits[ks[2]], 0}`` (``kagnn_link_rank``; exact integers, no read-back): ``2U`` = over positives ``i`` and negatives
+    ``j``, 2 where ``s_i > s_j`` and 1 where ``s_i == s_j``, so ROC-AUC is ``2U / (2 * n_pos * n_neg)`` (``link_rank_figures``);
+    ``hits[k]`` = the positives strictly above the ``k``-th largest negative score, all of them when there are fewer than ``k``
+    negatives.  Rows of weight 0 and rows with a NaN score take no part (the latter are counted in ``nan_rows``); ``-0.0`` and
+    ``+0.0`` tie, ``+-Inf`` are ordinary values.  ``ks``: up to 3 integers >= 1.  ``out``: a contiguous int64 ``[8]`` device tensor
+    to overwrite (a row of a history)."""
+    ks = [int(k) for k in ks]
+    if len(ks) > LINK_RANK_MAX_KS or any(k < 1 or k >= 1 << 31 for k in ks):
+        raise ValueError(f"link_rank: ks holds at most {LINK_RANK_MAX_KS} values, each in [1, 2^31); got {ks}")
+    _bce_operands("link_rank", scores, labels_u8, weight_u8)
+    s = scores.detach().contiguous()
+    p, dev = s.numel(), s.device
+    if out is None:
+        out = torch.empty(8, dtype=torch.int64, device=dev)
+    elif out.dtype != torch.int64 or out.shape != (8,) or not out.is_contiguous() or out.device != dev:
+        raise ValueError("link_rank: out must be a contiguous int64 [8] tensor on the scores' device")
+    nbytes = _sizes("kagnn_link_rank_workspace_bytes", p)
+    ws = _ws(nbytes, dev)
+    ks_host = (ctypes.c_int32 * max(len(ks), 1))(*ks)
+    with _device_of(s):
+        _call("kagnn_link_rank", _ptr(s), _ptr(labels_u8.contiguous()), None if weight_u8 is None else _ptr(weight_u8.contiguous()), p,
+              ks_host, len(ks), _ptr(out), _ptr(ws), nbytes, _stream())
+    return out
+
+
+def link_rank_figures(record, ks=(20, 50, 100)) -> dict:
+    """a ``link_rank`` record (any device; read here) as numbers: ``auc`` (NaN without a positive or a negative), ``hits`` -- the
+    share of positives above the ``k``-th negative, per ``k`` -- and the four counts"""
+    r = [int(v) for v in record.reshape(-1).tolist()]
+    u2, n_pos, n_neg = r[0], r[1], r[2]
+    auc = u2 / (2 * n_pos * n_neg) if n_pos and n_neg else float("nan")
+    hits = {int(k): (r[4 + j] / n_pos if n_pos else float("nan")) for j, k in enumerate(ks)}
+    return {"auc": auc, "hits": hits, "two_u": u2, "n_pos": n_pos, "n_neg": n_neg, "nan_rows": r[3]}
 
 
 # ======================================================================== GAT attention aggregation
