@@ -55,7 +55,7 @@ extern "C" {
 #define KAGNN_DTYPE_F32 0
 #define KAGNN_DTYPE_BF16 1
 
-int kagnn_version(void);          /* 278 = 277 + kagnn_edge_keys_build (+ _workspace_bytes), kagnn_negative_sample, kagnn_bce_logits_fwd / _bwd, kagnn_link_rank (+ _workspace_bytes); 277 = 276 + kagnn_neighbor_sample_mark, kagnn_edge_subgraph_count, kagnn_edge_subgraph_fill; 276 = 275 + kagnn_k_hop_mark, kagnn_subgraph_count, kagnn_subgraph_fill (+ kagnn_subgraph_workspace_bytes); 273 = 272 with kagnn_kan_grid_refit on kagnn_kan_grid_resize's kernels (up to 46 coefficients; its bits and its workspace size change); 272 = 271 + kagnn_kan_grid_resize (+ _workspace_bytes); 271 = 270 + kagnn_attention_fwd, kagnn_attention_bwd (+ _workspace_bytes); 270 = 269 + kagnn_fastkan_edge_abs_sum, kagnn_fastkan_edge_abs_sum_bwd (+ _workspace_bytes), kagnn_fastkan_edge_curves; 269 = 268 + kagnn_kan_edge_abs_sum, kagnn_kan_edge_abs_sum_bwd (+ _workspace_bytes), kagnn_kan_edge_curves; 268 = 267 + spline orders 5..KAGNN_MAX_SPLINE_ORDER in the per-operation KANLinear calls (no new entry point); 267 = 266 + kagnn_linear_fwd, kagnn_linear_bwd_input, kagnn_linear_bwd_weight (+ _workspace_bytes); 266 = 265 + kagnn_l1_loss_meter_fwd, kagnn_regression_epoch_update; 265 = 264 + kagnn_node_eval, kagnn_early_stop_update, kagnn_copy_if; 264 = 263 + kagnn_degree_one_hot, kagnn_nll_loss_fwd / _bwd; 263 = 262 + kagnn_batch_assemble; 262 = 261 - the fields edge_src, edge_dst, csr_flags of kagnn_kagin_model_t; 261 = 260 + kagnn_fastkan_fwd_stats_in_kernel; 260 = round 6: + the feature-sharded FastKAN entry points kagnn_fastkan_row_moments .. _shard_bwd_finish, + kagnn_kagin_model_*; 250 = 240 + KAGNN_PREC_HALF; 240 = 230 + kagnn_gin_kan_layer_bwd_bn_sums; 230 = 220 + the *_affine entry points of a folded BatchNorm1d; 220 = 210 + the stage timer) */
+int kagnn_version(void);          /* 279 = 278 + kagnn_symbolic_fit (+ _workspace_bytes); 278 = 277 + kagnn_edge_keys_build (+ _workspace_bytes), kagnn_negative_sample, kagnn_bce_logits_fwd / _bwd, kagnn_link_rank (+ _workspace_bytes); 277 = 276 + kagnn_neighbor_sample_mark, kagnn_edge_subgraph_count, kagnn_edge_subgraph_fill; 276 = 275 + kagnn_k_hop_mark, kagnn_subgraph_count, kagnn_subgraph_fill (+ kagnn_subgraph_workspace_bytes); 273 = 272 with kagnn_kan_grid_refit on kagnn_kan_grid_resize's kernels (up to 46 coefficients; its bits and its workspace size change); 272 = 271 + kagnn_kan_grid_resize (+ _workspace_bytes); 271 = 270 + kagnn_attention_fwd, kagnn_attention_bwd (+ _workspace_bytes); 270 = 269 + kagnn_fastkan_edge_abs_sum, kagnn_fastkan_edge_abs_sum_bwd (+ _workspace_bytes), kagnn_fastkan_edge_curves; 269 = 268 + kagnn_kan_edge_abs_sum, kagnn_kan_edge_abs_sum_bwd (+ _workspace_bytes), kagnn_kan_edge_curves; 268 = 267 + spline orders 5..KAGNN_MAX_SPLINE_ORDER in the per-operation KANLinear calls (no new entry point); 267 = 266 + kagnn_linear_fwd, kagnn_linear_bwd_input, kagnn_linear_bwd_weight (+ _workspace_bytes); 266 = 265 + kagnn_l1_loss_meter_fwd, kagnn_regression_epoch_update; 265 = 264 + kagnn_node_eval, kagnn_early_stop_update, kagnn_copy_if; 264 = 263 + kagnn_degree_one_hot, kagnn_nll_loss_fwd / _bwd; 263 = 262 + kagnn_batch_assemble; 262 = 261 - the fields edge_src, edge_dst, csr_flags of kagnn_kagin_model_t; 261 = 260 + kagnn_fastkan_fwd_stats_in_kernel; 260 = round 6: + the feature-sharded FastKAN entry points kagnn_fastkan_row_moments .. _shard_bwd_finish, + kagnn_kagin_model_*; 250 = 240 + KAGNN_PREC_HALF; 240 = 230 + kagnn_gin_kan_layer_bwd_bn_sums; 230 = 220 + the *_affine entry points of a folded BatchNorm1d; 220 = 210 + the stage timer) */
 const char* kagnn_last_error(void);
 
 /* Stage timer -- a measurement aid, off by default (no reference counterpart: the reference times whole epochs with
@@ -1261,6 +1261,40 @@ typedef struct kagnn_batch_assemble {
 } kagnn_batch_assemble_t;
 int kagnn_batch_assemble_struct_bytes(void);                          /* sizeof(kagnn_batch_assemble_t): a binding checks its mirror */
 int kagnn_batch_assemble(const kagnn_batch_assemble_t* a, void* stream);
+
+/* Symbolic fits of edge functions (symbolic.hip; pykan's suggest_symbolic / fit_params, all edges of a layer at once).
+ * x [num_rows, in] (row stride ldx), phi [num_rows, out, in] contiguous: the layer's edge functions at those rows, what
+ * kagnn_kan_edge_curves / kagnn_fastkan_edge_curves write for t = x.  For every function f of `functions` (HOST int32 ids of
+ * the library below), output o and input i the model is  phi_{o,i}(t) ~ c f(a t + b) + d:
+ *   params[f, o, i] = (a, b, c, d)     r2[f, o, i]          (f: position in `functions`)
+ * Library, argument t in fp32:  0 t   1 t^2   2 t^3   3 t^4   4 1/t   5 1/t^2   6 sqrt(t)   7 1/sqrt(t)   8 exp(t)   9 log(t)
+ *   10 |t|   11 sin(t)   12 cos(t)   13 tan(t)   14 tanh(t)   15 sign(t)   16 arctan(t)   17 exp(-t^2)   18 t / (1 + exp(-t)).
+ * No singularity protection: a value outside a function's domain is non-finite and falls under the rule.
+ * Score of a candidate (a, b) for edge (o, i):  t_n = fmaf(a, x[n,i], b) in fp32, u_n = f(t_n), y_n = phi[n,o,i]; with the
+ * means and the centred sums S_uu, S_yy, S_uy:  r2 = S_uy^2 / (S_uu S_yy),  and 0 when the candidate is degenerate: some u_n or
+ * one of the sums non-finite, or S_uu / N <= max(1e-5 mean(u^2), 1e-24) (a constant or saturated u, a = 0).  The same
+ * threshold on y makes every score of the edge 0.  A non-finite x[n,i] or phi[n,o,i] zeroes the scores of exactly the edges
+ * that read it and sets their c, d to NaN; every other edge is bit-equal to a clean run.
+ * Search: each axis has Gn = grid_number candidates  v_k = (float)((double)lo + k * ((double)hi - (double)lo) / (Gn - 1));  the
+ * best candidate has the largest r2, ties go to the lowest flat index a_id * Gn + b_id.  The zoom is per axis: an interior
+ * winner k gives the next range [v_{k-1}, v_{k+1}], k = 0 gives [v_0, v_1], k = Gn - 1 gives [v_{Gn-2}, v_{Gn-1}] (pykan leaves
+ * the other axis untouched when one hits the boundary; this does not).  Iteration 1 uses the caller's ranges, later ones
+ * per-edge ranges.  (a, b) is the last iteration's winner, c = S_uy / S_uu, d = ybar - c ubar there, r2 its score; if every
+ * candidate scored 0: candidate 0, r2 = 0, c = 0, d = ybar.  Deterministic, no atomics.
+ * tables / ranges / winners (each may be NULL): every iteration's score table [iterations, F, out, in, Gn, Gn], ranges
+ * (a_lo, a_hi, b_lo, b_hi) [iterations, F, out, in, 4] and winning flat index int32 [iterations, F, out, in], written by the
+ * same kernels.  Limits: grid_number 3..KAGNN_SYMBOLIC_MAX_GRID, iterations 1..KAGNN_SYMBOLIC_MAX_ITERATIONS, in, out >= 1,
+ * in <= 65535; num_rows = 1 makes everything degenerate; num_rows = 0 zero-fills params, r2 and whichever of tables / ranges / winners is given, without a launch.  Nothing
+ * beyond `workspace_bytes` of the query is used (the query needs no GPU); nothing of size num_rows x Gn^2 exists. */
+#define KAGNN_SYMBOLIC_NUM_FUNCTIONS 19
+#define KAGNN_SYMBOLIC_MAX_GRID 128
+#define KAGNN_SYMBOLIC_MAX_ITERATIONS 8
+int kagnn_symbolic_fit_workspace_bytes(int64_t num_rows, int32_t in_features, int32_t out_features, int32_t num_functions,
+                                       size_t* bytes_host);
+int kagnn_symbolic_fit(const float* x, int64_t ldx, const float* phi, int64_t num_rows, int32_t in_features, int32_t out_features,
+                       const int32_t* functions_host, int32_t num_functions, float a_lo, float a_hi, float b_lo, float b_hi,
+                       int32_t grid_number, int32_t iterations, float* params, float* r2, float* tables, float* ranges,
+                       int32_t* winners, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -59,6 +59,10 @@ _SIGNATURES = {
     "kagnn_link_rank_workspace_bytes": (c_int32, [c_int64, POINTER(c_size_t)]),
     # scores labels weight P ks(host int32) num_ks record ws bytes stream
     "kagnn_link_rank": (c_int32, [_P, _P, _P, c_int64, POINTER(c_int32), c_int32, _P, _P, c_size_t, _P]),
+    "kagnn_symbolic_fit_workspace_bytes": (c_int32, [c_int64, c_int32, c_int32, c_int32, POINTER(c_size_t)]),
+    # x ldx phi N in out functions(host int32) F a_lo a_hi b_lo b_hi grid_number iterations params r2 tables ranges winners ws bytes stream
+    "kagnn_symbolic_fit": (c_int32, [_P, c_int64, _P, c_int64, c_int32, c_int32, POINTER(c_int32), c_int32, c_float, c_float, c_float,
+                                     c_float, c_int32, c_int32, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
     "kagnn_gcn_deg_inv_sqrt": (c_int32, [_P, _P, c_int64, _P, _P]),
     "kagnn_aggregate_workspace_bytes": (c_int32, [c_int64, c_int32, POINTER(c_size_t)]),
     "kagnn_aggregate_sum": (c_int32, [_P, c_int64, _P, c_int64, _P, _P, _P, c_int64, c_int32, c_float,
@@ -283,6 +287,7 @@ REGRESSION_MAX_TARGETS = 32  # KAGNN_REGRESSION_MAX_TARGETS
 SAMPLE_MAX_LEVELS = 16       # KAGNN_SAMPLE_MAX_LEVELS
 NEGATIVE_MAX_ATTEMPTS = 32   # KAGNN_NEGATIVE_MAX_ATTEMPTS
 BCE_WORKSPACE_BYTES = 6144   # KAGNN_BCE_WORKSPACE_BYTES
+SYMBOLIC_NUM_FUNCTIONS, SYMBOLIC_MAX_GRID, SYMBOLIC_MAX_ITERATIONS = 19, 128, 8      # KAGNN_SYMBOLIC_*
 
 
 class BatchAssemble(ctypes.Structure):

@@ -84,7 +84,7 @@ using namespace kagnn;
 #pragma GCC visibility push(default)
 extern "C" {
 
-int kagnn_version(void) { return 278; }
+int kagnn_version(void) { return 279; }
 const char* kagnn_last_error(void) { return g_err; }
 
 int kagnn_stage_timer_enable(const char* only) {
@@ -1416,6 +1416,54 @@ int kagnn_kan_edge_curves(const float* t, int64_t ldt, int64_t P, const float* k
     if (P == 0) return KAGNN_OK;
     KAGNN_CHECK_ARG(t && knots && sw && phi, "null array");
     return kan_edge_curves(t, ldt, P, knots, per_feature_knots != 0, in, out, G, K, bw, sw, sc, phi, as_stream(stream));
+}
+
+// ---------------------------------------------------------------- symbolic fits of edge functions (symbolic.hip)
+static int check_symbolic_dims(const char* fn, int64_t N, int32_t in, int32_t out, int32_t F) {
+    KAGNN_CHECK_ARG_AS(fn, N >= 0 && N < 2147483647LL, "num_rows outside [0, 2^31 - 1)");
+    KAGNN_CHECK_ARG_AS(fn, in >= 1 && out >= 1 && in <= 65535, "in_features must be 1..65535, out_features >= 1");
+    KAGNN_CHECK_ARG_AS(fn, F >= 1 && F <= KAGNN_SYMBOLIC_NUM_FUNCTIONS, "num_functions must be 1..19");
+    return KAGNN_OK;
+}
+
+int kagnn_symbolic_fit_workspace_bytes(int64_t N, int32_t in, int32_t out, int32_t F, size_t* bytes) {
+    KAGNN_CHECK_ARG(bytes != nullptr, "null output");
+    int rc = check_symbolic_dims(__func__, N, in, out, F);
+    if (rc) return rc;
+    *bytes = symbolic_ws_bytes(N, in, out, F);
+    return KAGNN_OK;
+}
+
+int kagnn_symbolic_fit(const float* x, int64_t ldx, const float* phi, int64_t N, int32_t in, int32_t out, const int32_t* functions,
+                       int32_t F, float a_lo, float a_hi, float b_lo, float b_hi, int32_t grid_number, int32_t iterations,
+                       float* params, float* r2, float* tables, float* ranges, int32_t* winners, void* ws, size_t ws_bytes,
+                       void* stream) {
+    KAGNN_STAGE(stream);
+    int rc = check_symbolic_dims(__func__, N, in, out, F);
+    if (rc) return rc;
+    KAGNN_CHECK_ARG(functions != nullptr, "functions is null (a host array of library ids)");
+    for (int f = 0; f < F; ++f) {
+        KAGNN_CHECK_ARG(functions[f] >= 0 && functions[f] < KAGNN_SYMBOLIC_NUM_FUNCTIONS, "unknown function id (the library has ids 0..18)");
+        for (int g = 0; g < f; ++g) KAGNN_CHECK_ARG(functions[g] != functions[f], "a function id is listed twice");
+    }
+    KAGNN_CHECK_ARG(grid_number >= 3 && grid_number <= KAGNN_SYMBOLIC_MAX_GRID, "grid_number must be 3..128");
+    KAGNN_CHECK_ARG(iterations >= 1 && iterations <= KAGNN_SYMBOLIC_MAX_ITERATIONS, "iterations must be 1..8");
+    KAGNN_CHECK_ARG(a_lo - a_lo == 0.0f && a_hi - a_hi == 0.0f && b_lo - b_lo == 0.0f && b_hi - b_hi == 0.0f, "a non-finite range");
+    KAGNN_CHECK_ARG(ldx >= in, "ldx smaller than in_features");
+    KAGNN_CHECK_ARG(params && r2, "null output");
+    if (N == 0) {                                            // nothing to fit: zeros, no launch
+        const size_t ne = (size_t)F * out * in;
+        KAGNN_HIP(hipMemsetAsync(params, 0, ne * 4 * sizeof(float), as_stream(stream)));
+        KAGNN_HIP(hipMemsetAsync(r2, 0, ne * sizeof(float), as_stream(stream)));
+        const size_t per_it = ne * (size_t)iterations;
+        if (tables) KAGNN_HIP(hipMemsetAsync(tables, 0, per_it * grid_number * grid_number * sizeof(float), as_stream(stream)));
+        if (ranges) KAGNN_HIP(hipMemsetAsync(ranges, 0, per_it * 4 * sizeof(float), as_stream(stream)));
+        if (winners) KAGNN_HIP(hipMemsetAsync(winners, 0, per_it * sizeof(int32_t), as_stream(stream)));
+        return KAGNN_OK;
+    }
+    KAGNN_CHECK_ARG(x && phi && ws, "null array");
+    return symbolic_fit(x, ldx, phi, N, in, out, functions, F, a_lo, a_hi, b_lo, b_hi, grid_number, iterations, params, r2, tables,
+                        ranges, winners, ws, ws_bytes, as_stream(stream));
 }
 
 // ---------------------------------------------------------------- direct peer-to-peer exchange (p2p.hip)

@@ -241,6 +241,12 @@ int fastkan_edge_abs_sum_bwd(const float* x, long ldx, long N, int in, int out, 
 int fastkan_edge_curves(const float* t, long ldt, const float* tb, long ldtb, long P, int in, int out, int ng, const float* centers,
                         float den, const float* sw, const float* bw, float* phi, hipStream_t st);
 
+// ---- symbolic.hip
+size_t symbolic_ws_bytes(long N, int in, int out, int F);
+int symbolic_fit(const float* x, long ldx, const float* phi, long N, int in, int out, const int* functions, int F, float alo,
+                 float ahi, float blo, float bhi, int Gn, int iterations, float* params, float* r2, float* tables, float* ranges,
+                 int* winners, void* ws, size_t ws_bytes, hipStream_t st);
+
 // ---- gat.hip
 int gat_logits(const float* xh, long ld, long N, int H, int C, const float* att_src, const float* att_dst, float* a_s, float* a_d,
                hipStream_t st);

@@ -308,6 +308,15 @@ class KANLinear(nn.Module):
         reference's ``plot_curve`` (``fastkan.py``) for all edges at once."""
         return ops.kan_edge_curves(points, *self._edge_args())
 
+    def suggest_symbolic(self, x: torch.Tensor, functions=None, topk: int = 3, max_rows: int = 4096, **search):
+        """Which elementary function is every edge ``phi_{o,i}``: a ``SymbolicSuggestion`` (``kagnn_amd/symbolic.py``) with the
+        ``topk`` best ``c f(a x + b) + d`` per edge, ranked by ``r2`` (ties: the lower library id), for the ``functions`` of
+        ``SYMBOLIC_LIB`` (default: all 19).  ``x [N, in]`` is the layer's own input; of more than ``max_rows`` rows the evenly strided
+        subset ``x[::ceil(N / max_rows)]`` is used.  ``edge_curves`` on those rows, then ``ops.symbolic_fit`` (``**search``:
+        ``a_range``, ``b_range``, ``grid_number``, ``iterations``).  Spline orders 1..4.  Nothing of the layer changes."""
+        from .symbolic import suggest_kanlinear
+        return suggest_kanlinear(self, x, functions, topk, max_rows, **search)
+
     def regularization_loss(self, regularize_activation=1.0, regularize_entropy=1.0, x: Optional[torch.Tensor] = None):
         """``x=None``: efficient-KAN's stand-in on ``|spline_weight|`` (``ekan.py:213-233``).  With the layer's input ``x``: the
         KAN paper's L1 + entropy regulariser on the edge activations, ``mag = edge_l1(x)`` in the same formula."""
@@ -386,12 +395,21 @@ class KAN(nn.Module):
                 x = layer._forward(x)
         return out
 
+    def suggest_symbolic(self, x: torch.Tensor, **kw) -> list:
+        """``KANLinear.suggest_symbolic`` of every layer on its own input, ``x`` being the chain's"""
+        from .symbolic import suggest_chain
+        return suggest_chain(self, x, **kw)
+
 
 def _collect(layer: KANLinear, x: torch.Tensor) -> None:
-    for names, stats in ops._edge_collectors():
-        name = names.get(id(layer))
-        if name is not None:
-            stats[name] = layer.edge_l1(x if x.dtype == torch.float32 else x.float())
+    for entry in ops._edge_collectors():
+        name = entry[0].get(id(layer))
+        if name is None:
+            continue
+        if len(entry) > 2:
+            entry[2](name, layer, x)              # a kagnn_amd.suggest_symbolic walk: it wants the input, not the statistics
+        else:
+            entry[1][name] = layer.edge_l1(x if x.dtype == torch.float32 else x.float())
 
 
 @contextlib.contextmanager

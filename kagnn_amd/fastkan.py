@@ -120,6 +120,14 @@ class FastKANLayer(nn.Module):
         sw, bw = self._edge_weights()
         return ops.fastkan_edge_curves(points, sw, bw, self.rbf.grid, self.rbf.denominator, base_points)
 
+    def suggest_symbolic(self, x: torch.Tensor, functions=None, topk: int = 3, max_rows: int = 4096, use_layernorm: bool = True,
+                         **search):
+        """``KANLinear.suggest_symbolic`` for this layer, on ``edge_curves``.  With a LayerNorm the FIT VARIABLE is the normalised
+        input ``u = layernorm(x)``, as in ``edge_curves``: ``phi_{o,i} ~ c f(a u_i + b) + d``, the base branch evaluated at the row
+        before the norm.  ``SymbolicSuggestion.x`` holds ``u``."""
+        from .symbolic import suggest_fastkan
+        return suggest_fastkan(self, x, functions, topk, max_rows, use_layernorm, **search)
+
     @torch.no_grad()
     def plot_curve(self, input_index: int, output_index: int, num_pts: int = 1000, num_extrapolate_bins: int = 2):
         """The reference's ``plot_curve`` (fastkan.py:87-115): ``(x, y)`` with ``x = linspace(grid_min - N_e h, grid_max + N_e h,
@@ -179,6 +187,11 @@ class FastKAN(nn.Module):
                 x = layer._forward(x)
         return out
 
+    def suggest_symbolic(self, x: torch.Tensor, **kw) -> list:
+        """``FastKANLayer.suggest_symbolic`` of every layer on its own input, ``x`` being the chain's"""
+        from .symbolic import suggest_chain
+        return suggest_chain(self, x, **kw)
+
 
 class AttentionWithFastKANTransform(nn.Module):
     """Multi-head attention whose five linear maps are ``FastKANLayer``s and whose additive ``bias`` enters AFTER the softmax
@@ -216,7 +229,11 @@ class AttentionWithFastKANTransform(nn.Module):
 
 def _collect(layer: FastKANLayer, x: torch.Tensor, use_layernorm: bool) -> None:
     """inside ``kagnn_amd.collect_edge_l1`` blocks of this thread: ``edge_l1`` of the input ``forward`` sees, with its ``use_layernorm``"""
-    for names, stats in ops._edge_collectors():
-        name = names.get(id(layer))
-        if name is not None:
-            stats[name] = layer.edge_l1(x if x.dtype == torch.float32 else x.float(), use_layernorm)
+    for entry in ops._edge_collectors():
+        name = entry[0].get(id(layer))
+        if name is None:
+            continue
+        if len(entry) > 2:
+            entry[2](name, layer, x, use_layernorm)       # a kagnn_amd.suggest_symbolic walk: it wants the input, not the statistics
+        else:
+            entry[1][name] = layer.edge_l1(x if x.dtype == torch.float32 else x.float(), use_layernorm)

@@ -10,6 +10,7 @@ from __future__ import annotations
 import ctypes
 import functools
 import inspect
+import math
 import os
 import threading
 import weakref
@@ -3507,3 +3508,75 @@ def fastkan_layer(x, ln_weight, ln_bias, spline_weight, base_weight, base_bias, 
                                      float(denominator), float(ln_eps), int(mode))[0]
     return _FastKANFn.apply(x, ln_weight, ln_bias, spline_weight, base_weight, base_bias, centers,
                             float(denominator), float(ln_eps), int(mode))
+
+
+# ======================================================================== symbolic fits of edge functions (csrc/symbolic.hip)
+# the fixed library of kagnn_symbolic_fit, in id order (include/kagnn_hip.h)
+SYMBOLIC_FUNCTIONS = ("x", "x^2", "x^3", "x^4", "1/x", "1/x^2", "sqrt", "1/sqrt(x)", "exp", "log", "abs", "sin", "cos", "tan", "tanh",
+                      "sgn", "arctan", "gaussian", "silu")
+
+
+class SymbolicFit(NamedTuple):
+    """what ``symbolic_fit`` returns.  ``functions``: the fitted names, the order of dimension 0 of ``params [F, out, in, 4]``
+    (``a, b, c, d`` of ``phi ~ c f(a x + b) + d``) and ``r2 [F, out, in]``.  With ``tables=True`` also every iteration's score
+    table ``[iterations, F, out, in, Gn, Gn]``, ranges ``[iterations, F, out, in, 4]`` (``a_lo, a_hi, b_lo, b_hi``) and winning
+    flat index ``a_id * Gn + b_id``, int32 ``[iterations, F, out, in]``; else ``None``."""
+    functions: Tuple[str, ...]
+    params: torch.Tensor
+    r2: torch.Tensor
+    tables: Optional[torch.Tensor] = None
+    ranges: Optional[torch.Tensor] = None
+    winners: Optional[torch.Tensor] = None
+
+
+def symbolic_fit(x, phi, functions=None, a_range=(-10, 10), b_range=(-10, 10), grid_number: int = 101, iterations: int = 3,
+                 tables: bool = False) -> SymbolicFit:
+    """For every edge function ``phi[:, o, i]`` sampled on the rows ``x[:, i]`` and every function ``f`` of ``functions`` (names of
+    ``SYMBOLIC_FUNCTIONS``; default: all), the best ``c f(a x + b) + d`` and its ``R^2`` -- pykan's ``suggest_symbolic`` /
+    ``fit_params`` for all edges of a layer at once, on the device.  ``x [N, in]`` fp32 (a row stride is allowed), ``phi [N, out, in]``
+    fp32 contiguous: what ``kan_edge_curves(x, ...)`` / ``fastkan_edge_curves(x, ...)`` return.  The search is a ``grid_number`` x
+    ``grid_number`` grid over ``(a, b)`` on ``a_range`` x ``b_range``, zoomed ``iterations - 1`` times around the winner, per axis;
+    the rule (scores, degenerate candidates, ties, zoom) is stated at ``kagnn_symbolic_fit`` in include/kagnn_hip.h.  Deterministic.
+    ``tables=True`` (tests, debugging, small shapes) also returns every iteration's score table, ranges and winner.
+    Not differentiable."""
+    names = tuple(SYMBOLIC_FUNCTIONS if functions is None else functions)
+    if not names:
+        raise ValueError("symbolic_fit: no functions given")
+    for nm in names:
+        if nm not in SYMBOLIC_FUNCTIONS:
+            raise ValueError(f"symbolic_fit: unknown function {nm!r}; the library is {', '.join(SYMBOLIC_FUNCTIONS)}")
+    if len(set(names)) != len(names):
+        raise ValueError("symbolic_fit: a function is listed twice")
+    gn, its = int(grid_number), int(iterations)
+    if not 3 <= gn <= _lib.SYMBOLIC_MAX_GRID:
+        raise ValueError(f"symbolic_fit: grid_number must be 3..{_lib.SYMBOLIC_MAX_GRID} (got {grid_number})")
+    if not 1 <= its <= _lib.SYMBOLIC_MAX_ITERATIONS:
+        raise ValueError(f"symbolic_fit: iterations must be 1..{_lib.SYMBOLIC_MAX_ITERATIONS} (got {iterations})")
+    if x.dtype != torch.float32 or phi.dtype != torch.float32:
+        raise TypeError(f"kagnn_amd kernels are fp32; got {x.dtype} and {phi.dtype}")
+    if x.dim() != 2 or phi.dim() != 3 or phi.size(0) != x.size(0) or phi.size(2) != x.size(1) or x.size(1) < 1 or phi.size(1) < 1:
+        raise ValueError(f"symbolic_fit: x must be [N, in] and phi [N, out, in]; got {tuple(x.shape)} and {tuple(phi.shape)}")
+    if not phi.is_contiguous():
+        raise ValueError("symbolic_fit: phi must be contiguous [N, out, in] (what edge_curves returns)")
+    ranges_host = [float(a_range[0]), float(a_range[1]), float(b_range[0]), float(b_range[1])]
+    if not all(math.isfinite(v) for v in ranges_host):
+        raise ValueError("symbolic_fit: a_range and b_range must be finite")
+    _need_cuda(x, phi)
+    x, phi = _rows(x.detach()), phi.detach()
+    n, fout, fin = phi.shape
+    f, dev = len(names), x.device
+    ids = (ctypes.c_int32 * f)(*[SYMBOLIC_FUNCTIONS.index(nm) for nm in names])
+    params = torch.empty((f, fout, fin, 4), dtype=torch.float32, device=dev)
+    r2 = torch.empty((f, fout, fin), dtype=torch.float32, device=dev)
+    tab = rng = win = None
+    if tables:
+        tab = torch.zeros((its, f, fout, fin, gn, gn), dtype=torch.float32, device=dev)
+        rng = torch.zeros((its, f, fout, fin, 4), dtype=torch.float32, device=dev)
+        win = torch.zeros((its, f, fout, fin), dtype=torch.int32, device=dev)
+    if n == 0:                           # nothing to fit: zeros, and no call
+        return SymbolicFit(names, params.zero_(), r2.zero_(), tab, rng, win)
+    ws = _ws(_sizes("kagnn_symbolic_fit_workspace_bytes", n, fin, fout, f), dev)
+    with _device_of(x):
+        _call("kagnn_symbolic_fit", _ptr(x), _ld(x), _ptr(phi), n, fin, fout, ids, f, *ranges_host, gn, its, _ptr(params), _ptr(r2),
+              _ptr(tab), _ptr(rng), _ptr(win), _ptr(ws), ws.numel(), _stream())
+    return SymbolicFit(names, params, r2, tab, rng, win)

@@ -47,6 +47,7 @@ HOT = [
     (r"bn_", 0, 0),
     (r"batch_assemble_kernel", 0, 0),                  # the loader's one launch per mini-batch
     (r"linear_gemm_kernel<|linear_dw_reduce_kernel", 0, 0),   # the dense layer of the MLP baselines
+    (r"sym_shared_kernel<|sym_zoom_kernel<", 0, 0),    # the symbolic-fit search: 19 functions x (two output widths of the shared pass, the zoom pass)
     (r"attention_", 0, 0),                             # dense attention: up to 4 x 32 row registers per lane at head_dim 128
 ]
 
