@@ -55,7 +55,7 @@ extern "C" {
 #define KAGNN_DTYPE_F32 0
 #define KAGNN_DTYPE_BF16 1
 
-int kagnn_version(void);          /* 279 = 278 + kagnn_symbolic_fit (+ _workspace_bytes); 278 = 277 + kagnn_edge_keys_build (+ _workspace_bytes), kagnn_negative_sample, kagnn_bce_logits_fwd / _bwd, kagnn_link_rank (+ _workspace_bytes); 277 = 276 + kagnn_neighbor_sample_mark, kagnn_edge_subgraph_count, kagnn_edge_subgraph_fill; 276 = 275 + kagnn_k_hop_mark, kagnn_subgraph_count, kagnn_subgraph_fill (+ kagnn_subgraph_workspace_bytes); 273 = 272 with kagnn_kan_grid_refit on kagnn_kan_grid_resize's kernels (up to 46 coefficients; its bits and its workspace size change); 272 = 271 + kagnn_kan_grid_resize (+ _workspace_bytes); 271 = 270 + kagnn_attention_fwd, kagnn_attention_bwd (+ _workspace_bytes); 270 = 269 + kagnn_fastkan_edge_abs_sum, kagnn_fastkan_edge_abs_sum_bwd (+ _workspace_bytes), kagnn_fastkan_edge_curves; 269 = 268 + kagnn_kan_edge_abs_sum, kagnn_kan_edge_abs_sum_bwd (+ _workspace_bytes), kagnn_kan_edge_curves; 268 = 267 + spline orders 5..KAGNN_MAX_SPLINE_ORDER in the per-operation KANLinear calls (no new entry point); 267 = 266 + kagnn_linear_fwd, kagnn_linear_bwd_input, kagnn_linear_bwd_weight (+ _workspace_bytes); 266 = 265 + kagnn_l1_loss_meter_fwd, kagnn_regression_epoch_update; 265 = 264 + kagnn_node_eval, kagnn_early_stop_update, kagnn_copy_if; 264 = 263 + kagnn_degree_one_hot, kagnn_nll_loss_fwd / _bwd; 263 = 262 + kagnn_batch_assemble; 262 = 261 - the fields edge_src, edge_dst, csr_flags of kagnn_kagin_model_t; 261 = 260 + kagnn_fastkan_fwd_stats_in_kernel; 260 = round 6: + the feature-sharded FastKAN entry points kagnn_fastkan_row_moments .. _shard_bwd_finish, + kagnn_kagin_model_*; 250 = 240 + KAGNN_PREC_HALF; 240 = 230 + kagnn_gin_kan_layer_bwd_bn_sums; 230 = 220 + the *_affine entry points of a folded BatchNorm1d; 220 = 210 + the stage timer) */
+int kagnn_version(void);          /* 280 = 279 + kagnn_symbolic_edges_plan (+ _bytes), kagnn_symbolic_edges_fwd, kagnn_symbolic_edges_bwd (+ _workspace_bytes); 279 = 278 + kagnn_symbolic_fit (+ _workspace_bytes); 278 = 277 + kagnn_edge_keys_build (+ _workspace_bytes), kagnn_negative_sample, kagnn_bce_logits_fwd / _bwd, kagnn_link_rank (+ _workspace_bytes); 277 = 276 + kagnn_neighbor_sample_mark, kagnn_edge_subgraph_count, kagnn_edge_subgraph_fill; 276 = 275 + kagnn_k_hop_mark, kagnn_subgraph_count, kagnn_subgraph_fill (+ kagnn_subgraph_workspace_bytes); 273 = 272 with kagnn_kan_grid_refit on kagnn_kan_grid_resize's kernels (up to 46 coefficients; its bits and its workspace size change); 272 = 271 + kagnn_kan_grid_resize (+ _workspace_bytes); 271 = 270 + kagnn_attention_fwd, kagnn_attention_bwd (+ _workspace_bytes); 270 = 269 + kagnn_fastkan_edge_abs_sum, kagnn_fastkan_edge_abs_sum_bwd (+ _workspace_bytes), kagnn_fastkan_edge_curves; 269 = 268 + kagnn_kan_edge_abs_sum, kagnn_kan_edge_abs_sum_bwd (+ _workspace_bytes), kagnn_kan_edge_curves; 268 = 267 + spline orders 5..KAGNN_MAX_SPLINE_ORDER in the per-operation KANLinear calls (no new entry point); 267 = 266 + kagnn_linear_fwd, kagnn_linear_bwd_input, kagnn_linear_bwd_weight (+ _workspace_bytes); 266 = 265 + kagnn_l1_loss_meter_fwd, kagnn_regression_epoch_update; 265 = 264 + kagnn_node_eval, kagnn_early_stop_update, kagnn_copy_if; 264 = 263 + kagnn_degree_one_hot, kagnn_nll_loss_fwd / _bwd; 263 = 262 + kagnn_batch_assemble; 262 = 261 - the fields edge_src, edge_dst, csr_flags of kagnn_kagin_model_t; 261 = 260 + kagnn_fastkan_fwd_stats_in_kernel; 260 = round 6: + the feature-sharded FastKAN entry points kagnn_fastkan_row_moments .. _shard_bwd_finish, + kagnn_kagin_model_*; 250 = 240 + KAGNN_PREC_HALF; 240 = 230 + kagnn_gin_kan_layer_bwd_bn_sums; 230 = 220 + the *_affine entry points of a folded BatchNorm1d; 220 = 210 + the stage timer) */
 const char* kagnn_last_error(void);
 
 /* Stage timer -- a measurement aid, off by default (no reference counterpart: the reference times whole epochs with
@@ -1295,6 +1295,47 @@ int kagnn_symbolic_fit(const float* x, int64_t ldx, const float* phi, int64_t nu
                        const int32_t* functions_host, int32_t num_functions, float a_lo, float a_hi, float b_lo, float b_hi,
                        int32_t grid_number, int32_t iterations, float* params, float* r2, float* tables, float* ranges,
                        int32_t* winners, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Fixed symbolic edges (symbolic_edges.hip; pykan's fix_symbolic): edges of a KANLinear replaced by their formulas, evaluated
+ * beside the layer's spline part.  An edge list is E records (o, i, fid) -- output, input, function id of the library above
+ * (KAGNN_SYMBOLIC_NUM_FUNCTIONS) -- sorted by (o, i), no pair twice, 0 <= E <= out_features * in_features, with the trainable
+ * parameters affine [E, 4] = (a, b, c, d), fp32, contiguous.  All arithmetic is fp32 in every precision mode; no atomics: the
+ * same inputs give the same bits, and a row's results do not depend on where the row sits or on num_rows.
+ *
+ *   t = fmaf(a, x[n,i], b)
+ *   s[n,o]   = sum, in list order starting from 0, over the edges of output o, of fmaf(c, f(t), d)
+ *   y[n,o]   = y_in[n,o] + s[n,o]     (y_in NULL: y = s; an output without an edge: y_in bit for bit, or 0)
+ *   gx[n,i]  = sum, in list order starting from 0, over the edges reading input i, of fmaf(w, a, .),  w = (gy[n,o] * c) * f'(t)
+ *              (an input no edge reads: exactly 0; gx NULL: not computed)
+ *   g_affine[e] = sums over n of ( w * x[n,i],  w,  gy[n,o] * f(t),  gy[n,o] ): 64 consecutive rows are added in a fixed order,
+ *              these sums are added per row slab in row order, and the slabs in index order.
+ *
+ * f is the library's plain function (sqrt or log outside their domain and 1/x at 0 give what IEEE gives; pykan's
+ * singularity-protected variants are deliberately not provided), except that sgn hands a NaN on.  f' is the derivative torch's
+ * autograd gives for the same expression: 1, 2t, 3t^2, 4t^3, -1/t^2, -2/t^3, 1/(2 sqrt t), -1/(2 t sqrt t), exp t, 1/t, sgn t
+ * (abs: 0 at 0), cos t, -sin t, 1 + tan^2 t, 1 - tanh^2 t, 0 (sgn), 1/(1 + t^2), -2t exp(-t^2), s(1 + t(1 - s)) with
+ * s = 1/(1 + exp(-t)) (silu).
+ *
+ * How the list travels.  kagnn_symbolic_edges_plan validates the HOST list edges_host [E, 3] (int32) once -- range of o, i and
+ * fid, the order, duplicates -- and writes a plan of kagnn_symbolic_edges_plan_bytes(E, in, out) bytes into HOST memory.  The
+ * caller keeps that block and a byte-for-byte copy of it on the device; forward and backward take both, check the host copy's
+ * header against their arguments (nothing else is validated again), read nothing back and do not synchronise.  The plan's
+ * words: {magic, E, in, out, 0, 0, 0, 0}, optr[out + 1], records {o, i, fid, 0}, iptr[in + 1], iedge[E] (each array padded to a
+ * multiple of 4 words).
+ *
+ * x [num_rows, in], y_in / y / gy [num_rows, out], gx [num_rows, in]: row-major fp32 with their own leading dimensions; y must
+ * not overlap y_in.  E == 0 or num_rows == 0 launch no kernel (y = y_in or 0; gradients 0).  Workspace of the backward:
+ * kagnn_symbolic_edges_bwd_workspace_bytes(num_rows, E), a function of its arguments alone (no device needed). */
+int kagnn_symbolic_edges_plan_bytes(int64_t num_edges, int32_t in_features, int32_t out_features, size_t* bytes_host);
+int kagnn_symbolic_edges_plan(const int32_t* edges_host, int64_t num_edges, int32_t in_features, int32_t out_features,
+                              int32_t* plan_host, size_t plan_bytes);
+int kagnn_symbolic_edges_bwd_workspace_bytes(int64_t num_rows, int64_t num_edges, size_t* bytes_host);
+int kagnn_symbolic_edges_fwd(const float* x, int64_t ldx, int64_t num_rows, int32_t in_features, int32_t out_features,
+                             const int32_t* plan_host, const int32_t* plan_dev, const float* affine, const float* y_in,
+                             int64_t ldyin, float* y, int64_t ldy, void* stream);
+int kagnn_symbolic_edges_bwd(const float* x, int64_t ldx, const float* gy, int64_t ldgy, int64_t num_rows, int32_t in_features,
+                             int32_t out_features, const int32_t* plan_host, const int32_t* plan_dev, const float* affine,
+                             float* gx, int64_t ldgx, float* g_affine, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -22,6 +22,6 @@ from .explain import edge_mask, explain_edges, receptive_hops                   
 from .data import (DeviceBatch, DeviceBatchLoader, DeviceGraphDataset, LinkSplit, NeighborLoader, NodeBatch,   # noqa: F401
                    random_link_split)
 from . import symbolic                                                           # noqa: F401
-from .symbolic import SYMBOLIC_LIB, SymbolicSuggestion, suggest_symbolic         # noqa: F401
+from .symbolic import SYMBOLIC_LIB, SymbolicSuggestion, auto_symbolic, suggest_symbolic         # noqa: F401
 
 __version__ = "0.1.0"

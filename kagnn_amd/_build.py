@@ -16,7 +16,7 @@ LIBPATH = os.path.join(LIBDIR, "libkagnn_hip.so")
 RCCL_LIBPATH = os.path.join(LIBDIR, "libkagnn_rccl.so")
 RCCL_SOURCE = "rccl_sharded.hip"
 ROCM_LIB = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib")
-SOURCES = ["api.hip", "fused_calls.hip", "csr.hip", "aggregate.hip", "aggregate_edge.hip", "aggregate_bf16.hip", "kan_fp32.hip", "kan_high_order.hip", "kan_edge.hip", "fastkan_edge.hip", "linear.hip", "attention.hip", "kan_split.hip", "kan_sparse_fwd.hip", "kan_split_bwd.hip", "kan_grid.hip", "fastkan.hip", "bn.hip", "gat.hip", "loss.hip", "classify.hip", "nodeclass.hip", "regress.hip", "p2p.hip", "batch.hip", "subgraph.hip", "linkpred.hip", "symbolic.hip"]
+SOURCES = ["api.hip", "fused_calls.hip", "csr.hip", "aggregate.hip", "aggregate_edge.hip", "aggregate_bf16.hip", "kan_fp32.hip", "kan_high_order.hip", "kan_edge.hip", "fastkan_edge.hip", "linear.hip", "attention.hip", "kan_split.hip", "kan_sparse_fwd.hip", "kan_split_bwd.hip", "kan_grid.hip", "fastkan.hip", "bn.hip", "gat.hip", "loss.hip", "classify.hip", "nodeclass.hip", "regress.hip", "p2p.hip", "batch.hip", "subgraph.hip", "linkpred.hip", "symbolic.hip", "symbolic_edges.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden",
          "-Wno-unused-result", "-DNDEBUG"]
 

@@ -63,6 +63,15 @@ _SIGNATURES = {
     # x ldx phi N in out functions(host int32) F a_lo a_hi b_lo b_hi grid_number iterations params r2 tables ranges winners ws bytes stream
     "kagnn_symbolic_fit": (c_int32, [_P, c_int64, _P, c_int64, c_int32, c_int32, POINTER(c_int32), c_int32, c_float, c_float, c_float,
                                      c_float, c_int32, c_int32, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "kagnn_symbolic_edges_plan_bytes": (c_int32, [c_int64, c_int32, c_int32, POINTER(c_size_t)]),
+    # edges(host int32 [E,3]) E in out plan(host int32) bytes
+    "kagnn_symbolic_edges_plan": (c_int32, [_P, c_int64, c_int32, c_int32, _P, c_size_t]),
+    "kagnn_symbolic_edges_bwd_workspace_bytes": (c_int32, [c_int64, c_int64, POINTER(c_size_t)]),
+    # x ldx N in out plan_host plan_dev affine y_in ldyin y ldy stream
+    "kagnn_symbolic_edges_fwd": (c_int32, [_P, c_int64, c_int64, c_int32, c_int32, _P, _P, _P, _P, c_int64, _P, c_int64, _P]),
+    # x ldx gy ldgy N in out plan_host plan_dev affine gx ldgx g_affine ws bytes stream
+    "kagnn_symbolic_edges_bwd": (c_int32, [_P, c_int64, _P, c_int64, c_int64, c_int32, c_int32, _P, _P, _P, _P, c_int64, _P, _P,
+                                           c_size_t, _P]),
     "kagnn_gcn_deg_inv_sqrt": (c_int32, [_P, _P, c_int64, _P, _P]),
     "kagnn_aggregate_workspace_bytes": (c_int32, [c_int64, c_int32, POINTER(c_size_t)]),
     "kagnn_aggregate_sum": (c_int32, [_P, c_int64, _P, c_int64, _P, _P, _P, c_int64, c_int32, c_float,

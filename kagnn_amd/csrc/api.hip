@@ -84,7 +84,7 @@ using namespace kagnn;
 #pragma GCC visibility push(default)
 extern "C" {
 
-int kagnn_version(void) { return 279; }
+int kagnn_version(void) { return 280; }
 const char* kagnn_last_error(void) { return g_err; }
 
 int kagnn_stage_timer_enable(const char* only) {
@@ -1464,6 +1464,78 @@ int kagnn_symbolic_fit(const float* x, int64_t ldx, const float* phi, int64_t N,
     KAGNN_CHECK_ARG(x && phi && ws, "null array");
     return symbolic_fit(x, ldx, phi, N, in, out, functions, F, a_lo, a_hi, b_lo, b_hi, grid_number, iterations, params, r2, tables,
                         ranges, winners, ws, ws_bytes, as_stream(stream));
+}
+
+// ---------------------------------------------------------------- fixed symbolic edges (symbolic_edges.hip)
+static int check_symbolic_edges_dims(const char* fn, int64_t E, int32_t in, int32_t out) {
+    KAGNN_CHECK_ARG_AS(fn, in >= 1 && out >= 1, "in_features and out_features must be >= 1");
+    KAGNN_CHECK_ARG_AS(fn, E >= 0 && E <= (int64_t)in * out && E < (1LL << 28), "num_edges must be 0..out_features * in_features (below 2^28)");
+    return KAGNN_OK;
+}
+
+int kagnn_symbolic_edges_plan_bytes(int64_t E, int32_t in, int32_t out, size_t* bytes) {
+    KAGNN_CHECK_ARG(bytes != nullptr, "null output");
+    int rc = check_symbolic_edges_dims(__func__, E, in, out);
+    if (rc) return rc;
+    *bytes = symbolic_edges_plan_bytes(E, in, out);
+    return KAGNN_OK;
+}
+
+int kagnn_symbolic_edges_plan(const int32_t* edges_host, int64_t E, int32_t in, int32_t out, int32_t* plan_host, size_t plan_bytes) {
+    int rc = check_symbolic_edges_dims(__func__, E, in, out);
+    if (rc) return rc;
+    KAGNN_CHECK_ARG(plan_host != nullptr && (E == 0 || edges_host != nullptr), "null array");
+    KAGNN_CHECK_ARG(plan_bytes >= symbolic_edges_plan_bytes(E, in, out), "plan buffer too small");
+    return symbolic_edges_plan(edges_host, E, in, out, plan_host);
+}
+
+int kagnn_symbolic_edges_bwd_workspace_bytes(int64_t N, int64_t E, size_t* bytes) {
+    KAGNN_CHECK_ARG(bytes != nullptr, "null output");
+    KAGNN_CHECK_ARG(N >= 0 && N < 2147483647LL, "num_rows outside [0, 2^31 - 1)");
+    KAGNN_CHECK_ARG(E >= 0 && E < (1LL << 28), "num_edges outside [0, 2^28)");
+    *bytes = symbolic_edges_bwd_ws_bytes(N, E);
+    return KAGNN_OK;
+}
+
+int kagnn_symbolic_edges_fwd(const float* x, int64_t ldx, int64_t N, int32_t in, int32_t out, const int32_t* plan_host,
+                             const int32_t* plan_dev, const float* affine, const float* y_in, int64_t ldyin, float* y, int64_t ldy,
+                             void* stream) {
+    KAGNN_STAGE(stream);
+    KAGNN_CHECK_ARG(in >= 1 && out >= 1, "in_features and out_features must be >= 1");
+    KAGNN_CHECK_ARG(N >= 0 && N < 2147483647LL, "num_rows outside [0, 2^31 - 1)");
+    KAGNN_CHECK_ARG(ldx >= in && ldy >= out && (!y_in || ldyin >= out), "a leading dimension is smaller than its width");
+    KAGNN_CHECK_ARG(plan_host != nullptr, "plan_host is null");
+    if (N == 0) return KAGNN_OK;
+    KAGNN_CHECK_ARG(y != nullptr && y != y_in, "y is null or y_in itself");
+    if (plan_host[1] == 0) {                                 // no edge: y = y_in or 0, no launch
+        const size_t w = (size_t)out * sizeof(float);
+        if (y_in) KAGNN_HIP(hipMemcpy2DAsync(y, (size_t)ldy * sizeof(float), y_in, (size_t)ldyin * sizeof(float), w, (size_t)N,
+                                             hipMemcpyDeviceToDevice, as_stream(stream)));
+        else KAGNN_HIP(hipMemset2DAsync(y, (size_t)ldy * sizeof(float), 0, w, (size_t)N, as_stream(stream)));
+        return KAGNN_OK;
+    }
+    KAGNN_CHECK_ARG(x && plan_dev && affine, "null array");
+    return symbolic_edges_fwd(x, ldx, N, in, out, plan_host, plan_dev, affine, y_in, ldyin, y, ldy, as_stream(stream));
+}
+
+int kagnn_symbolic_edges_bwd(const float* x, int64_t ldx, const float* gy, int64_t ldgy, int64_t N, int32_t in, int32_t out,
+                             const int32_t* plan_host, const int32_t* plan_dev, const float* affine, float* gx, int64_t ldgx,
+                             float* g_affine, void* ws, size_t ws_bytes, void* stream) {
+    KAGNN_STAGE(stream);
+    KAGNN_CHECK_ARG(in >= 1 && out >= 1, "in_features and out_features must be >= 1");
+    KAGNN_CHECK_ARG(N >= 0 && N < 2147483647LL, "num_rows outside [0, 2^31 - 1)");
+    KAGNN_CHECK_ARG(ldx >= in && ldgy >= out && (!gx || ldgx >= in), "a leading dimension is smaller than its width");
+    KAGNN_CHECK_ARG(plan_host != nullptr, "plan_host is null");
+    const int64_t E = plan_host[1];
+    KAGNN_CHECK_ARG(E == 0 || g_affine != nullptr, "g_affine is null");
+    if (N == 0 || E == 0) {                                  // empty sums: zeros, no launch
+        if (gx && N > 0) KAGNN_HIP(hipMemset2DAsync(gx, (size_t)ldgx * sizeof(float), 0, (size_t)in * sizeof(float), (size_t)N, as_stream(stream)));
+        if (E > 0 && E <= (int64_t)in * out) KAGNN_HIP(hipMemsetAsync(g_affine, 0, (size_t)E * 4 * sizeof(float), as_stream(stream)));
+        return KAGNN_OK;
+    }
+    KAGNN_CHECK_ARG(x && gy && plan_dev && affine && ws, "null array");
+    return symbolic_edges_bwd(x, ldx, gy, ldgy, N, in, out, plan_host, plan_dev, affine, gx, ldgx, g_affine, ws, ws_bytes,
+                              as_stream(stream));
 }
 
 // ---------------------------------------------------------------- direct peer-to-peer exchange (p2p.hip)

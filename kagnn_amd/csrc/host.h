@@ -247,6 +247,16 @@ int symbolic_fit(const float* x, long ldx, const float* phi, long N, int in, int
                  float ahi, float blo, float bhi, int Gn, int iterations, float* params, float* r2, float* tables, float* ranges,
                  int* winners, void* ws, size_t ws_bytes, hipStream_t st);
 
+// ---- symbolic_edges.hip (fixed symbolic edges of a KANLinear: sum over a sparse edge list of c f(a x + b) + d, and its backward)
+size_t symbolic_edges_plan_bytes(long E, int in, int out);
+int symbolic_edges_plan(const int* edges_host, long E, int in, int out, int* plan_host);
+size_t symbolic_edges_bwd_ws_bytes(long N, long E);
+int symbolic_edges_fwd(const float* x, long ldx, long N, int in, int out, const int* plan_host, const int* plan_dev,
+                       const float* affine, const float* y_in, long ldyin, float* y, long ldy, hipStream_t st);
+int symbolic_edges_bwd(const float* x, long ldx, const float* gy, long ldgy, long N, int in, int out, const int* plan_host,
+                       const int* plan_dev, const float* affine, float* gx, long ldgx, float* g_affine, void* ws, size_t ws_bytes,
+                       hipStream_t st);
+
 // ---- gat.hip
 int gat_logits(const float* xh, long ld, long N, int H, int C, const float* att_src, const float* att_dst, float* a_s, float* a_d,
                hipStream_t st);

@@ -30,6 +30,7 @@
 // (f, o, i).  The optional tables / ranges / winners outputs are written by the same kernels.
 #include "common.h"
 #include "host.h"
+#include "symbolic_fn.h"
 
 #include <cfloat>
 
@@ -57,53 +58,7 @@ size_t symbolic_ws_bytes(long N, int in, int out, int F) {
            sizeof(SymBest) * (size_t)F * in * out * kSymSlots + 64;
 }
 
-template <int FID>
-__device__ __forceinline__ float sym_fn(float t) {
-    if constexpr (FID == 0) return t;
-    else if constexpr (FID == 1) return t * t;
-    else if constexpr (FID == 2) return t * t * t;
-    else if constexpr (FID == 3) { const float q = t * t; return q * q; }
-    else if constexpr (FID == 4) return 1.0f / t;
-    else if constexpr (FID == 5) return 1.0f / (t * t);
-    else if constexpr (FID == 6) return sqrtf(t);
-    else if constexpr (FID == 7) return 1.0f / sqrtf(t);
-    else if constexpr (FID == 8) return expf(t);
-    else if constexpr (FID == 9) return logf(t);
-    else if constexpr (FID == 10) return fabsf(t);
-    else if constexpr (FID == 11) return sinf(t);
-    else if constexpr (FID == 12) return cosf(t);
-    else if constexpr (FID == 13) return tanf(t);
-    else if constexpr (FID == 14) return tanhf(t);
-    else if constexpr (FID == 15) return t > 0.0f ? 1.0f : (t < 0.0f ? -1.0f : 0.0f);
-    else if constexpr (FID == 16) return atanf(t);
-    else if constexpr (FID == 17) return expf(-(t * t));
-    else return t / (1.0f + expf(-t));
-}
-
-// the same library in fp64, for the one evaluation per (function, edge) that (c, d) come from: d = ybar - c ubar carries the
-// rounding of every u_n times ubar / sigma_u, up to 300 at the degeneracy threshold, which fp32 values of f cannot hold to 2e-5
-template <int FID>
-__device__ __forceinline__ double sym_fn_d(double t) {
-    if constexpr (FID == 0) return t;
-    else if constexpr (FID == 1) return t * t;
-    else if constexpr (FID == 2) return t * t * t;
-    else if constexpr (FID == 3) { const double q = t * t; return q * q; }
-    else if constexpr (FID == 4) return 1.0 / t;
-    else if constexpr (FID == 5) return 1.0 / (t * t);
-    else if constexpr (FID == 6) return sqrt(t);
-    else if constexpr (FID == 7) return 1.0 / sqrt(t);
-    else if constexpr (FID == 8) return exp(t);
-    else if constexpr (FID == 9) return log(t);
-    else if constexpr (FID == 10) return fabs(t);
-    else if constexpr (FID == 11) return sin(t);
-    else if constexpr (FID == 12) return cos(t);
-    else if constexpr (FID == 13) return tan(t);
-    else if constexpr (FID == 14) return tanh(t);
-    else if constexpr (FID == 15) return t > 0.0 ? 1.0 : (t < 0.0 ? -1.0 : 0.0);
-    else if constexpr (FID == 16) return atan(t);
-    else if constexpr (FID == 17) return exp(-(t * t));
-    else return t / (1.0 + exp(-t));
-}
+// (sym_fn<FID> and its fp64 twin sym_fn_d<FID>: symbolic_fn.h, shared with symbolic_edges.hip)
 
 // candidate k of an axis: (float)(lo + k (hi - lo) / (Gn - 1)), in fp64 as the header states it
 __device__ __forceinline__ float sym_axis(float lo, float hi, int k, int Gn) {

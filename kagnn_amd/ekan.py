@@ -42,7 +42,11 @@ class KANLinear(nn.Module):
 
     ``B(x)`` are the ``grid_size + spline_order`` uniform B-spline bases per input feature; they
     are evaluated in registers inside the HIP kernel and never stored.
+
+    ``fix_symbolic`` replaces single edges by ``c f(a x + b) + d`` (INTEGRATION.md "Fixed symbolic edges"); a layer that never fixed
+    an edge has the reference's state and routes.
     """
+    _symbolic = None        # (also for a module unpickled from before the attribute existed)
 
     def __init__(self, in_features, out_features, grid_size=5, spline_order=3, scale_noise=0.1,
                  scale_base=1.0, scale_spline=1.0, enable_standalone_scale_spline=True,
@@ -79,6 +83,7 @@ class KANLinear(nn.Module):
             self.spline_scaler = nn.Parameter(torch.empty(out_features, in_features))
         self._knots_key = None
         self._knots_row = None
+        self._symbolic: Optional[ops.SymbolicEdges] = None     # the list of fixed symbolic edges (fix_symbolic); None: the reference's layer
         self.reset_parameters()
         self.refresh_knots()
 
@@ -161,10 +166,25 @@ class KANLinear(nn.Module):
     def _apply(self, fn, *args, **kwargs):
         out = super()._apply(fn, *args, **kwargs)          # .to() / .cuda() / .float(): the cache is a plain attribute and does not move
         self.refresh_knots()
+        if self._symbolic is not None and self._symbolic.device != self.symbolic_index.device:
+            self._symbolic = ops.SymbolicEdges.from_sorted(self._symbolic.triples, self.in_features, self.out_features,
+                                                           self.symbolic_index.device)
         return out
 
-    def _load_from_state_dict(self, *args, **kwargs):
-        super()._load_from_state_dict(*args, **kwargs)     # a checkpoint's grid may hold per-feature rows
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        index = state_dict.get(prefix + "symbolic_index")
+        if index is None:
+            self._drop_symbolic_state()                    # the checkpoint's layer has no fixed edge
+        else:                                              # make room for the checkpoint's list, whatever this layer holds
+            dev = self.base_weight.device
+            self._drop_symbolic_state()
+            self.symbolic_affine = nn.Parameter(torch.zeros((index.size(0), 4), dtype=torch.float32, device=dev))
+            self.register_buffer("symbolic_index", torch.zeros((index.size(0), 3), dtype=torch.int32, device=dev))
+            self.register_buffer("symbolic_keep", torch.ones((self.out_features, self.in_features), dtype=torch.float32, device=dev))
+        super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)     # a checkpoint's grid may hold per-feature rows
+        if index is not None:
+            self._symbolic = ops.SymbolicEdges.from_sorted(self.symbolic_index.cpu().tolist(), self.in_features, self.out_features,
+                                                           self.symbolic_index.device)
         self.refresh_knots()
 
     def forward(self, x: torch.Tensor, _packed=None) -> torch.Tensor:
@@ -180,21 +200,40 @@ class KANLinear(nn.Module):
     def _forward(self, x: torch.Tensor, _packed=None) -> torch.Tensor:
         """the layer itself, without the statistics of a ``collect_edge_l1`` block (the chain walks of ``KAN.edge_l1`` /
         ``KAN.regularization_loss(x=)`` are not the model's forward)"""
+        if self._symbolic is not None:
+            return self._forward_fixed(x)
         scaler = self.spline_scaler if self.enable_standalone_scale_spline else None
         return ops.kan_linear(x, self.base_weight, self.spline_weight, scaler, self._knots(),
                               self.grid_size, self.spline_order, self.precision, _packed)
 
+    def _kept_operands(self):
+        """``(base_weight, spline_weight, spline_scaler)`` with the fixed edges switched off: small torch ops on ``symbolic_keep``, so the
+        fixed edges' entries get exactly zero gradient"""
+        keep = self.symbolic_keep
+        if self.enable_standalone_scale_spline:
+            return self.base_weight * keep, self.spline_weight, self.spline_scaler * keep
+        return self.base_weight * keep, self.spline_weight * keep.unsqueeze(-1), None
+
+    def _forward_fixed(self, x: torch.Tensor) -> torch.Tensor:
+        """the layer with fixed symbolic edges: ``ops.kan_linear`` on the kept spline edges, then ``ops.symbolic_edges`` adds the
+        formulas to its output (any spline order: the symbolic kernel does not see the spline)"""
+        if torch.compiler.is_compiling():
+            raise NotImplementedError("a KANLinear with fixed symbolic edges is not supported under torch.compile (unfix_symbolic first)")
+        bw, sw, sc = self._kept_operands()
+        y = ops.kan_linear(x, bw, sw, sc, self._knots(), self.grid_size, self.spline_order, self.precision)
+        return ops.symbolic_edges(x, self._symbolic, self.symbolic_affine, self.out_features, y=y)
+
     def read_out_blocks_in_one_launch(self, widths) -> bool:
         """would ``forward_parts`` over fp32 blocks of these widths run as one forward launch (``kagnn_kan_fwd_parts_ok``)?"""
         mode = self.precision if self.precision is not None else ops.default_precision()
-        return (not ops.high_order(self.spline_order) and self._knots().dim() == 1 and ops.split_like(mode) and sum(widths) == self.in_features
+        return (self._symbolic is None and not ops.high_order(self.spline_order) and self._knots().dim() == 1 and ops.split_like(mode) and sum(widths) == self.in_features
                 and ops.parts_one_launch_widths_ok(tuple(int(w) for w in widths), self.out_features, self.grid_size, self.spline_order, mode))
 
     def forward_parts(self, parts, skip_gradients=None) -> torch.Tensor:
         """``forward(torch.cat(parts, dim=1))`` without the concatenation (``ops.kan_linear_parts``)."""
         knots = self._knots()
-        if knots.dim() != 1 or ops.high_order(self.spline_order) or ops.layer_inputs_visible():
-            # adaptive grid (per-feature knot rows) / orders above 4: keep it simple; a collect_edge_l1 block: forward() must see the input
+        if knots.dim() != 1 or ops.high_order(self.spline_order) or ops.layer_inputs_visible() or self._symbolic is not None:
+            # adaptive grid (per-feature knot rows) / orders above 4 / fixed symbolic edges: keep it simple; a collect_edge_l1 block: forward() must see the input
             return self.forward(ops.concat_columns([t.materialise() if isinstance(t, ops.AffineRows) else t for t in parts]))
         scaler = self.spline_scaler if self.enable_standalone_scale_spline else None
         return ops.kan_linear_parts(parts, self.base_weight, self.spline_weight, scaler, knots, self.grid_size,
@@ -300,13 +339,144 @@ class KANLinear(nn.Module):
         what the KAN paper's regulariser is defined on, and what tells which inputs / edges a trained layer uses.  One fused
         kernel (``ops.kan_edge_abs_sum``): no [N, out, in] tensor.  Differentiable.  Spline orders 1..4."""
         assert x.dim() == 2 and x.size(1) == self.in_features
+        if self._symbolic is not None:
+            # the layer as it now is: the kept spline edges, and mean |c f(a x + b) + d| of the fixed ones ("0": nothing)
+            from .symbolic import fixed_edge_values
+            rows = max(x.size(0), 1)
+            mag = ops.kan_edge_abs_sum(x, *self._kept_operands(), *self._edge_args()[3:]) / rows
+            idx = self.symbolic_index.long()
+            if idx.size(0) == 0 or x.size(0) == 0:
+                return mag
+            step = max(1, (1 << 22) // idx.size(0))
+            total = sum(fixed_edge_values(x[r:r + step], self._symbolic.triples, self.symbolic_affine).abs().sum(0)
+                        for r in range(0, x.size(0), step))
+            return mag.index_put((idx[:, 0], idx[:, 1]), total / rows)
         return ops.kan_edge_abs_sum(x, *self._edge_args()) / max(x.size(0), 1)
 
     @torch.no_grad()
     def edge_curves(self, points: torch.Tensor) -> torch.Tensor:
         """``[P, out, in]``: every edge function sampled at ``points`` (``[P]``, shared by all inputs, or ``[P, in]``) -- the
-        reference's ``plot_curve`` (``fastkan.py``) for all edges at once."""
+        reference's ``plot_curve`` (``fastkan.py``) for all edges at once.  Fixed symbolic edges show their formula (``"0"``: 0)."""
+        if self._symbolic is not None:
+            from .symbolic import fixed_edge_values
+            phi = ops.kan_edge_curves(points, *self._kept_operands(), *self._edge_args()[3:])
+            idx = self.symbolic_index.long()
+            if idx.size(0):
+                pts = points.to(phi.dtype)
+                pts = pts.reshape(-1, 1).expand(-1, self.in_features) if pts.dim() == 1 else pts
+                phi[:, idx[:, 0], idx[:, 1]] = fixed_edge_values(pts, self._symbolic.triples, self.symbolic_affine.detach())
+            return phi
         return ops.kan_edge_curves(points, *self._edge_args())
+
+    # ------------------------------------------------------------------ fixed symbolic edges (pykan's fix_symbolic)
+    def _drop_symbolic_state(self) -> None:
+        self._symbolic = None
+        self._parameters.pop("symbolic_affine", None)
+        self._buffers.pop("symbolic_index", None)
+        self._buffers.pop("symbolic_keep", None)
+        self._non_persistent_buffers_set.discard("symbolic_index")
+        self._non_persistent_buffers_set.discard("symbolic_keep")
+
+    def fixed_edges(self) -> Dict[tuple, str]:
+        """``{(o, i): name}`` of the fixed edges, sorted by ``(o, i)``; ``name`` is a function of ``SYMBOLIC_LIB`` or ``"0"`` (switched off)"""
+        if self._symbolic is None:
+            return {}
+        out = {(o, i): ops.SYMBOLIC_FUNCTIONS[f] for o, i, f in self._symbolic.triples}
+        for o, i in (self.symbolic_keep == 0).nonzero().cpu().tolist():
+            out.setdefault((o, i), "0")
+        return dict(sorted(out.items()))
+
+    def _set_fixed(self, fixed: Dict[tuple, tuple]) -> None:
+        """install ``{(o, i): (name, affine row or None)}`` as the layer's fixed edges: NEW ``symbolic_affine`` Parameter and buffers, one
+        validated ``ops.SymbolicEdges``; empty: the symbolic state is removed and the layer is the reference's again"""
+        dev = self.base_weight.device
+        self._drop_symbolic_state()
+        if not fixed:
+            return
+        live = sorted((o, i, ops.SYMBOLIC_FUNCTIONS.index(name)) for (o, i), (name, _) in fixed.items() if name != "0")
+        edges = ops.SymbolicEdges.from_sorted(live, self.in_features, self.out_features, dev)
+        rows = [fixed[(o, i)][1].detach().to(device=dev, dtype=torch.float32).reshape(4) for o, i, _ in live]
+        affine = torch.stack(rows) if rows else torch.zeros((0, 4), dtype=torch.float32, device=dev)
+        keep = torch.ones((self.out_features, self.in_features), dtype=torch.float32, device=dev)
+        at = torch.tensor(sorted(fixed), dtype=torch.int64, device=dev).reshape(-1, 2)
+        keep[at[:, 0], at[:, 1]] = 0.0
+        self.symbolic_affine = nn.Parameter(affine.contiguous(), requires_grad=self.base_weight.requires_grad)
+        self.register_buffer("symbolic_index", edges.index)
+        self.register_buffer("symbolic_keep", keep)
+        self._symbolic = edges
+
+    def _fixed_state(self) -> Dict[tuple, tuple]:
+        if self._symbolic is None:
+            return {}
+        rows = {(o, i): self.symbolic_affine[e] for e, (o, i, _) in enumerate(self._symbolic.triples)}
+        return {k: (name, rows.get(k)) for k, name in self.fixed_edges().items()}
+
+    def _check_edge(self, o, i) -> tuple:
+        o, i = int(o), int(i)
+        if not (0 <= o < self.out_features and 0 <= i < self.in_features):
+            raise IndexError(f"edge ({o}, {i}) is outside a layer of {self.out_features} x {self.in_features}")
+        return o, i
+
+    def fix_symbolic(self, o: int, i: int, name: str, params=None, x: Optional[torch.Tensor] = None, max_rows: int = 4096, **search):
+        """Replace edge ``(o, i)`` by ``c f(a x + b) + d`` in the forward (pykan's ``fix_symbolic``): ``name`` is a function of
+        ``SYMBOLIC_LIB``, or ``"0"``, which switches the edge off with no symbolic term.  ``params = (a, b, c, d)`` is given, or fitted
+        on the rows ``x [N, in]`` (the layer's own input): ``ops.symbolic_fit`` of that one function on ``edge_curves`` with
+        ``suggest_symbolic``'s row rule (``max_rows``) and ``**search`` -- bit for bit the parameters ``suggest_symbolic`` reports for
+        that function.  Returns the fit's ``r2``, or ``None`` when nothing was fitted.
+
+        The four numbers are trainable (``symbolic_affine [E, 4]``, one row per fixed function edge in ``(o, i)`` order); the edge's
+        spline parameters stay where they are, get exactly zero gradient while it is fixed, and are back with ``unfix_symbolic``.
+        Every change of the list makes ``symbolic_affine`` a NEW Parameter: rebuild the optimizer, as after ``refine``.  The plain
+        functions: ``sqrt`` / ``log`` outside their domain and ``1/x`` at 0 give what IEEE gives (pykan's singularity-protected
+        variants are not provided)."""
+        from .symbolic import SYMBOLIC_LIB, _rows32, strided_rows
+        o, i = self._check_edge(o, i)
+        if name != "0" and name not in SYMBOLIC_LIB:
+            raise ValueError(f"fix_symbolic: unknown function {name!r}; the library is {', '.join(SYMBOLIC_LIB)} and \"0\"")
+        r2, row = None, None
+        if name != "0":
+            if params is not None:
+                row = torch.as_tensor(params, dtype=torch.float32).reshape(-1)
+                if row.numel() != 4:
+                    raise ValueError("fix_symbolic: params must be (a, b, c, d)")
+            elif x is not None:
+                with torch.no_grad():
+                    rows = strided_rows(_rows32(x, self.in_features), max_rows)
+                    fit = ops.symbolic_fit(rows, self.edge_curves(rows), (name,), **search)
+                row, r2 = fit.params[0, o, i].clone(), float(fit.r2[0, o, i])
+            else:
+                raise ValueError("fix_symbolic: give params=(a, b, c, d), or the rows x to fit them on")
+        fixed = self._fixed_state()
+        fixed[(o, i)] = (name, row)
+        self._set_fixed(fixed)
+        return r2
+
+    def unfix_symbolic(self, o: int, i: int) -> None:
+        """edge ``(o, i)`` is a spline again, with the coefficients it had; the last edge unfixed removes the symbolic state"""
+        o, i = self._check_edge(o, i)
+        fixed = self._fixed_state()
+        if (o, i) not in fixed:
+            raise KeyError(f"edge ({o}, {i}) is not fixed")
+        del fixed[(o, i)]
+        self._set_fixed(fixed)
+
+    def symbolic_formula(self, o: int, digits: int = 4) -> str:
+        """output ``o`` as text, ``0.73*sin(3.1*x0 + 0.4) - 0.2 + ...`` over the inputs ``x0, x1, ...``; defined when all of ``o``'s
+        incoming edges are fixed"""
+        from .symbolic import format_edge
+        o, _ = self._check_edge(o, 0)
+        fixed = self._fixed_state()
+        missing = [i for i in range(self.in_features) if (o, i) not in fixed]
+        if missing:
+            raise ValueError(f"symbolic_formula: output {o} still has spline edges from inputs {missing}")
+        text = ""
+        for i in range(self.in_features):
+            name, row = fixed[(o, i)]
+            if name == "0":
+                continue
+            term = format_edge(name, *(float(v) for v in row.tolist()), digits=digits, var=f"x{i}")
+            text = term if not text else (f"{text} - {term[1:]}" if term.startswith("-") else f"{text} + {term}")
+        return text or "0"
 
     def suggest_symbolic(self, x: torch.Tensor, functions=None, topk: int = 3, max_rows: int = 4096, **search):
         """Which elementary function is every edge ``phi_{o,i}``: a ``SymbolicSuggestion`` (``kagnn_amd/symbolic.py``) with the
@@ -367,7 +537,7 @@ class KAN(nn.Module):
         """all layers' weight packs in one launch when the chain runs on the sparse-forward / split kernels"""
         first = self.layers[0]
         mode = first.precision if first.precision is not None else ops.default_precision()
-        if ops.layer_inputs_visible() or ops.high_order(self.spline_order) or not ops.split_like(mode) or any(l.precision != first.precision or l._knots().dim() != 1 for l in self.layers):
+        if ops.layer_inputs_visible() or ops.high_order(self.spline_order) or not ops.split_like(mode) or any(l.precision != first.precision or l._knots().dim() != 1 or l._symbolic is not None for l in self.layers):
             return None
         if x.size(0) == 0 or not ops._fits32(x, 1):
             return None

@@ -232,7 +232,8 @@ def _gine_stack_plan(x, convs, bns):
             first = layers[0]
         for l in layers:
             if (l.in_features != H or l.out_features != H or l.precision != first.precision or l.grid_size != first.grid_size
-                    or l.spline_order != first.spline_order or not l.enable_standalone_scale_spline):
+                    or l.spline_order != first.spline_order or not l.enable_standalone_scale_spline
+                    or getattr(l, "_symbolic", None) is not None):          # (fixed symbolic edges: the layer runs its own forward)
                 return None
         all_layers += layers
         if not (bn.training and bn.affine and bn.num_features == H):
@@ -614,7 +615,7 @@ def kagin_regression_forward(model, data):
     ro_knots, ro_modes = [], []
     for l in ro:
         k = l._knots()
-        if k.dim() != 1 or l.grid_size != G_r or l.spline_order != K_r or G_r + K_r > 16 or K_r > 4:
+        if k.dim() != 1 or l.grid_size != G_r or l.spline_order != K_r or G_r + K_r > 16 or K_r > 4 or getattr(l, "_symbolic", None) is not None:
             return None
         m = l.precision if l.precision is not None else default_precision()
         if split_like(m) and max(l.in_features, l.out_features) > 7680:

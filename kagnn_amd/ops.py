@@ -1737,6 +1737,8 @@ def _chain_plan(layers):
     mode = first.precision if first.precision is not None else default_precision()
     if any(high_order(l.spline_order) for l in layers):
         return None                                      # the fused calls take orders 1..4: the caller composes the operations
+    if any(getattr(l, "_symbolic", None) is not None for l in layers):
+        return None                                      # a layer with fixed symbolic edges runs its own forward (KANLinear.fix_symbolic)
     if any(l.precision != first.precision or l.grid_size != first.grid_size or l.spline_order != first.spline_order
            or l.grid_size + l.spline_order > 16 or not l.enable_standalone_scale_spline for l in layers):
         return None
@@ -3580,3 +3582,131 @@ def symbolic_fit(x, phi, functions=None, a_range=(-10, 10), b_range=(-10, 10), g
         _call("kagnn_symbolic_fit", _ptr(x), _ld(x), _ptr(phi), n, fin, fout, ids, f, *ranges_host, gn, its, _ptr(params), _ptr(r2),
               _ptr(tab), _ptr(rng), _ptr(win), _ptr(ws), ws.numel(), _stream())
     return SymbolicFit(names, params, r2, tab, rng, win)
+
+
+# ======================================================================== fixed symbolic edges (csrc/symbolic_edges.hip)
+class SymbolicEdges:
+    """A validated list of fixed symbolic edges of one layer: ``edges`` = ``(o, i, name)`` triples (any order; a pair at most once),
+    sorted here by ``(o, i)``.  ``triples``: the sorted host tuples ``(o, i, function id)``; ``index``: the same as int32 ``[E, 3]`` on
+    ``device``; ``plan_host`` / ``plan``: the library's plan of the list (``kagnn_symbolic_edges_plan``: validated once, here) on the
+    host and on the device.  Build one per change of the list; row ``e`` of the ``affine [E, 4]`` operand of ``symbolic_edges``
+    belongs to ``triples[e]``."""
+
+    def __init__(self, edges, in_features: int, out_features: int, device):
+        fin, fout = int(in_features), int(out_features)
+        if fin < 1 or fout < 1:
+            raise ValueError(f"SymbolicEdges: in_features and out_features must be >= 1 (got {in_features}, {out_features})")
+        triples = []
+        for rec in edges:
+            o, i, f = rec
+            if isinstance(f, str):
+                if f not in SYMBOLIC_FUNCTIONS:
+                    raise ValueError(f"SymbolicEdges: unknown function {f!r}; the library is {', '.join(SYMBOLIC_FUNCTIONS)}")
+                f = SYMBOLIC_FUNCTIONS.index(f)
+            triples.append((int(o), int(i), int(f)))
+        triples.sort()
+        self.triples: Tuple[Tuple[int, int, int], ...] = tuple(triples)
+        self.in_features, self.out_features = fin, fout
+        self._build(torch.device(device))
+
+    @classmethod
+    def from_sorted(cls, triples, in_features: int, out_features: int, device) -> "SymbolicEdges":
+        """the list AS GIVEN, ``(o, i, function id)`` integer triples: an unsorted list, a repeated pair, an edge outside the layer
+        or an unknown id are refused by the library's own validation"""
+        self = cls.__new__(cls)
+        self.triples = tuple((int(o), int(i), int(f)) for o, i, f in triples)
+        self.in_features, self.out_features = int(in_features), int(out_features)
+        self._build(torch.device(device))
+        return self
+
+    def _build(self, device) -> None:
+        e = len(self.triples)
+        host = torch.tensor(self.triples, dtype=torch.int32).reshape(e, 3).contiguous()
+        if self.in_features < 1 or self.out_features < 1 or e > self.in_features * self.out_features:
+            raise ValueError(f"SymbolicEdges: {e} edges do not fit a layer of {self.out_features} x {self.in_features}")
+        nbytes = _sizes("kagnn_symbolic_edges_plan_bytes", e, self.in_features, self.out_features)
+        self.plan_host = torch.zeros(nbytes // 4, dtype=torch.int32)
+        try:
+            _call("kagnn_symbolic_edges_plan", _ptr(host), e, self.in_features, self.out_features, _ptr(self.plan_host), nbytes)
+        except RuntimeError as ex:
+            raise ValueError(str(ex)) from None
+        self.index = host.to(device)
+        self.plan = self.plan_host.to(device)
+
+    def __len__(self):
+        return len(self.triples)
+
+    @property
+    def device(self):
+        return self.plan.device
+
+
+def symbolic_edges_workspace_bytes(num_rows: int, num_edges: int) -> int:
+    """the backward's workspace (``kagnn_symbolic_edges_bwd_workspace_bytes``): a function of the two counts, no device needed"""
+    return _sizes("kagnn_symbolic_edges_bwd_workspace_bytes", int(num_rows), int(num_edges))
+
+
+class _SymbolicEdgesFn(Function):
+    @staticmethod
+    @_on_operand_device
+    def forward(ctx, x, affine, y_in, edges):
+        x = _rows(x.detach())
+        aff = affine.detach().contiguous()
+        yi = None if y_in is None else _rows(y_in.detach())
+        n, fout = x.size(0), edges.out_features
+        y = torch.empty((n, fout), dtype=torch.float32, device=x.device)
+        _call("kagnn_symbolic_edges_fwd", _ptr(x), _ld(x), n, edges.in_features, fout, _ptr(edges.plan_host), _ptr(edges.plan),
+              _ptr(aff), _ptr(yi), 0 if yi is None else _ld(yi), _ptr(y), fout, _stream())
+        ctx.save_for_backward(x, aff)
+        ctx.edges = edges
+        return y
+
+    @staticmethod
+    @once_differentiable
+    @_on_operand_device
+    def backward(ctx, gy):
+        x, aff = ctx.saved_tensors
+        edges = ctx.edges
+        need = ctx.needs_input_grad
+        gaff = gx = None
+        if need[0] or need[1]:
+            g = _rows(gy)
+            n, e = x.size(0), len(edges)
+            gx = torch.empty((n, edges.in_features), dtype=torch.float32, device=x.device) if need[0] else None
+            gaff = torch.empty((e, 4), dtype=torch.float32, device=x.device)
+            ws = _ws(symbolic_edges_workspace_bytes(n, e), x.device)
+            _call("kagnn_symbolic_edges_bwd", _ptr(x), _ld(x), _ptr(g), _ld(g), n, edges.in_features, edges.out_features,
+                  _ptr(edges.plan_host), _ptr(edges.plan), _ptr(aff), _ptr(gx), edges.in_features, _ptr(gaff), _ptr(ws), ws.numel(),
+                  _stream())
+        return gx, (gaff if need[1] else None), (gy if need[2] else None), None
+
+
+def symbolic_edges(x, edges: SymbolicEdges, affine, out_features: int, y: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``y[n,o] + sum over the fixed edges (o, i, f) of c f(a x[n,i] + b) + d`` (``y`` absent: the sum alone) -- the symbolic part
+    of a layer with fixed edges, ``[N, out_features]``.  ``x [N, in]`` fp32 (a row stride is allowed), ``edges``: a
+    ``SymbolicEdges``, ``affine [E, 4]`` = ``(a, b, c, d)`` per edge of ``edges.triples``, ``y [N, out_features]`` typically the spline
+    part's output.  One tape node, differentiable in ``x``, ``affine`` and ``y`` (whose gradient is the incoming one itself); exact
+    fp32, deterministic, nothing of size ``N x E``; the formulae are stated at ``kagnn_symbolic_edges_fwd`` in include/kagnn_hip.h.
+    The plain functions: ``sqrt`` / ``log`` outside their domain and ``1/x`` at 0 give what IEEE gives.  No edge or no row: no
+    launch (``y`` or zeros; zero gradients)."""
+    if not isinstance(edges, SymbolicEdges):
+        raise TypeError("symbolic_edges: edges must be an ops.SymbolicEdges")
+    fout = int(out_features)
+    if fout != edges.out_features:
+        raise ValueError(f"symbolic_edges: the list was built for {edges.out_features} outputs, not {out_features}")
+    if x.dim() != 2 or x.size(1) != edges.in_features:
+        raise ValueError(f"symbolic_edges: x must be [N, {edges.in_features}]; got {tuple(x.shape)}")
+    if affine.shape != (len(edges), 4):
+        raise ValueError(f"symbolic_edges: affine must be [{len(edges)}, 4]; got {tuple(affine.shape)}")
+    if y is not None and y.shape != (x.size(0), fout):
+        raise ValueError(f"symbolic_edges: y must be [{x.size(0)}, {fout}]; got {tuple(y.shape)}")
+    for t in (x, affine, y):
+        if t is not None and t.dtype != torch.float32:
+            raise TypeError(f"kagnn_amd kernels are fp32; got {t.dtype}")
+    _need_cuda(x, affine, y, edges.plan)
+    if x.size(0) == 0 or len(edges) == 0:                     # nothing to evaluate: no launch
+        base = y.clone() if y is not None else torch.zeros((x.size(0), fout), dtype=torch.float32, device=x.device)
+        if len(edges) and affine.requires_grad and torch.is_grad_enabled():
+            base = base + 0.0 * affine.sum()                   # (no row: the tape still reaches affine, with zeros)
+        return base
+    return _SymbolicEdgesFn.apply(x, affine, y, edges)

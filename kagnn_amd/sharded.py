@@ -264,6 +264,8 @@ class ShardedKANLinear(nn.Module):
         if full.spline_order > 4:
             raise ValueError("sharded KANLinear layers are not supported at spline_order above 4 (the exact-fp32 kernels of these "
                              "orders take neither packed= nor out=)")
+        if getattr(full, "_symbolic", None) is not None:
+            raise NotImplementedError("a KANLinear with fixed symbolic edges cannot be sharded (unfix_symbolic first)")
         self.grid_size, self.spline_order = full.grid_size, full.spline_order
         self.out_features = full.out_features
         if columns is None:
@@ -782,6 +784,8 @@ class TransposedShardedGIKANLayer(nn.Module):
         for l in conv.nn.layers:
             if l.in_features % self.world or l.out_features % self.world:
                 raise ValueError("layer widths must be divisible by the world size")
+            if getattr(l, "_symbolic", None) is not None:
+                raise NotImplementedError("a KANLinear with fixed symbolic edges cannot be sharded (unfix_symbolic first)")
         import copy
         self.layers = nn.ModuleList(copy.deepcopy(l) for l in conv.nn.layers)      # replicated parameters
         self._flat_pending = None          # (engine run id, gradients as they stood when that backward pass reached the module)

@@ -5,8 +5,13 @@ pykan's ``suggest_symbolic`` / ``fit_params`` for every edge of a layer at once:
 ``suggest_symbolic`` methods sample their edge functions on the rows they are given (``edge_curves``) and rank the functions per
 edge; ``suggest_symbolic(model, ...)`` does so for every eligible layer of a model on the input it sees in one forward.
 
-Not here: replacing an edge by its formula in the forward (pykan's ``fix_symbolic``), pruning, sympy expressions, gradients
-through the fit.
+Acting on a fit: ``KANLinear.fix_symbolic`` puts a formula into the layer's forward (``ops.symbolic_edges``,
+``csrc/symbolic_edges.hip``) with its four numbers trainable, ``"0"`` switches a dead edge off, ``auto_symbolic`` does both for a
+whole model from one ``suggest_symbolic`` walk, ``KANLinear.symbolic_formula`` reads an output off as text.
+
+Not here: fixed edges in a ``FastKANLayer``, in the sharded / RCCL layers or under ``torch.compile`` (a layer with fixed edges raises
+there), pruning whole nodes (which changes shapes), pykan's singularity-protected functions (the library is the plain one: ``sqrt``
+/ ``log`` outside their domain and ``1/x`` at 0 give what IEEE gives), sympy expressions, gradients through the fit.
 """
 from __future__ import annotations
 
@@ -42,6 +47,28 @@ SYMBOLIC_LIB = {
 assert tuple(SYMBOLIC_LIB) == ops.SYMBOLIC_FUNCTIONS and all(v[0] == k for k, v in enumerate(SYMBOLIC_LIB.values()))
 
 
+def format_edge(name: str, a: float, b: float, c: float, d: float, digits: int = 4, var: str = "x") -> str:
+    """``c*f(a*var + b) + d`` as text (``SymbolicSuggestion.formula``, ``KANLinear.symbolic_formula``)"""
+    num = lambda v: f"{abs(v):.{int(digits)}g}"
+    sign = lambda v: "-" if (v < 0 or (v == 0 and str(v).startswith("-"))) else "+"
+    arg = f"{'-' if sign(a) == '-' else ''}{num(a)}*{var} {sign(b)} {num(b)}"
+    body = SYMBOLIC_LIB[name][2].format(arg)
+    return f"{'-' if sign(c) == '-' else ''}{num(c)}*{body} {sign(d)} {num(d)}"
+
+
+def fixed_edge_values(x: torch.Tensor, triples, affine: torch.Tensor) -> torch.Tensor:
+    """``[N, E]``: ``c f(a x[:, i] + b) + d`` of the fixed edges ``triples = (o, i, function id)`` in torch ops -- the views of a layer
+    with fixed edges (``edge_l1``, ``edge_curves``) and the tests' restatement; the forward itself runs ``ops.symbolic_edges``"""
+    cols = torch.tensor([i for _, i, _ in triples], dtype=torch.int64, device=x.device)
+    t = affine[:, 0] * x.index_select(1, cols) + affine[:, 1]
+    fn_of = [v[1] for v in SYMBOLIC_LIB.values()]
+    out = torch.zeros_like(t)
+    for fid in sorted({f for _, _, f in triples}):
+        at = torch.tensor([e for e, (_, _, f) in enumerate(triples) if f == fid], dtype=torch.int64, device=x.device)
+        out = out.index_copy(1, at, fn_of[fid](t.index_select(1, at)))
+    return affine[:, 2] * out + affine[:, 3]
+
+
 class SymbolicSuggestion:
     """The ``topk`` best functions of every edge of one layer, ranked by ``r2`` (ties: the lower library id first).
 
@@ -68,11 +95,7 @@ class SymbolicSuggestion:
         """``c*f(a*x + b) + d`` of edge ``(o, i)`` as text, e.g. ``0.731*sin(3.1*x + 0.4) - 0.2``: numbers with ``digits`` significant
         digits (9 reproduces the fp32 parameters exactly).  The function names are numpy's, plus ``silu(t) = t / (1 + exp(-t))``."""
         a, b, c, d = (float(v) for v in self.params[rank, o, i].tolist())
-        num = lambda v: f"{abs(v):.{int(digits)}g}"
-        sign = lambda v: "-" if (v < 0 or (v == 0 and str(v).startswith("-"))) else "+"
-        arg = f"{'-' if sign(a) == '-' else ''}{num(a)}*x {sign(b)} {num(b)}"
-        body = SYMBOLIC_LIB[self.names[rank][o][i]][2].format(arg)
-        return f"{'-' if sign(c) == '-' else ''}{num(c)}*{body} {sign(d)} {num(d)}"
+        return format_edge(self.names[rank][o][i], a, b, c, d, digits=digits)
 
     @torch.no_grad()
     def curves(self, points: torch.Tensor, rank: int = 0) -> torch.Tensor:
@@ -183,3 +206,38 @@ def suggest_symbolic(model: torch.nn.Module, *args, functions: Optional[Sequence
         if keep_inputs:
             out[name].input = x
     return out
+
+
+def auto_symbolic(model: torch.nn.Module, *args, r2_threshold: float, dead_threshold: float, functions: Optional[Sequence[str]] = None,
+                  max_rows: int = 4096, search: Optional[dict] = None, **kwargs) -> Dict[str, list]:
+    """Fix what a model's fits allow (pykan's ``auto_symbolic``): ONE ``suggest_symbolic(model, *args, functions=..., topk=1, ...)``
+    walk, then per eligible ``KANLinear`` (spline order <= 4) and per edge that is still a spline: ``edge_l1 < dead_threshold`` -> fixed
+    to ``"0"``; else the rank-0 function when its ``r2 >= r2_threshold``, with the suggestion's parameters (no second fit); else left
+    as it is.  Returns ``{layer name: [(o, i, name, r2)]}`` of what was fixed (``r2`` of a ``"0"`` edge: ``None``).  Both thresholds are
+    the caller's to choose.  Every touched layer gets a NEW ``symbolic_affine`` Parameter: rebuild the optimizer."""
+    from .ekan import KANLinear
+    found = suggest_symbolic(model, *args, functions=functions, topk=1, max_rows=max_rows, search=search, **kwargs)
+    layers = dict(model.named_modules())
+    report: Dict[str, list] = {}
+    for name, sug in found.items():
+        layer = layers[name]
+        if not isinstance(layer, KANLinear):
+            continue
+        l1, r2, params = sug.edge_l1.cpu(), sug.r2[0].cpu(), sug.params[0].cpu()
+        fixed = layer._fixed_state()
+        done = []
+        for o in range(layer.out_features):
+            for i in range(layer.in_features):
+                if (o, i) in fixed:
+                    continue
+                if float(l1[o, i]) < dead_threshold:
+                    fixed[(o, i)] = ("0", None)
+                    done.append((o, i, "0", None))
+                elif float(r2[o, i]) >= r2_threshold:
+                    fn = sug.names[0][o][i]
+                    fixed[(o, i)] = (fn, params[o, i].clone())
+                    done.append((o, i, fn, float(r2[o, i])))
+        if done:
+            layer._set_fixed(fixed)
+        report[name] = done
+    return report

@@ -48,6 +48,7 @@ HOT = [
     (r"batch_assemble_kernel", 0, 0),                  # the loader's one launch per mini-batch
     (r"linear_gemm_kernel<|linear_dw_reduce_kernel", 0, 0),   # the dense layer of the MLP baselines
     (r"sym_shared_kernel<|sym_zoom_kernel<", 0, 0),    # the symbolic-fit search: 19 functions x (two output widths of the shared pass, the zoom pass)
+    (r"se_fwd_kernel<|se_bwd_kernel<", 0, 0),          # fixed symbolic edges: a 19-way scalar switch around the transcendentals
     (r"attention_", 0, 0),                             # dense attention: up to 4 x 32 row registers per lane at head_dim 128
 ]
 
