@@ -55,7 +55,7 @@ extern "C" {
 #define KAGNN_DTYPE_F32 0
 #define KAGNN_DTYPE_BF16 1
 
-int kagnn_version(void);          /* 280 = 279 + kagnn_symbolic_edges_plan (+ _bytes), kagnn_symbolic_edges_fwd, kagnn_symbolic_edges_bwd (+ _workspace_bytes); 279 = 278 + kagnn_symbolic_fit (+ _workspace_bytes); 278 = 277 + kagnn_edge_keys_build (+ _workspace_bytes), kagnn_negative_sample, kagnn_bce_logits_fwd / _bwd, kagnn_link_rank (+ _workspace_bytes); 277 = 276 + kagnn_neighbor_sample_mark, kagnn_edge_subgraph_count, kagnn_edge_subgraph_fill; 276 = 275 + kagnn_k_hop_mark, kagnn_subgraph_count, kagnn_subgraph_fill (+ kagnn_subgraph_workspace_bytes); 273 = 272 with kagnn_kan_grid_refit on kagnn_kan_grid_resize's kernels (up to 46 coefficients; its bits and its workspace size change); 272 = 271 + kagnn_kan_grid_resize (+ _workspace_bytes); 271 = 270 + kagnn_attention_fwd, kagnn_attention_bwd (+ _workspace_bytes); 270 = 269 + kagnn_fastkan_edge_abs_sum, kagnn_fastkan_edge_abs_sum_bwd (+ _workspace_bytes), kagnn_fastkan_edge_curves; 269 = 268 + kagnn_kan_edge_abs_sum, kagnn_kan_edge_abs_sum_bwd (+ _workspace_bytes), kagnn_kan_edge_curves; 268 = 267 + spline orders 5..KAGNN_MAX_SPLINE_ORDER in the per-operation KANLinear calls (no new entry point); 267 = 266 + kagnn_linear_fwd, kagnn_linear_bwd_input, kagnn_linear_bwd_weight (+ _workspace_bytes); 266 = 265 + kagnn_l1_loss_meter_fwd, kagnn_regression_epoch_update; 265 = 264 + kagnn_node_eval, kagnn_early_stop_update, kagnn_copy_if; 264 = 263 + kagnn_degree_one_hot, kagnn_nll_loss_fwd / _bwd; 263 = 262 + kagnn_batch_assemble; 262 = 261 - the fields edge_src, edge_dst, csr_flags of kagnn_kagin_model_t; 261 = 260 + kagnn_fastkan_fwd_stats_in_kernel; 260 = round 6: + the feature-sharded FastKAN entry points kagnn_fastkan_row_moments .. _shard_bwd_finish, + kagnn_kagin_model_*; 250 = 240 + KAGNN_PREC_HALF; 240 = 230 + kagnn_gin_kan_layer_bwd_bn_sums; 230 = 220 + the *_affine entry points of a folded BatchNorm1d; 220 = 210 + the stage timer) */
+int kagnn_version(void);          /* 281 = 280 + kagnn_kan_edge_moments (+ _workspace_bytes); 280 = 279 + kagnn_symbolic_edges_plan (+ _bytes), kagnn_symbolic_edges_fwd, kagnn_symbolic_edges_bwd (+ _workspace_bytes); 279 = 278 + kagnn_symbolic_fit (+ _workspace_bytes); 278 = 277 + kagnn_edge_keys_build (+ _workspace_bytes), kagnn_negative_sample, kagnn_bce_logits_fwd / _bwd, kagnn_link_rank (+ _workspace_bytes); 277 = 276 + kagnn_neighbor_sample_mark, kagnn_edge_subgraph_count, kagnn_edge_subgraph_fill; 276 = 275 + kagnn_k_hop_mark, kagnn_subgraph_count, kagnn_subgraph_fill (+ kagnn_subgraph_workspace_bytes); 273 = 272 with kagnn_kan_grid_refit on kagnn_kan_grid_resize's kernels (up to 46 coefficients; its bits and its workspace size change); 272 = 271 + kagnn_kan_grid_resize (+ _workspace_bytes); 271 = 270 + kagnn_attention_fwd, kagnn_attention_bwd (+ _workspace_bytes); 270 = 269 + kagnn_fastkan_edge_abs_sum, kagnn_fastkan_edge_abs_sum_bwd (+ _workspace_bytes), kagnn_fastkan_edge_curves; 269 = 268 + kagnn_kan_edge_abs_sum, kagnn_kan_edge_abs_sum_bwd (+ _workspace_bytes), kagnn_kan_edge_curves; 268 = 267 + spline orders 5..KAGNN_MAX_SPLINE_ORDER in the per-operation KANLinear calls (no new entry point); 267 = 266 + kagnn_linear_fwd, kagnn_linear_bwd_input, kagnn_linear_bwd_weight (+ _workspace_bytes); 266 = 265 + kagnn_l1_loss_meter_fwd, kagnn_regression_epoch_update; 265 = 264 + kagnn_node_eval, kagnn_early_stop_update, kagnn_copy_if; 264 = 263 + kagnn_degree_one_hot, kagnn_nll_loss_fwd / _bwd; 263 = 262 + kagnn_batch_assemble; 262 = 261 - the fields edge_src, edge_dst, csr_flags of kagnn_kagin_model_t; 261 = 260 + kagnn_fastkan_fwd_stats_in_kernel; 260 = round 6: + the feature-sharded FastKAN entry points kagnn_fastkan_row_moments .. _shard_bwd_finish, + kagnn_kagin_model_*; 250 = 240 + KAGNN_PREC_HALF; 240 = 230 + kagnn_gin_kan_layer_bwd_bn_sums; 230 = 220 + the *_affine entry points of a folded BatchNorm1d; 220 = 210 + the stage timer) */
 const char* kagnn_last_error(void);
 
 /* Stage timer -- a measurement aid, off by default (no reference counterpart: the reference times whole epochs with
@@ -708,6 +708,18 @@ int kagnn_kan_edge_curves(const float* t, int64_t ldt, int64_t num_points, const
                           int32_t in_features, int32_t out_features, int32_t grid_size, int32_t spline_order,
                           const float* base_weight, const float* spline_weight, const float* spline_scaler, float* phi,
                           void* stream);
+/* first and second moments of every edge function over the rows (the edge scale that attribution scores are built on):
+ *   mean[o*ld_mean + i] = (1/N) sum_n phi_{o,i}(x[n,i]),   m2[o*ld_m2 + i] = sum_n (phi_{o,i}(x[n,i]) - mean[o,i])^2
+ * m2 is the centred SUM of squares: the caller chooses the divisor, and results over a partition of the rows merge by the
+ * pairwise formula.  Accumulated about a pivot phi_{o,i}(x[0,i]) in fp32 within a row slab, merged over the slabs in fp64: an
+ * edge that sits on an offset keeps its scale.  Either output may be NULL, not both.  A non-finite x[n,i] makes column i of
+ * both NaN.  num_rows 0: zeros.                                                                                                 */
+int kagnn_kan_edge_moments_workspace_bytes(int64_t num_rows, int32_t in_features, int32_t out_features, int32_t grid_size,
+                                           int32_t spline_order, size_t* bytes_host);
+int kagnn_kan_edge_moments(const float* x, int64_t ldx, int64_t num_rows, const float* knots, int32_t per_feature_knots,
+                           int32_t in_features, int32_t out_features, int32_t grid_size, int32_t spline_order,
+                           const float* base_weight, const float* spline_weight, const float* spline_scaler, float* mean,
+                           int64_t ld_mean, float* m2, int64_t ld_m2, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * FastKAN layer.  Replaces FastKANLayer.forward (node_classification_clean/fastkan.py:76-85:

@@ -5,7 +5,8 @@ Host side: Python mirrors of the reference's ``nn.Module`` surface (``ekan``, ``
 C ABI of ``include/kagnn_hip.h``, reached through ``kagnn_amd.ops``.
 """
 from . import _lib, ops                                                          # noqa: F401
-from .ekan import KAN, KANLinear, collect_edge_l1, refine_grids                                # noqa: F401
+from .ekan import (KAN, KANLinear, Attribution, EdgeStats, PruneReport, apply_pruning, attribute, collect_edge_l1, prune,   # noqa: F401
+                   refine_grids)                             # noqa: F401
 from .fastkan import (AttentionWithFastKANTransform, FastKAN, FastKANLayer, RadialBasisFunction,   # noqa: F401
                       SplineLinear)
 from .models import (FASTKAGATConv, FASTKAGCNConv, FKANLayer, GFASTKAN_Nodes,        # noqa: F401

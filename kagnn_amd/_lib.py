@@ -169,6 +169,10 @@ _SIGNATURES = {
     # t ldt P knots per_feature in out G K bw sw sc phi stream
     "kagnn_kan_edge_curves": (c_int32, [_P, c_int64, c_int64, _P, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, _P,
                                         _P]),
+    "kagnn_kan_edge_moments_workspace_bytes": (c_int32, [c_int64, c_int32, c_int32, c_int32, c_int32, POINTER(c_size_t)]),
+    # x ldx N knots per_feature in out G K bw sw sc mean ld_mean m2 ld_m2 ws bytes stream
+    "kagnn_kan_edge_moments": (c_int32, [_P, c_int64, c_int64, _P, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, _P,
+                                         c_int64, _P, c_int64, _P, c_size_t, _P]),
     "kagnn_kan_grid_refit_workspace_bytes": (c_int32, [c_int64, c_int32, c_int32, c_int32, POINTER(c_size_t)]),
     "kagnn_kan_grid_refit": (c_int32, [_P, c_int64, c_int64, _P, _P, c_int32, c_int32, c_int32, c_int32, _P, _P, _P,
                                        _P, c_size_t, _P]),

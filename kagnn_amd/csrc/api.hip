@@ -84,7 +84,7 @@ using namespace kagnn;
 #pragma GCC visibility push(default)
 extern "C" {
 
-int kagnn_version(void) { return 280; }
+int kagnn_version(void) { return 281; }
 const char* kagnn_last_error(void) { return g_err; }
 
 int kagnn_stage_timer_enable(const char* only) {
@@ -1416,6 +1416,34 @@ int kagnn_kan_edge_curves(const float* t, int64_t ldt, int64_t P, const float* k
     if (P == 0) return KAGNN_OK;
     KAGNN_CHECK_ARG(t && knots && sw && phi, "null array");
     return kan_edge_curves(t, ldt, P, knots, per_feature_knots != 0, in, out, G, K, bw, sw, sc, phi, as_stream(stream));
+}
+
+int kagnn_kan_edge_moments_workspace_bytes(int64_t N, int32_t in, int32_t out, int32_t G, int32_t K, size_t* bytes) {
+    int rc = check_kan_dims(__func__, in, out, G, K, KAGNN_PREC_FP32);
+    if (rc) return rc;
+    KAGNN_CHECK_ARG(bytes != nullptr && N >= 0, "null output or negative row count");
+    *bytes = kan_edge_moments_ws_bytes(N, in, out);
+    return KAGNN_OK;
+}
+
+int kagnn_kan_edge_moments(const float* x, int64_t ldx, int64_t N, const float* knots, int32_t per_feature_knots, int32_t in,
+                           int32_t out, int32_t G, int32_t K, const float* bw, const float* sw, const float* sc, float* mean,
+                           int64_t ld_mean, float* m2, int64_t ld_m2, void* ws, size_t ws_bytes, void* stream) {
+    KAGNN_STAGE(stream);
+    int rc = check_kan_dims(__func__, in, out, G, K, KAGNN_PREC_FP32);
+    if (rc) return rc;
+    KAGNN_CHECK_ARG(N >= 0 && ldx >= in && (!mean || ld_mean >= in) && (!m2 || ld_m2 >= in), "bad shape");
+    KAGNN_CHECK_ARG(per_feature_knots == 0 || per_feature_knots == 1, "per_feature_knots must be 0 or 1");
+    KAGNN_CHECK_ARG(mean != nullptr || m2 != nullptr, "mean and m2 are both null");
+    if (N == 0) {                                   // no rows: zeros, no kernel
+        const size_t w = (size_t)in * sizeof(float);
+        if (mean) KAGNN_HIP(hipMemset2DAsync(mean, (size_t)ld_mean * sizeof(float), 0, w, (size_t)out, as_stream(stream)));
+        if (m2) KAGNN_HIP(hipMemset2DAsync(m2, (size_t)ld_m2 * sizeof(float), 0, w, (size_t)out, as_stream(stream)));
+        return KAGNN_OK;
+    }
+    KAGNN_CHECK_ARG(x && knots && sw && ws, "null array");          // base_weight / spline_scaler NULL: the layer has none
+    return kan_edge_moments(x, ldx, N, knots, per_feature_knots != 0, in, out, G, K, bw, sw, sc, mean, ld_mean, m2, ld_m2, (float*)ws,
+                            ws_bytes, as_stream(stream));
 }
 
 // ---------------------------------------------------------------- symbolic fits of edge functions (symbolic.hip)

@@ -342,6 +342,10 @@ int kan_edge_abs_sum_bwd(const float* x, long ldx, long N, const float* knots, b
                          float* gx, long ldgx, float* ws, size_t ws_bytes, hipStream_t st);
 int kan_edge_curves(const float* t, long ldt, long P, const float* knots, bool pf, int in, int out, int G, int K, const float* bw,
                     const float* sw, const float* sc, float* phi, hipStream_t st);
+size_t kan_edge_moments_ws_bytes(long N, int in, int out);
+int kan_edge_moments(const float* x, long ldx, long N, const float* knots, bool pf, int in, int out, int G, int K, const float* bw,
+                     const float* sw, const float* sc, float* mean, long ld_mean, float* m2, long ld_m2, float* ws, size_t ws_bytes,
+                     hipStream_t st);
 
 // ---- p2p.hip
 int p2p_reduce_scatter(const float* const* parts, int P, int rank, long N, int out, long ld, float* y, long ldy, hipStream_t st);

@@ -14,7 +14,8 @@ from __future__ import annotations
 import contextlib
 import math
 import os
-from typing import Dict, List, Optional, Sequence
+from dataclasses import dataclass, field
+from typing import Dict, List, NamedTuple, Optional, Sequence
 
 import torch
 from torch import nn
@@ -22,7 +23,37 @@ from torch import nn
 from . import ops
 
 
+_FIXED_CHUNK_ELEMENTS = 1 << 22      # [rows, fixed edges] values per chunk when a layer's fixed symbolic edges are evaluated in torch ops
 _PACK_CHAIN = True      # all layers of a chain packed in one launch (a module attribute for the bitwise A/B tests, no longer an environment switch)
+
+
+class EdgeStats(NamedTuple):
+    """``KANLinear.edge_stats``: mean and standard deviation of every edge function over the rows, both ``[out, in]``"""
+    mean: torch.Tensor
+    std: torch.Tensor
+
+
+@dataclass
+class Attribution:
+    """``KAN.attribute``: per layer ``edge_std [out_l, in_l]`` (the edge functions' standard deviation on the layer's input),
+    ``out_std [out_l]`` (the layer outputs' standard deviation), ``edge_scores [out_l, in_l]``; ``node_scores``: one vector per width,
+    ``L + 1`` of them, the first being the chain's input features.  ``input``: the chain's input when the caller asked to keep it."""
+    edge_std: List[torch.Tensor]
+    out_std: List[torch.Tensor]
+    edge_scores: List[torch.Tensor]
+    node_scores: List[torch.Tensor]
+    input: Optional[torch.Tensor] = None
+
+    @property
+    def input_scores(self) -> torch.Tensor:
+        return self.node_scores[0]
+
+
+@dataclass
+class PruneReport:
+    """``kagnn_amd.prune``: per chain name ``{"keep": [index tensor per interior width], "edges": [pruned (o, i) rows per layer],
+    "widths_before": [...], "widths_after": [...]}`` -- host data; ``apply_pruning`` replays it on a fresh model"""
+    chains: Dict[str, dict] = field(default_factory=dict)
 
 
 def _init_bases(points: torch.Tensor, knots: torch.Tensor, order: int) -> torch.Tensor:
@@ -347,7 +378,7 @@ class KANLinear(nn.Module):
             idx = self.symbolic_index.long()
             if idx.size(0) == 0 or x.size(0) == 0:
                 return mag
-            step = max(1, (1 << 22) // idx.size(0))
+            step = max(1, _FIXED_CHUNK_ELEMENTS // idx.size(0))
             total = sum(fixed_edge_values(x[r:r + step], self._symbolic.triples, self.symbolic_affine).abs().sum(0)
                         for r in range(0, x.size(0), step))
             return mag.index_put((idx[:, 0], idx[:, 1]), total / rows)
@@ -367,6 +398,67 @@ class KANLinear(nn.Module):
                 phi[:, idx[:, 0], idx[:, 1]] = fixed_edge_values(pts, self._symbolic.triples, self.symbolic_affine.detach())
             return phi
         return ops.kan_edge_curves(points, *self._edge_args())
+
+    @torch.no_grad()
+    def edge_stats(self, x: torch.Tensor, unbiased: bool = True) -> EdgeStats:
+        """``EdgeStats(mean, std)``, both ``[out, in]``: mean and standard deviation of ``phi_{o,i}(x[n,i])`` over the rows of ``x`` -- the
+        centred scale of every edge that attribution scores are built on (pykan's ``edge_actscale``).  ``std = sqrt(m2 / (N - 1))`` as
+        ``torch.std`` (``unbiased=False``: ``/ N``); one row gives NaN under ``unbiased=True``, as torch does.  One fused kernel
+        (``ops.kan_edge_moments``): no [N, out, in] tensor.  A layer with fixed symbolic edges is described as it now is: the fixed
+        functions' own moments, ``"0"`` edges exactly 0.  Not differentiable.  Spline orders 1..4."""
+        assert x.dim() == 2 and x.size(1) == self.in_features
+        x = x.detach() if x.dtype == torch.float32 else x.detach().float()
+        n = x.size(0)
+        if self._symbolic is None:
+            mean, m2 = ops.kan_edge_moments(x, *self._edge_args())
+        else:
+            from .symbolic import fixed_edge_values
+            mean, m2 = ops.kan_edge_moments(x, *self._kept_operands(), *self._edge_args()[3:])
+            idx = self.symbolic_index.long()
+            if idx.size(0) and n:
+                step = max(1, _FIXED_CHUNK_ELEMENTS // idx.size(0))
+                count, f_mean, f_m2 = 0, 0.0, 0.0
+                for r in range(0, n, step):           # one evaluation per row chunk, the chunks merged pairwise in fp64
+                    v = fixed_edge_values(x[r:r + step], self._symbolic.triples, self.symbolic_affine.detach()).double()
+                    c_mean = v.mean(0)
+                    delta = c_mean - f_mean
+                    total = count + v.size(0)
+                    f_m2 = f_m2 + (v - c_mean).square().sum(0) + delta * delta * (count * v.size(0) / total)
+                    f_mean = f_mean + delta * (v.size(0) / total)
+                    count = total
+                mean = mean.index_put((idx[:, 0], idx[:, 1]), f_mean.float())
+                m2 = m2.index_put((idx[:, 0], idx[:, 1]), f_m2.float())
+        return EdgeStats(mean, (m2 / (n - 1 if unbiased else n)).sqrt())
+
+    @torch.no_grad()
+    def _keep(self, rows: Optional[torch.Tensor], cols: Optional[torch.Tensor]) -> None:
+        """keep these outputs (``rows``) / inputs (``cols``), sorted int64 CPU index tensors or None: NEW Parameters and grid buffer of
+        the smaller shapes; fixed edges on a removed row or column are dropped, the rest re-indexed"""
+        fixed = self._fixed_state()
+        dev = self.base_weight.device
+        names = ("base_weight", "spline_weight") + (("spline_scaler",) if self.enable_standalone_scale_spline else ())
+        for name in names:
+            old = getattr(self, name)
+            v = old.detach()
+            if rows is not None:
+                v = v.index_select(0, rows.to(dev))
+            if cols is not None:
+                v = v.index_select(1, cols.to(dev))
+            setattr(self, name, nn.Parameter(v.contiguous(), requires_grad=old.requires_grad))
+        if cols is not None:
+            self.grid = self.grid.index_select(0, cols.to(dev)).contiguous()       # (it may hold per-feature knot rows)
+        row_of = {int(o): j for j, o in enumerate(range(self.out_features) if rows is None else rows.tolist())}
+        col_of = {int(i): j for j, i in enumerate(range(self.in_features) if cols is None else cols.tolist())}
+        self.out_features, self.in_features = len(row_of), len(col_of)
+        self._set_fixed({(row_of[o], col_of[i]): v for (o, i), v in fixed.items() if o in row_of and i in col_of})
+        self.refresh_knots()
+
+    def _switch_off(self, pairs) -> None:
+        """``fix_symbolic(o, i, "0")`` for every ``(o, i)`` of ``pairs`` at once: one new symbolic state"""
+        fixed = self._fixed_state()
+        for o, i in pairs:
+            fixed.setdefault(self._check_edge(o, i), ("0", None))
+        self._set_fixed(fixed)
 
     # ------------------------------------------------------------------ fixed symbolic edges (pykan's fix_symbolic)
     def _drop_symbolic_state(self) -> None:
@@ -570,6 +662,110 @@ class KAN(nn.Module):
         from .symbolic import suggest_chain
         return suggest_chain(self, x, **kw)
 
+    # ------------------------------------------------------------------ attribution and pruning (pykan's attribute / prune)
+    def attribute(self, x: torch.Tensor, out_scores=None) -> Attribution:
+        """Which inputs, hidden units and edges the chain uses on the rows ``x`` (pykan's ``attribute``, without multiplication nodes).
+        One eval-style walk under ``no_grad``, every layer on its own input: ``E_l = layer_l.edge_stats(x_l).std`` and ``s_l``, the
+        column standard deviation of ``layer_l(x_l)``; then from ``node_scores[L] = out_scores`` (default: ones) backwards
+        ``edge_scores[l][o,i] = E_l[o,i] node_scores[l+1][o] / (s_l[o] + 1e-4)``, ``node_scores[l][i] = sum_o edge_scores[l][o,i]``.
+        Everything stays on the device.  Spline orders 1..4."""
+        return _attribute_layers(list(self.layers), x, out_scores)
+
+    @torch.no_grad()
+    def keep_nodes(self, keep) -> None:
+        """Shrink the chain's INTERIOR widths: ``keep[l]`` holds the sorted indices of the units of width ``l + 1`` that stay (one
+        entry per interior width; the chain's input and output widths never change, so it keeps fitting its neighbours).  Layer ``l``
+        keeps those rows of its parameters, layer ``l + 1`` those columns and those rows of its grid buffer; ``in_features`` /
+        ``out_features`` follow; fixed symbolic edges on a removed unit are dropped, the others re-indexed.  Every touched layer gets
+        NEW Parameters: rebuild the optimizer, as after ``refine``.  An empty keep list raises ``ValueError``."""
+        layers = list(self.layers)
+        if len(keep) != len(layers) - 1:
+            raise ValueError(f"keep_nodes: one index list per interior width, {len(layers) - 1} of them (got {len(keep)})")
+        lists = []
+        for l, k in enumerate(keep):
+            k = torch.as_tensor(k, dtype=torch.int64).reshape(-1).cpu()
+            width = layers[l].out_features
+            if k.numel() == 0:
+                raise ValueError(f"keep_nodes: nothing is kept of interior width {l + 1}")
+            if int(k[0]) < 0 or int(k[-1]) >= width or bool((k[1:] <= k[:-1]).any()):
+                raise ValueError(f"keep_nodes: keep[{l}] must be sorted, without repeats, within [0, {width})")
+            lists.append(k)
+        for l, k in enumerate(lists):
+            if k.numel() == layers[l].out_features:
+                continue
+            layers[l]._keep(k, None)
+            layers[l + 1]._keep(None, k)
+        ops._KNOTS_EQUAL.clear()
+
+    def prune_nodes(self, x: torch.Tensor, threshold: float = 1e-2) -> List[torch.Tensor]:
+        """``attribute(x)``, then ``keep_nodes`` of the interior units whose score exceeds ``threshold`` (of a width where none does:
+        the one of highest score).  Returns the keep lists (int64, on the host).  New Parameters: rebuild the optimizer."""
+        keep = _keep_lists(self.attribute(x), threshold)
+        self.keep_nodes(keep)
+        return keep
+
+    def prune_edges(self, x: torch.Tensor, threshold: float = 3e-2) -> List[torch.Tensor]:
+        """``attribute(x)``, then every spline edge with ``edge_scores[l][o,i] < threshold`` is switched off as
+        ``fix_symbolic(o, i, "0")`` does (its parameters stay and get exactly zero gradient); already fixed edges are left alone.
+        Returns the pruned ``(o, i)`` rows per layer (int64 ``[P_l, 2]``, on the host).  New ``symbolic_affine`` Parameters: rebuild
+        the optimizer."""
+        return _switch_off_edges(list(self.layers), self.attribute(x), threshold)
+
+    def prune(self, x: torch.Tensor, node_threshold: float = 1e-2, edge_threshold: float = 3e-2):
+        """``prune_nodes``, then ``prune_edges`` on a fresh attribution of the shrunk chain (pykan's ``prune``): ``(keep lists,
+        pruned edges)``"""
+        keep = self.prune_nodes(x, node_threshold)
+        return keep, self.prune_edges(x, edge_threshold)
+
+
+@torch.no_grad()
+def _attribute_layers(layers, x: torch.Tensor, out_scores=None) -> Attribution:
+    for layer in layers:
+        if ops.high_order(layer.spline_order):
+            raise NotImplementedError(f"attribute: spline_order must be in 1..{ops.FUSED_MAX_SPLINE_ORDER} (got {layer.spline_order}); "
+                                      "the per-edge activation kernels do not cover the orders above")
+    x = x.detach() if x.dtype == torch.float32 else x.detach().float()
+    edge_std, out_std = [], []
+    for layer in layers:
+        edge_std.append(layer.edge_stats(x).std)
+        x = layer._forward(x)                     # (not a forward of the model: nothing records it)
+        out_std.append(torch.var_mean(x, dim=0)[0].sqrt())
+    score = torch.ones_like(out_std[-1]) if out_scores is None else \
+        torch.as_tensor(out_scores, dtype=torch.float32, device=x.device).reshape(out_std[-1].shape)
+    node, edge = [score], []
+    for e, s in zip(reversed(edge_std), reversed(out_std)):
+        edge.insert(0, e * (node[0] / (s + 1e-4)).unsqueeze(1))
+        node.insert(0, edge[0].sum(0))
+    return Attribution(edge_std, out_std, edge, node)
+
+
+def _keep_lists(att: Attribution, threshold: float) -> List[torch.Tensor]:
+    """per interior width the units with ``node_scores > threshold`` (none: the best one); one read-back of the masks"""
+    masks = []
+    for score in att.node_scores[1:-1]:
+        m = score > threshold
+        best = torch.zeros_like(m).index_fill_(0, score.nan_to_num(nan=-math.inf).argmax().reshape(1), True)
+        masks.append(torch.where(m.any(), m, best))
+    if not masks:
+        return []
+    host = torch.cat(masks).cpu()
+    return [m.nonzero().reshape(-1) for m in host.split([m.numel() for m in masks])]
+
+
+def _switch_off_edges(layers, att: Attribution, threshold: float) -> List[torch.Tensor]:
+    masks = []
+    for layer, score in zip(layers, att.edge_scores):
+        m = score < threshold
+        masks.append((m if layer._symbolic is None else m & (layer.symbolic_keep != 0)).reshape(-1))
+    host = torch.cat(masks).cpu()                          # one read-back
+    out = []
+    for layer, m in zip(layers, host.split([m.numel() for m in masks])):
+        pairs = m.reshape(layer.out_features, layer.in_features).nonzero()
+        if pairs.size(0):
+            layer._switch_off(pairs.tolist())
+        out.append(pairs)
+    return out
+
 
 def _collect(layer: KANLinear, x: torch.Tensor) -> None:
     for entry in ops._edge_collectors():
@@ -673,3 +869,103 @@ def refine_grids(model: nn.Module, grid_size: int, *args, adaptive: bool = False
     report = dict(walk.report)
     report["skipped"] = skipped + [n for n in names.values() if n not in walk.report]
     return report
+
+
+def _chains(model: nn.Module):
+    """``[(name, the KAN or None, layers)]`` in ``named_modules()`` order: every ``KAN`` under ``model``, and every ``KANLinear`` outside any
+    ``KAN`` as a chain of one"""
+    inside = {id(l) for m in model.modules() if isinstance(m, KAN) for l in m.layers}
+    out = []
+    for n, m in model.named_modules():
+        if isinstance(m, KAN):
+            out.append((n, m, list(m.layers)))
+        elif isinstance(m, KANLinear) and id(m) not in inside:
+            out.append((n, None, [m]))
+    return out
+
+
+def _forget_shapes(model: nn.Module) -> None:
+    # everything derived from the old shapes or parameters (as after refine_grids)
+    ops._KNOTS_EQUAL.clear()
+    for m in model.modules():
+        m.__dict__.pop("_kagnn_model_call_template", None)
+
+
+def attribute(model: nn.Module, *args, keep_inputs: bool = False, **kwargs) -> Dict[str, Attribution]:
+    """Attribution scores for a whole model: ONE forward ``model(*args, **kwargs)`` under ``no_grad`` in eval mode (no dropout, no
+    running statistics move; the ``training`` flags are restored) inside a visible-inputs block (``ops.layer_inputs_visible``: the
+    fused layer / stack / model routes take their composed per-layer form for this one forward and are back afterwards), during
+    which every chain records the input it sees (the latest call wins).  Then ``{chain name: chain.attribute(that input)}`` for every
+    ``ekan.KAN`` under ``model``; a ``KANLinear`` outside any ``KAN`` counts as a chain of one.  Every chain's own outputs are scored 1:
+    attribution does NOT cross an aggregation, a BatchNorm or any other module between two chains -- the scores say what each chain
+    uses of ITS input, not what the model uses of the graph's features.  ``keep_inputs``: every ``Attribution.input`` holds the
+    recorded input.  Spline orders 1..4."""
+    chains = _chains(model)
+    first = {id(layers[0]): n for n, _, layers in chains}
+    seen: Dict[str, torch.Tensor] = {}
+
+    def visit(name, layer, x, *_):
+        seen[name] = x.detach()
+
+    entry = (first, {}, visit)
+    flags = [(m, m.training) for m in model.modules()]
+    model.eval()
+    active = ops._edge_collectors()
+    active.append(entry)
+    try:
+        with torch.no_grad():
+            model(*args, **kwargs)
+    finally:
+        active.remove(entry)
+        for m, flag in flags:
+            m.training = flag
+    out = {}
+    for name, _, layers in chains:
+        if name in seen:
+            out[name] = _attribute_layers(layers, seen[name])
+            if keep_inputs:
+                out[name].input = seen[name]
+    return out
+
+
+def prune(model: nn.Module, *args, node_threshold: float = 1e-2, edge_threshold: float = 3e-2, **kwargs) -> PruneReport:
+    """Prune every chain of a model (``KAN.prune`` chain by chain, on the inputs the chains see in the model): one
+    ``attribute(model, ...)`` pass decides the hidden units of every ``KAN`` (``KAN.keep_nodes``), a second pass on the shrunk model
+    decides the edges (switched off as ``fix_symbolic(o, i, "0")``).  Chains' outer widths never change.  Returns a ``PruneReport``;
+    the touched layers have NEW Parameters: rebuild the optimizer.  A checkpoint of the pruned model loads into a fresh model of the
+    original sizes after ``apply_pruning(fresh, report)``."""
+    report = PruneReport()
+    chains = _chains(model)
+    found = attribute(model, *args, **kwargs)
+    for name, chain, layers in chains:
+        if name not in found:
+            continue
+        before = [layers[0].in_features] + [l.out_features for l in layers]
+        keep = _keep_lists(found[name], node_threshold)
+        if chain is not None:
+            chain.keep_nodes(keep)
+        report.chains[name] = {"keep": keep, "edges": [], "widths_before": before,
+                               "widths_after": [layers[0].in_features] + [l.out_features for l in layers]}
+    _forget_shapes(model)
+    found = attribute(model, *args, **kwargs)
+    for name, _, layers in chains:
+        if name in found:
+            report.chains[name]["edges"] = _switch_off_edges(layers, found[name], edge_threshold)
+    _forget_shapes(model)
+    return report
+
+
+def apply_pruning(model: nn.Module, report: PruneReport) -> None:
+    """Replay a ``PruneReport`` on a fresh model of the ORIGINAL sizes: the keep lists and the ``"0"`` edges, so that
+    ``model.load_state_dict(pruned.state_dict())`` then succeeds (``load_state_dict`` itself is unchanged)."""
+    chains = {n: (chain, layers) for n, chain, layers in _chains(model)}
+    for name, entry in report.chains.items():
+        if name not in chains:
+            raise KeyError(f"apply_pruning: the model has no chain {name!r}")
+        chain, layers = chains[name]
+        if chain is not None:
+            chain.keep_nodes(entry["keep"])
+        for layer, pairs in zip(layers, entry["edges"]):
+            if len(pairs):
+                layer._switch_off(torch.as_tensor(pairs).reshape(-1, 2).tolist())
+    _forget_shapes(model)

@@ -2241,6 +2241,29 @@ def kan_edge_abs_sum(x, base_weight, spline_weight, spline_scaler, knots, grid_s
     return _KanEdgeAbsSumFn.apply(x, base_weight, spline_weight, spline_scaler, knots, int(grid_size), int(spline_order))
 
 
+def kan_edge_moments(x, base_weight, spline_weight, spline_scaler, knots, grid_size: int, spline_order: int, out=None):
+    """``(mean, m2)``, both ``[out, in]``: ``mean[o,i] = mean_n phi_{o,i}(x[n,i])`` and the centred sum of squares
+    ``m2[o,i] = sum_n (phi_{o,i}(x[n,i]) - mean[o,i])^2`` -- a SUM, so the caller chooses the divisor, and results over a partition
+    of the rows merge pairwise.  Operands as for ``kan_edge_abs_sum``.  Accumulated about a pivot row (an edge on a large offset
+    keeps its scale); exact fp32; the same inputs give the same bits.  Not differentiable.  ``out = (mean, m2)``: row-strided
+    [out, in] views to write into."""
+    bw, sw, sc, kn, pf, fin, fout = _edge_operands("kan_edge_moments", x, base_weight, spline_weight, spline_scaler, knots, grid_size,
+                                                   spline_order)
+    x = _rows(x.detach())
+    if x.size(1) != fin:
+        raise AssertionError("x must be [rows, in_features]")
+    n, G, K = x.size(0), int(grid_size), int(spline_order)
+    mean, m2 = out if out is not None else (torch.empty((fout, fin), dtype=torch.float32, device=x.device) for _ in range(2))
+    for t in (mean, m2):                          # (the kernel writes [out, in] blocks with a row stride and unit column stride)
+        if t.shape != (fout, fin) or t.dtype != torch.float32 or t.device != x.device or t.stride(1) != 1 or (fout > 1 and t.stride(0) < fin):
+            raise AssertionError("kan_edge_moments: out must be two fp32 [out_features, in_features] views on x's device with unit column stride")
+    with _device_of(x):
+        ws = _ws(_sizes("kagnn_kan_edge_moments_workspace_bytes", n, fin, fout, G, K), x.device)
+        _call("kagnn_kan_edge_moments", _ptr(x), _ld(x), n, _ptr(kn), pf, fin, fout, G, K, _ptr(bw), _ptr(sw), _ptr(sc), _ptr(mean),
+              _ld(mean), _ptr(m2), _ld(m2), _ptr(ws), ws.numel(), _stream())
+    return mean, m2
+
+
 def kan_edge_curves(points, base_weight, spline_weight, spline_scaler, knots, grid_size: int, spline_order: int) -> torch.Tensor:
     """``phi[P, out, in]``: every edge function sampled at ``points`` -- ``[P]`` (the same abscissae for every input feature)
     or ``[P, in]``.  Not differentiable."""

@@ -49,6 +49,7 @@ HOT = [
     (r"linear_gemm_kernel<|linear_dw_reduce_kernel", 0, 0),   # the dense layer of the MLP baselines
     (r"sym_shared_kernel<|sym_zoom_kernel<", 0, 0),    # the symbolic-fit search: 19 functions x (two output widths of the shared pass, the zoom pass)
     (r"se_fwd_kernel<|se_bwd_kernel<", 0, 0),          # fixed symbolic edges: a 19-way scalar switch around the transcendentals
+    (r"kan_phi_moments_kernel<", 0, 0),                # attribution's edge moments: 2 x 32 accumulators per lane and pass (2 x 64 fit without scratch but leave one wave per SIMD)
     (r"attention_", 0, 0),                             # dense attention: up to 4 x 32 row registers per lane at head_dim 128
 ]
 
