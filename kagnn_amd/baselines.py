@@ -21,7 +21,7 @@ import torch.nn.functional as F
 
 from . import ops
 from .graph_models import AtomEncoder, BondEncoder, GINEKANLayer, _segment_ptr
-from .models import _AttentionConv, _NodeModel, _NormalisedConv, _SumAggregateConv, _has_hooks
+from .models import _AttentionConv, _NodeModel, _NormalisedConv, _SumAggregateConv
 from .norm import BatchNorm1d
 
 
@@ -38,7 +38,7 @@ class LinearReLU(nn.Sequential):
     tensor between them); anything else runs the plain sequential."""
 
     def forward(self, input: torch.Tensor) -> torch.Tensor:
-        if len(self) >= 2 and type(self[0]) is Linear and type(self[1]) is nn.ReLU and not _has_hooks(self[0]) and not _has_hooks(self[1]):
+        if len(self) >= 2 and type(self[0]) is Linear and type(self[1]) is nn.ReLU and ops._hook_free((self[0], self[1])):
             x = ops.linear(input, self[0].weight, self[0].bias, relu=True)
             for m in list(self)[2:]:
                 x = m(x)

@@ -233,16 +233,37 @@ class KANLinear(nn.Module):
         ``KAN.regularization_loss(x=)`` are not the model's forward)"""
         if self._symbolic is not None:
             return self._forward_fixed(x)
-        scaler = self.spline_scaler if self.enable_standalone_scale_spline else None
-        return ops.kan_linear(x, self.base_weight, self.spline_weight, scaler, self._knots(),
+        return ops.kan_linear(x, self.base_weight, self.spline_weight, self._scaler(), self._knots(),
                               self.grid_size, self.spline_order, self.precision, _packed)
+
+    def _scaler(self):
+        return self.spline_scaler if self.enable_standalone_scale_spline else None
+
+    def _plain_knots(self):
+        """What every host path that hands this layer's raw parameters to a library call asks (the one-call layer / stack / model
+        nodes, the chain pack, the one-launch read-out): is the forward exactly ``ops.kan_linear`` on them over ONE uniform knot
+        vector at orders 1..4?  That vector, else ``None`` (fixed symbolic edges, orders above 4, per-feature knot rows).  A feature
+        that changes what a layer computes adds its condition HERE."""
+        if self._symbolic is not None or self.spline_order > ops.FUSED_MAX_SPLINE_ORDER:      # (ops.high_order, without the call)
+            return None
+        knots = self._knots()
+        return knots if knots.dim() == 1 else None
+
+    def _refuse_fixed_edges(self, what: str) -> None:
+        if self._symbolic is not None:       # for a caller that keeps copies or slices of the raw parameters: they could not tell
+            raise NotImplementedError(f"a KANLinear with fixed symbolic edges cannot be {what} (unfix_symbolic first)")
+
+    def _fast_operands(self):
+        """``(base_weight, spline_weight, spline_scaler or None, knots)`` of a layer ``_plain_knots`` accepts, else ``None``"""
+        knots = self._plain_knots()
+        return None if knots is None else (self.base_weight, self.spline_weight, self._scaler(), knots)
 
     def _kept_operands(self):
         """``(base_weight, spline_weight, spline_scaler)`` with the fixed edges switched off: small torch ops on ``symbolic_keep``, so the
         fixed edges' entries get exactly zero gradient"""
-        keep = self.symbolic_keep
-        if self.enable_standalone_scale_spline:
-            return self.base_weight * keep, self.spline_weight, self.spline_scaler * keep
+        keep, scaler = self.symbolic_keep, self._scaler()
+        if scaler is not None:
+            return self.base_weight * keep, self.spline_weight, scaler * keep
         return self.base_weight * keep, self.spline_weight * keep.unsqueeze(-1), None
 
     def _forward_fixed(self, x: torch.Tensor) -> torch.Tensor:
@@ -257,18 +278,16 @@ class KANLinear(nn.Module):
     def read_out_blocks_in_one_launch(self, widths) -> bool:
         """would ``forward_parts`` over fp32 blocks of these widths run as one forward launch (``kagnn_kan_fwd_parts_ok``)?"""
         mode = self.precision if self.precision is not None else ops.default_precision()
-        return (self._symbolic is None and not ops.high_order(self.spline_order) and self._knots().dim() == 1 and ops.split_like(mode) and sum(widths) == self.in_features
+        return (self._plain_knots() is not None and ops.split_like(mode) and sum(widths) == self.in_features
                 and ops.parts_one_launch_widths_ok(tuple(int(w) for w in widths), self.out_features, self.grid_size, self.spline_order, mode))
 
     def forward_parts(self, parts, skip_gradients=None) -> torch.Tensor:
         """``forward(torch.cat(parts, dim=1))`` without the concatenation (``ops.kan_linear_parts``)."""
-        knots = self._knots()
-        if knots.dim() != 1 or ops.high_order(self.spline_order) or ops.layer_inputs_visible() or self._symbolic is not None:
-            # adaptive grid (per-feature knot rows) / orders above 4 / fixed symbolic edges: keep it simple; a collect_edge_l1 block: forward() must see the input
+        fast = None if ops.layer_inputs_visible() else self._fast_operands()
+        if fast is None:
+            # not the plain layer (_plain_knots): keep it simple; a collect_edge_l1 block: forward() must see the input
             return self.forward(ops.concat_columns([t.materialise() if isinstance(t, ops.AffineRows) else t for t in parts]))
-        scaler = self.spline_scaler if self.enable_standalone_scale_spline else None
-        return ops.kan_linear_parts(parts, self.base_weight, self.spline_weight, scaler, knots, self.grid_size,
-                                    self.spline_order, self.precision, skip_gradients)
+        return ops.kan_linear_parts(parts, *fast, self.grid_size, self.spline_order, self.precision, skip_gradients)
 
     # ------------------------------------------------------------------ not on the KAGNN path
     def b_splines(self, x: torch.Tensor) -> torch.Tensor:
@@ -293,8 +312,7 @@ class KANLinear(nn.Module):
                                       "function from order 12). A layer whose grid buffer already holds per-feature knot rows runs.")
         g, k = self.grid_size, self.spline_order
         new_grid = self._quantile_knots(x, g, margin)
-        scaler = self.spline_scaler if self.enable_standalone_scale_spline else None
-        fitted = ops.kan_grid_refit(x, self.grid, new_grid, self.spline_weight, scaler, g, k)
+        fitted = ops.kan_grid_refit(x, self.grid, new_grid, self.spline_weight, self._scaler(), g, k)
         self.grid.copy_(new_grid)
         self.spline_weight.data.copy_(fitted)
         self.refresh_knots()
@@ -362,8 +380,7 @@ class KANLinear(nn.Module):
 
     # ------------------------------------------------------------------ the edge functions phi_{o,i}
     def _edge_args(self):
-        scaler = self.spline_scaler if self.enable_standalone_scale_spline else None
-        return self.base_weight, self.spline_weight, scaler, self._knots(), self.grid_size, self.spline_order
+        return self.base_weight, self.spline_weight, self._scaler(), self._knots(), self.grid_size, self.spline_order
 
     def edge_l1(self, x: torch.Tensor) -> torch.Tensor:
         """``[out, in]``: the mean magnitude ``mean_n |phi_{o,i}(x[n,i])|`` of every edge's activation over the rows of ``x`` --
@@ -629,13 +646,12 @@ class KAN(nn.Module):
         """all layers' weight packs in one launch when the chain runs on the sparse-forward / split kernels"""
         first = self.layers[0]
         mode = first.precision if first.precision is not None else ops.default_precision()
-        if ops.layer_inputs_visible() or ops.high_order(self.spline_order) or not ops.split_like(mode) or any(l.precision != first.precision or l._knots().dim() != 1 or l._symbolic is not None for l in self.layers):
+        if ops.layer_inputs_visible() or not ops.split_like(mode) or x.size(0) == 0 or not ops._fits32(x, 1):
             return None
-        if x.size(0) == 0 or not ops._fits32(x, 1):
+        fast = [l._fast_operands() for l in self.layers]
+        if any(f is None or l.precision != first.precision for f, l in zip(fast, self.layers)):
             return None
-        return ops.kan_pack_chain([(l.base_weight, l.spline_weight,
-                                    l.spline_scaler if l.enable_standalone_scale_spline else None) for l in self.layers],
-                                  self.grid_size, self.spline_order, mode)
+        return ops.kan_pack_chain([f[:3] for f in fast], self.grid_size, self.spline_order, mode)
 
     def regularization_loss(self, regularize_activation=1.0, regularize_entropy=1.0, x: Optional[torch.Tensor] = None):
         """``x``: the chain's input -- every layer is then regularised on the activations of ITS input (the chain is walked)"""

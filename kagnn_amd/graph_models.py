@@ -17,7 +17,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import graph_ops, ops
-from .models import (FASTKAGATConv, FASTKAGCNConv, GIFASTKANLayer, GIKANLayer, KAGATConv, KAGCNConv, _has_hooks, conv_bn_dropout,
+from .models import (FASTKAGATConv, FASTKAGCNConv, GIFASTKANLayer, GIKANLayer, KAGATConv, KAGCNConv, conv_bn_dropout,
                      make_fastkan, make_kan)
 from .norm import BatchNorm1d
 
@@ -107,7 +107,7 @@ class _GraphLevel(nn.Module):
             raise NotImplementedError("edge_mask: the GINE convolutions are not supported inside the block")
         # GINE stacks (graph_regression/models.py:107-119): all convolutions + norms as ONE tape node where the shapes allow it
         if (edge_attr is not None and self.training and not (self.dropout.p > 0.0) and all(isinstance(c, GINEKANLayer) for c in self.conv)
-                and all(type(b) is BatchNorm1d for b in self.bn) and not any(_has_hooks(m) for m in list(self.conv) + list(self.bn))):
+                and all(type(b) is BatchNorm1d for b in self.bn) and ops._hook_free(list(self.conv) + list(self.bn))):
             h = graph_ops.gine_kan_stack(x, edge_attr, g, list(self.conv), list(self.bn))
             if h is not None:
                 return h

@@ -11,11 +11,13 @@ import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
+from .ekan import KAN, KANLinear
+from .norm import BatchNorm1d
 from .ops import (PREC_FP32, GraphIndex, _batchnorm_fwd_raw, _call, _chain_bwd_buffers, _chain_bwd_result, _chain_fwd_call,
-                  _chain_layers, _chain_plan, _chain_saved, _chain_unsaved, _fits32, _fixed_args, _kan_bwd_input_raw,
-                  _kan_bwd_weight_raw, _kan_fwd_raw, _ld, _need_cuda, _on_operand_device, _ptr, _ptr_array, _rows, _same_knots,
-                  _segment_broadcast_raw, _segment_pool_raw, _sizes, _stream, _weights_key, _ws, batch_graph_index, default_precision,
-                  kan_pack_chain, layer_inputs_visible, split_like)
+                  _chain_layers, _chain_plan, _chain_saved, _chain_unsaved, _fits32, _fixed_args, _hook_free, _kan_bwd_input_raw,
+                  _kan_bwd_weight_raw, _kan_fwd_raw, _ld, _need_cuda, _on_operand_device, _ptr, _ptr_array, _rows,
+                  _segment_broadcast_raw, _segment_pool_raw, _sizes, _stream, _uniform_chain, _weights_key, _ws, batch_graph_index,
+                  default_precision, kan_pack_chain, layer_inputs_visible, split_like)
 
 
 class _GineKanLayerFn(Function):
@@ -85,6 +87,21 @@ class _StackState:
     """what the backward of the GINE stack needs (kept by the tape node that ran the forward)"""
     __slots__ = ("g", "self_scales", "G", "K", "mode", "nconv", "nl", "H", "fb", "db", "xg", "ea", "acts_all", "h_all", "stats", "packs",
                  "knots", "bnw", "sws", "scs")
+
+    def saved(self):
+        """``(meta, tensors)``: what a tape node keeps as a plain attribute, and what it hands to ``save_for_backward``"""
+        return ((self.g, self.self_scales, self.G, self.K, self.mode, self.nconv, self.nl, self.H, self.fb, self.db),
+                (self.xg, self.ea, self.acts_all, self.h_all, self.stats, self.packs, self.knots, *self.bnw, *self.sws, *self.scs))
+
+    @classmethod
+    def restored(cls, meta, tensors):
+        """the state back from ``saved()`` and the saved tensors that begin with its own -> ``(state, the tensors after them)``"""
+        st = cls()
+        st.g, st.self_scales, st.G, st.K, st.mode, st.nconv, st.nl, st.H, st.fb, st.db = meta
+        st.xg, st.ea, st.acts_all, st.h_all, st.stats, st.packs, st.knots = tensors[:7]
+        a, n = 7 + st.nconv, st.nconv * st.nl
+        st.bnw, st.sws, st.scs = tensors[7:a], tensors[a:a + n], tensors[a + n:a + 2 * n]
+        return st, tensors[a + 2 * n:]
 
 
 def _gine_stack_fwd_raw(x, edge_attr, g, self_scales, knots, grid_size, spline_order, mode, running, momentum, eps, nconv, nl, params):
@@ -189,22 +206,15 @@ class _GineKanStackFn(Function):
     @_on_operand_device
     def forward(ctx, x, edge_attr, g, self_scales, knots, grid_size, spline_order, mode, running, momentum, eps, nconv, nl, *params):
         h, st = _gine_stack_fwd_raw(x, edge_attr, g, self_scales, knots, grid_size, spline_order, mode, running, momentum, eps, nconv, nl, params)
-        ctx.meta = (st.g, st.self_scales, st.G, st.K, st.mode, st.nconv, st.nl, st.H, st.fb, st.db)
-        ctx.save_for_backward(st.xg, st.ea, st.acts_all, st.h_all, st.stats, st.packs, st.knots, *st.bnw, *st.sws, *st.scs)
+        ctx.meta, tensors = st.saved()
+        ctx.save_for_backward(*tensors)
         return h
 
     @staticmethod
     @once_differentiable
     @_on_operand_device
     def backward(ctx, gh):
-        st = _StackState()
-        st.g, st.self_scales, st.G, st.K, st.mode, st.nconv, st.nl, st.H, st.fb, st.db = ctx.meta
-        t = ctx.saved_tensors
-        st.xg, st.ea, st.acts_all, st.h_all, st.stats, st.packs, st.knots = t[:7]
-        nconv, nl = st.nconv, st.nl
-        st.bnw = t[7:7 + nconv]
-        st.sws = t[7 + nconv:7 + nconv + nconv * nl]
-        st.scs = t[7 + nconv + nconv * nl:7 + nconv + 2 * nconv * nl]
+        st, _ = _StackState.restored(ctx.meta, ctx.saved_tensors)
         gx, gea, grads = _gine_stack_bwd_raw(gh, st, ctx.needs_input_grad[1])
         return (gx, gea, None, None, None, None, None, None, None, None, None, None, None, *grads)
 
@@ -219,30 +229,21 @@ def _gine_stack_plan(x, convs, bns):
             or x.size(0) < 2 or len(convs) < 2):
         return None
     H = x.size(1)
-    first = None
-    nl = None
-    all_layers = []
+    nl, all_layers = 0, []
     for conv, bn in zip(convs, bns):
-        layers = list(getattr(conv.nn, "layers", []))
-        if nl is None:
-            nl = len(layers)
-        if not (1 <= len(layers) == nl) or any(type(l).__name__ != "KANLinear" for l in layers):
+        layers = getattr(conv.nn, "layers", ())
+        nl = nl or len(layers)
+        if not (1 <= len(layers) == nl) or not (bn.training and bn.affine and bn.num_features == H):
             return None
-        if first is None:
-            first = layers[0]
-        for l in layers:
-            if (l.in_features != H or l.out_features != H or l.precision != first.precision or l.grid_size != first.grid_size
-                    or l.spline_order != first.spline_order or not l.enable_standalone_scale_spline
-                    or getattr(l, "_symbolic", None) is not None):          # (fixed symbolic edges: the layer runs its own forward)
-                return None
         all_layers += layers
-        if not (bn.training and bn.affine and bn.num_features == H):
+    for l in all_layers:
+        if type(l) is not KANLinear or l.in_features != H or l.out_features != H:
             return None
     #  ONE knot vector for every layer of every convolution, verified -- not assumed from the first layer
-    knots = [l._knots() for l in all_layers]
-    if any(k.dim() != 1 or k.numel() != knots[0].numel() for k in knots) or not _same_knots(all_layers, knots):
+    plan = _uniform_chain(all_layers)
+    if plan is None:
         return None
-    mode = first.precision if first.precision is not None else default_precision()
+    mode, first = plan[0], all_layers[0]
     if not split_like(mode) or first.spline_order != 3 or first.grid_size + first.spline_order > 8 or H > 64 or len(convs) * nl > 16:
         return None
     return first, nl, mode
@@ -293,7 +294,7 @@ def gine_kan_layer(x, edge_attr, g: "GraphIndex", self_scale: float, net, batch_
     if not _GINE_LAYER_ABI or layer_inputs_visible() or torch.compiler.is_compiling() or not x.is_cuda or x.dtype != torch.float32 or x.size(0) < 2:
         return None
     layers = list(getattr(net, "layers", []))
-    if not (1 <= len(layers) <= 8) or any(type(l).__name__ != "KANLinear" for l in layers):
+    if not (1 <= len(layers) <= 8) or any(type(l) is not KANLinear for l in layers):
         return None
     plan = _chain_plan(layers)
     if plan is None or not split_like(plan[0]):
@@ -400,41 +401,28 @@ class _KaginModelFn(Function):
             bw_c, sw_c, sc_c = bw.contiguous(), sw.contiguous(), None if sc is None else sc.contiguous()
             y, pd = _kan_fwd_raw(acts[-1], bw_c, sw_c, sc_c, plan.ro_knots[i], plan.ro_G, plan.ro_K, plan.ro_modes[i],
                                  None if packs is None else packs[i], _weights_key(bw, sw, sc) if packs is not None else None)
-            acts.append(y); pds.append(pd); kept.append((sw_c, sc_c))
+            acts.append(y); pds.append(pd); kept += [sw_c, sc_c]
         #  everything the backward reads goes through save_for_backward (autograd's in-place checks on weights and
         # activations apply, a retained graph can run twice) and the OUTPUT is not among it: acts[-1] in the state made an
         # output -> grad_fn -> state -> output cycle that kept a step's whole activation set alive until the cyclic collector ran
-        flat_kept = []
-        for sw_c, sc_c in kept:
-            flat_kept += [sw_c, sc_c]
-        tensors = [xi, ei, st.xg, st.ea, st.acts_all, st.h_all, st.stats, st.packs, st.knots, *st.bnw, *st.sws, *st.scs,
-                   *acts[:-1], *pds, *flat_kept]
-        ctx.save_for_backward(*tensors)
-        ctx.meta = (plan, g, seg, ashapes, bshapes, h.size(0), len(st.bnw), len(st.sws),
-                    (st.g, st.self_scales, st.G, st.K, st.mode, st.nconv, st.nl, st.H, st.fb, st.db))
+        stmeta, stack_tensors = st.saved()
+        ctx.save_for_backward(xi, ei, *stack_tensors, *acts[:-1], *pds, *kept)
+        ctx.meta = (plan, g, seg, ashapes, bshapes, h.size(0), stmeta)
         return acts[-1]
 
     @staticmethod
     @once_differentiable
     @_on_operand_device
     def backward(ctx, gout):
-        plan, g, seg, ashapes, bshapes, n, nbn, nsw, stmeta = ctx.meta
-        t = ctx.saved_tensors
-        st = _StackState()
-        st.g, st.self_scales, st.G, st.K, st.mode, st.nconv, st.nl, st.H, st.fb, st.db = stmeta
-        xi, ei, st.xg, st.ea, st.acts_all, st.h_all, st.stats, st.packs, st.knots = t[:9]
-        o = 9
-        st.bnw = t[o:o + nbn]; o += nbn
-        st.sws = t[o:o + nsw]; o += nsw
-        st.scs = t[o:o + nsw]; o += nsw
+        plan, g, seg, ashapes, bshapes, n, stmeta = ctx.meta
+        xi, ei, *t = ctx.saved_tensors
+        st, t = _StackState.restored(stmeta, t)
         nr = plan.n_readout
-        acts = t[o:o + nr]; o += nr
-        pds = t[o:o + nr]; o += nr
-        kept = [(t[o + 2 * i], t[o + 2 * i + 1]) for i in range(nr)]
+        acts, pds, kept = t[:nr], t[nr:2 * nr], t[2 * nr:]
         gy = _rows(gout)
         ro_grads = [None] * (3 * plan.n_readout)
         for i in reversed(range(plan.n_readout)):
-            x_i, (sw_c, sc_c) = acts[i], kept[i]
+            x_i, sw_c, sc_c = acts[i], kept[2 * i], kept[2 * i + 1]
             fin, fout, G, K, mode = x_i.size(1), sw_c.size(0), plan.ro_G, plan.ro_K, plan.ro_modes[i]
             gx = _kan_bwd_input_raw(x_i, gy, plan.ro_knots[i], pds[i], fin, fout, G, K, mode)
             ro_grads[3 * i:3 * i + 3] = _kan_bwd_weight_raw(x_i, gy, plan.ro_knots[i], sw_c, sc_c, fin, fout, G, K, mode, True)
@@ -566,17 +554,6 @@ _GINE_MODEL_CALL = True      # False: _KaginModelFn's per-operation library call
 _GINE_MODEL_NODE = True      # False: the model runs as its five kinds of tape nodes (bit-identical; module attribute for the A/B test)
 
 
-def _hook_free(mods) -> bool:
-    mod = torch.nn.modules.module
-    if (mod._global_forward_hooks or mod._global_forward_pre_hooks or mod._global_backward_hooks
-            or getattr(mod, "_global_backward_pre_hooks", None)):
-        return False
-    for m in mods:
-        if m._forward_hooks or m._forward_pre_hooks or m._backward_hooks or m._backward_pre_hooks:
-            return False
-    return True
-
-
 def kagin_regression_forward(model, data):
     """``KAGINRegression.forward(data)`` as ONE tape node (``_KaginModelFn``), or ``None`` when the model or the batch is outside
     what the node covers (the caller then runs its modules one by one): training mode, no dropout, embedding-table encoders on
@@ -594,10 +571,11 @@ def kagin_regression_forward(model, data):
     atabs, btabs = fast[0](x), fast[1](e)
     if atabs is None or btabs is None:
         return None
+    from .graph_models import GINEKANLayer, _segment_ptr     # (graph_models imports this module)
     convs, bns, ro = list(model.conv), list(model.bn), list(getattr(model.kan, "layers", []))
-    if not ro or any(type(l).__name__ != "KANLinear" for l in ro) or type(model.kan).__name__ != "KAN":
+    if not ro or any(type(l) is not KANLinear for l in ro) or type(model.kan) is not KAN:
         return None
-    if any(type(c).__name__ != "GINEKANLayer" for c in convs) or any(type(b).__name__ != "BatchNorm1d" or not hasattr(b, "step") for b in bns):
+    if any(type(c) is not GINEKANLayer for c in convs) or any(type(b) is not BatchNorm1d for b in bns):
         return None
     H = atabs[0].size(1)
     if btabs[0].size(1) != H or x.size(0) < 2:
@@ -612,18 +590,17 @@ def kagin_regression_forward(model, data):
         return None
     first, nl, mode = plan_s
     G_r, K_r = ro[0].grid_size, ro[0].spline_order
-    ro_knots, ro_modes = [], []
-    for l in ro:
-        k = l._knots()
-        if k.dim() != 1 or l.grid_size != G_r or l.spline_order != K_r or G_r + K_r > 16 or K_r > 4 or getattr(l, "_symbolic", None) is not None:
+    ro_knots, ro_modes, rparams = [], [], []
+    for l in ro:                          # (the read-out may differ per layer in precision, knots and scaler: plain layers is all it asks)
+        operands = l._fast_operands()
+        if operands is None or l.grid_size != G_r or l.spline_order != K_r or G_r + K_r > 16:
             return None
         m = l.precision if l.precision is not None else default_precision()
         if split_like(m) and max(l.in_features, l.out_features) > 7680:
             m = PREC_FP32
-        ro_knots.append(k); ro_modes.append(int(m))
+        ro_knots.append(operands[3]); ro_modes.append(int(m)); rparams += operands[:3]
     if ro[0].in_features != H:
         return None
-    from .graph_models import _segment_ptr
     g = batch_graph_index(data, x.size(0))
     seg = _segment_ptr(data)
     sparams, scales, running, momentum, eps = _gine_stack_args(convs, bns)
@@ -632,9 +609,6 @@ def kagin_regression_forward(model, data):
     plan.scales, plan.running, plan.momentum, plan.eps, plan.nconv, plan.nl = scales, running, momentum, eps, len(convs), nl
     plan.knots, plan.G, plan.K, plan.mode = first._knots(), first.grid_size, first.spline_order, mode
     plan.ro_knots, plan.ro_G, plan.ro_K, plan.ro_modes = ro_knots, G_r, K_r, ro_modes
-    rparams = []
-    for l in ro:
-        rparams += [l.base_weight, l.spline_weight, l.spline_scaler if l.enable_standalone_scale_spline else None]
     if _GINE_MODEL_CALL and H <= 64 and len(atabs) <= 16 and len(btabs) <= 16 and len(ro) <= 8:
         return _KaginModelCallFn.apply(x, e, g, seg, plan, model, *atabs, *btabs, *sparams, *rparams)
     return _KaginModelFn.apply(x, e, g, seg, plan, *atabs, *btabs, *sparams, *rparams)

@@ -240,13 +240,6 @@ class GIFASTKANLayer(_SumAggregateConv):
 _FUSED_NORM_BACKWARD = os.environ.get("KAGNN_FUSED_NORM_BACKWARD", "1") != "0"    # conv + BatchNorm1d as one tape node
 
 
-def _has_hooks(m: nn.Module) -> bool:
-    mod = torch.nn.modules.module
-    return bool(m._forward_hooks or m._forward_pre_hooks or m._backward_hooks or getattr(m, "_backward_pre_hooks", None)
-                or mod._global_forward_hooks or mod._global_forward_pre_hooks or mod._global_backward_hooks
-                or getattr(mod, "_global_backward_pre_hooks", None))
-
-
 def conv_bn_dropout(conv, bn, dropout, x, g, *conv_args, skip_gradient=None, lazy=False):
     """The epilogue ``dropout(bn(conv(x)))`` of every message-passing layer (reference
     ``node_classification_clean/models.py:198-201``, ``graph_regression/models.py:107-119``), fused (SURVEY.md 8(f)
@@ -256,38 +249,33 @@ def conv_bn_dropout(conv, bn, dropout, x, g, *conv_args, skip_gradient=None, laz
     seed would repeat the mask on every replay)."""
     # ``lazy`` (only _NodeModel.forward asks): return an ops.AffineRows -- the convolution's raw output plus the norm's per-column
     # affine -- instead of the normalised rows, when the one-node form below runs; ``x`` may itself be one (the previous layer's)
-    x_in = x
+    stock = torch.compiler.is_compiling() or type(dropout) is not nn.Dropout or not isinstance(bn, BatchNorm1d) or not _FUSED_EPILOGUE
+    dropping = not stock and dropout.training and dropout.p > 0.0
+    # may the norm join the convolution's tape node?  A training-mode affine norm, no dropout behind it, no hooks on either module
+    # (their intermediate tensor is never exposed); a subclass with its own forward must see its forward called
+    joins = (not stock and (isinstance(x, ops.AffineRows) or x.is_cuda) and _FUSED_NORM_BACKWARD and bn.training and bn.affine and not dropping and type(bn).forward is BatchNorm1d.forward
+             and ops._hook_free((conv, bn)))
+    gin = joins and isinstance(conv, _SumAggregateConv) and not conv_args and type(conv).forward is _SumAggregateConv.forward
     if isinstance(x, ops.AffineRows):
-        ok = (_FUSED_EPILOGUE and _FUSED_NORM_BACKWARD and not torch.compiler.is_compiling() and type(dropout) is nn.Dropout
-              and isinstance(bn, BatchNorm1d) and isinstance(conv, _SumAggregateConv) and not conv_args and bn.training and bn.affine
-              and not (dropout.training and dropout.p > 0.0) and not _has_hooks(conv) and not _has_hooks(bn)
-              and type(conv).forward is _SumAggregateConv.forward and type(bn).forward is BatchNorm1d.forward
-              and ops.default_activation_dtype() == torch.float32)
-        if ok:
+        if gin and ops.default_activation_dtype() == torch.float32:
             h = conv.forward_fused_norm(x, g, bn, skip_gradient, lazy=lazy)
             if h is not None:
                 return h
-        x = x_in.materialise()                            # a consumer that cannot fold the affine: write the rows out
-    fused = (_FUSED_EPILOGUE and x.is_cuda and not torch.compiler.is_compiling() and type(dropout) is nn.Dropout
-             and isinstance(bn, BatchNorm1d)
-             and not (dropout.p > 0.0 and dropout.training and torch.cuda.is_current_stream_capturing())
+        x = x.materialise()                               # a consumer that cannot fold the affine: write the rows out
+    fused = (not stock and x.is_cuda
+             and not (dropping and torch.cuda.is_current_stream_capturing())
              # a frozen BatchNorm (bn.eval()) under an active dropout: the fused pass ties the mask to the norm's training
              # flag, the reference's dropout(bn(.)) does not -- stock modules then
-             and (bn.training or not (dropout.training and dropout.p > 0.0)))
+             and (bn.training or not dropping))
     if not fused:
         return dropout(bn(conv(x, g, *conv_args)))
-    if (_FUSED_NORM_BACKWARD and isinstance(conv, _SumAggregateConv) and not conv_args and bn.training and bn.affine
-            and not (dropout.training and dropout.p > 0.0) and not _has_hooks(conv) and not _has_hooks(bn)
-            # (a subclass with its own forward must see its forward called)
-            and type(conv).forward is _SumAggregateConv.forward and type(bn).forward is BatchNorm1d.forward):
+    if gin:
         h = conv.forward_fused_norm(x, g, bn, skip_gradient,      # convolution + norm as one tape node
                                     lazy=lazy and ops.default_activation_dtype() == torch.float32 and x.dtype == torch.float32)
         if h is not None:
             return h
     # GINE message passing (graph_regression/models.py:107-119): convolution + norm as one tape node, one library call each way
-    if (_FUSED_NORM_BACKWARD and len(conv_args) == 1 and hasattr(conv, "forward_fused_norm") and not isinstance(conv, _SumAggregateConv)
-            and bn.training and bn.affine and not (dropout.training and dropout.p > 0.0) and not _has_hooks(conv) and not _has_hooks(bn)
-            and type(bn).forward is BatchNorm1d.forward and x.size(0) > 1):
+    if joins and len(conv_args) == 1 and hasattr(conv, "forward_fused_norm") and not isinstance(conv, _SumAggregateConv) and x.size(0) > 1:
         h = conv.forward_fused_norm(x, g, conv_args[0], bn)
         if h is not None:
             return h
@@ -344,9 +332,10 @@ class _NodeModel(nn.Module):
         # read-out on the split-precision cubic kernels, <= 64 classes, blocks wider than 32 columns, dropout off (the
         # per-layer conditions -- training-mode norm, no hooks, fp32 rows -- are checked by conv_bn_dropout)
         # (not inside a kagnn_amd.edge_mask block: the aggregation that folds the affine is unit-weight only)
-        lazy = (_LAZY_NORM and split and not ops.aggregation_visible() and x.is_cuda and not torch.compiler.is_compiling() and isinstance(self.lay_out, KANLinear) and self.lay_out.spline_order == 3
-                and self.lay_out.grid_size + 3 <= 8 and self.lay_out.out_features <= 64 and not (self.dropout.training and self.dropout.p > 0.0)
-                and all(bn.num_features > 32 for bn in self.bns)
+        lazy = (_LAZY_NORM and split and not ops.aggregation_visible() and x.is_cuda and not torch.compiler.is_compiling() and isinstance(self.lay_out, KANLinear)
+                and not (self.dropout.training and self.dropout.p > 0.0)
+                and ops.parts_affine_widths_ok(self.lay_out.out_features, self.lay_out.grid_size, self.lay_out.spline_order,
+                                               [bn.num_features for bn in self.bns])
                 and ops.split_like(self.lay_out.precision if self.lay_out.precision is not None else ops.default_precision()))
         skips = []
         for conv, bn in zip(self.convs, self.bns):

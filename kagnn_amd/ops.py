@@ -1727,24 +1727,44 @@ def _same_knots(layers, knots) -> bool:
     return hit
 
 
+def _hook_free(mods) -> bool:
+    """no hook, global or on one of ``mods`` (a hook must see a tensor the fused calls never expose): the global tables once, then the modules"""
+    mod = torch.nn.modules.module
+    if (mod._global_forward_hooks or mod._global_forward_pre_hooks or mod._global_backward_hooks
+            or getattr(mod, "_global_backward_pre_hooks", None)):
+        return False
+    for m in mods:
+        if m._forward_hooks or m._forward_pre_hooks or m._backward_hooks or m._backward_pre_hooks:
+            return False
+    return True
+
+
+def _uniform_chain(layers):
+    """What a one-call node over several ``KANLinear`` layers needs of them (``_chain_plan``, ``graph_ops._gine_stack_plan``): each
+    the plain layer (``KANLinear._plain_knots``) with the stand-alone spline scale, ONE precision, grid size and spline order, and --
+    the library evaluates them all on ONE knot vector -- grids that ARE equal, verified: uniform but different grids (another
+    grid_range, update_grid with grid_eps = 1) must not be folded onto the first layer's.  ``None``, or ``(mode, one knot vector per
+    layer)``.  Reads no parameter: the stack plan runs once per step of a host-bound model."""
+    precision, G, K = layers[0].precision, layers[0].grid_size, layers[0].spline_order
+    knots = []
+    for l in layers:
+        k = l._plain_knots()
+        if k is None or l.precision != precision or l.grid_size != G or l.spline_order != K or not l.enable_standalone_scale_spline:
+            return None
+        knots.append(k)
+    if not _same_knots(layers, knots):
+        return None
+    return (precision if precision is not None else default_precision()), knots
+
+
 def _chain_plan(layers):
     """Can the fused convolution nodes run this chain of ``KANLinear`` layers as one library call?  ``None``, or ``(mode, one knot
     vector per layer -- all equal --, the flat parameter list)``.  What ``gin_kan_layer`` and ``graph_ops.gine_kan_layer`` both
-    ask: one precision and one grid for all layers, at most 16 coefficients, the stand-alone spline scale, and -- the library
-    evaluates the whole chain on ONE knot vector -- uniform grids that ARE equal: layers with uniform but different grids (another
-    grid_range, update_grid with grid_eps = 1) must not be folded onto the first layer's."""
-    first = layers[0]
-    mode = first.precision if first.precision is not None else default_precision()
-    if any(high_order(l.spline_order) for l in layers):
-        return None                                      # the fused calls take orders 1..4: the caller composes the operations
-    if any(getattr(l, "_symbolic", None) is not None for l in layers):
-        return None                                      # a layer with fixed symbolic edges runs its own forward (KANLinear.fix_symbolic)
-    if any(l.precision != first.precision or l.grid_size != first.grid_size or l.spline_order != first.spline_order
-           or l.grid_size + l.spline_order > 16 or not l.enable_standalone_scale_spline for l in layers):
+    ask: a uniform chain (``_uniform_chain``) of at most 16 coefficients within the split kernels' addressing."""
+    plan = None if layers[0].grid_size + layers[0].spline_order > 16 else _uniform_chain(layers)
+    if plan is None:
         return None
-    knots = [l._knots() for l in layers]
-    if any(k.dim() != 1 or k.numel() != knots[0].numel() for k in knots) or not _same_knots(layers, knots):
-        return None
+    mode, knots = plan
     # (gin_kan_layer's condition: the split kernels' 32-bit addressing, see _fits32; gine_kan_layer takes split-like modes only)
     if split_like(mode) and max(max(l.in_features, l.out_features) for l in layers) > 7680:
         return None
@@ -1975,9 +1995,12 @@ class _KANLinearPartsFn(Function):
 def parts_affine_ok(fout: int, grid_size: int, spline_order: int, parts, lazy) -> bool:
     """can the read-out kernels apply a folded BatchNorm1d to these blocks?  (``kagnn_kan_linear_*_affine``: cubic layers of
     <= 8 coefficients and <= 64 outputs; the weight-gradient kernel needs blocks wider than 32 columns)"""
-    if spline_order != 3 or grid_size + spline_order > 8 or fout > 64:
-        return False
-    return all(not z or int(t.size(1)) > 32 for t, z in zip(parts, lazy))
+    return parts_affine_widths_ok(fout, grid_size, spline_order, [int(t.size(1)) for t, z in zip(parts, lazy) if z])
+
+
+def parts_affine_widths_ok(fout: int, grid_size: int, spline_order: int, lazy_widths) -> bool:
+    """``parts_affine_ok`` before the blocks exist: ``lazy_widths`` are the widths of the blocks that would arrive folded"""
+    return spline_order == 3 and grid_size + spline_order <= 8 and fout <= 64 and all(w > 32 for w in lazy_widths)
 
 
 def kan_linear_parts(parts, base_weight, spline_weight, spline_scaler, knots, grid_size: int, spline_order: int,

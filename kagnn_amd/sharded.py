@@ -264,8 +264,7 @@ class ShardedKANLinear(nn.Module):
         if full.spline_order > 4:
             raise ValueError("sharded KANLinear layers are not supported at spline_order above 4 (the exact-fp32 kernels of these "
                              "orders take neither packed= nor out=)")
-        if getattr(full, "_symbolic", None) is not None:
-            raise NotImplementedError("a KANLinear with fixed symbolic edges cannot be sharded (unfix_symbolic first)")
+        full._refuse_fixed_edges("sharded")
         self.grid_size, self.spline_order = full.grid_size, full.spline_order
         self.out_features = full.out_features
         if columns is None:
@@ -279,8 +278,8 @@ class ShardedKANLinear(nn.Module):
             self.out_lo, self.out_hi = rank * ow, (rank + 1) * ow
         self.base_weight = nn.Parameter(full.base_weight.detach()[:, columns].clone())
         self.spline_weight = nn.Parameter(full.spline_weight.detach()[:, columns].clone())
-        self.spline_scaler = (nn.Parameter(full.spline_scaler.detach()[:, columns].clone())
-                              if full.enable_standalone_scale_spline else None)
+        scaler = full._scaler()
+        self.spline_scaler = None if scaler is None else nn.Parameter(scaler.detach()[:, columns].clone())
         self.register_buffer("knots", full.grid[0].detach().clone())
         self.precision = full.precision
 
@@ -784,8 +783,7 @@ class TransposedShardedGIKANLayer(nn.Module):
         for l in conv.nn.layers:
             if l.in_features % self.world or l.out_features % self.world:
                 raise ValueError("layer widths must be divisible by the world size")
-            if getattr(l, "_symbolic", None) is not None:
-                raise NotImplementedError("a KANLinear with fixed symbolic edges cannot be sharded (unfix_symbolic first)")
+            l._refuse_fixed_edges("sharded")
         import copy
         self.layers = nn.ModuleList(copy.deepcopy(l) for l in conv.nn.layers)      # replicated parameters
         self._flat_pending = None          # (engine run id, gradients as they stood when that backward pass reached the module)
@@ -850,7 +848,7 @@ class TransposedShardedGIKANLayer(nn.Module):
             xin, xout = self._xch[("in", n, h.size(1))], self._xch[("out", n, self.layers[-1].out_features // self.world)]
         h = _P2PTranspose.apply(h, xin, True, n) if xin is not None else _ColsToRows.apply(h, self.group)
         for layer in self.layers:
-            sc = layer.spline_scaler if layer.enable_standalone_scale_spline else None
+            sc = layer._scaler()
             g = self.group
             wrap = (lambda p: _SumGradAcrossRanks.apply(p, g)) if self.sync_in_backward is True else (lambda p: p)
             h = self.local_ops.kan_linear(h, wrap(layer.base_weight), wrap(layer.spline_weight),

@@ -19,7 +19,7 @@ import pytest
 import torch
 
 import kagnn_amd
-from kagnn_amd import ops
+from kagnn_amd import graph_ops, ops
 from kagnn_amd.symbolic import SYMBOLIC_LIB
 from oracle import kan_oracle as orc
 from helpers import TOL, assert_close, must_fail, oracle_kan_linear_fwd_bwd, prenorm_bias_noise
@@ -498,7 +498,9 @@ FUSED = ("gin_kan_layer", "gine_kan", "kagin_model", "pack_chain", "fwd_parts")
 class _CallLog:
     def __init__(self, monkeypatch):
         self.names, real = [], ops._call
-        monkeypatch.setattr(ops, "_call", lambda name, *a: (self.names.append(name), real(name, *a))[1])
+        logged = lambda name, *a: (self.names.append(name), real(name, *a))[1]
+        monkeypatch.setattr(ops, "_call", logged)
+        monkeypatch.setattr(graph_ops, "_call", logged)         # (graph_ops imported the function by name)
 
     def take(self):
         got, self.names[:] = list(self.names), []
@@ -518,8 +520,10 @@ def _first_kanlinear(module):
     return next(m for m in module.modules() if isinstance(m, kagnn_amd.KANLinear))
 
 
-def _fix_one_edge_and_compare(model, layer_name, run, oracle, log, what):
-    """``run()`` -> (logits, backward done); ``oracle()`` -> (logits64, {name: grad64}) of the unfixed model on the same state"""
+def _fix_one_edge_and_compare(model, layer_name, run, oracle, log, what, limits=None):
+    """``run()`` -> (logits, backward done); ``oracle()`` -> (logits64, {name: grad64}) of the unfixed model on the same state.
+    ``limits``: {part of an entry point's name: how many such calls the step with the fixed edge may make} -- for a model whose one
+    call covers everything before the fix, so that the layers around the fixed one then run MORE fused calls than before, not fewer"""
     layer = dict(model.named_modules())[layer_name]
     o, i = EDGE
     with torch.no_grad():
@@ -538,7 +542,10 @@ def _fix_one_edge_and_compare(model, layer_name, run, oracle, log, what):
     out = run()
     calls_fixed = log.take()
     assert "kagnn_symbolic_edges_fwd" in calls_fixed and "kagnn_symbolic_edges_bwd" in calls_fixed, what
-    if _fused(calls_before):
+    if limits is not None:
+        for tag, most in limits.items():
+            assert sum(tag in n for n in calls_fixed) <= most, (what, tag, "the fixed layer still ran inside a fused entry point", calls_fixed)
+    elif _fused(calls_before):
         assert len(_fused(calls_fixed)) < len(_fused(calls_before)), (what, "the fixed layer still ran inside a fused entry point")
     assert_close(out, want, MODEL_TOL, what=f"{what}: logits")
     checked = 0
@@ -619,6 +626,56 @@ def test_kagin_with_one_fixed_edge(monkeypatch):
         return want.detach(), {q: v.grad for q, v in st.items() if v.is_floating_point() and v.requires_grad}
 
     _fix_one_edge_and_compare(model, layer_name, run, oracle, _CallLog(monkeypatch), "KAGIN")
+
+
+# the fixed edge's place -> what the step with it may still run: never the whole-model call; with the edge in a convolution not the
+# stack call either, and the one-call layer node for the OTHER convolution only; with it in the read-out no chain pack, and the convolutions as the ONE stack call each way
+REGRESSION_PLACES = {
+    "conv.1": ("conv.1.nn.layers.0", {"kagin_model": 0, "gine_kan_stack": 0, "gine_kan_layer_fwd": 1, "gine_kan_layer_bwd": 1}),
+    "read-out": ("kan.layers.0", {"kagin_model": 0, "pack_chain": 0, "gine_kan_stack_fwd": 1, "gine_kan_stack_bwd": 1, "gine_kan_layer": 0}),
+}
+
+
+@pytest.mark.parametrize("place", list(REGRESSION_PLACES))
+def test_kagin_regression_with_one_fixed_edge(monkeypatch, place):
+    """``KAGINRegression`` with embedding encoders runs as ONE library call each way (``kagnn_kagin_model_fwd / _bwd``) before the fix and
+    after ``unfix_symbolic``, and must leave that call -- and the stack call, for an edge in a convolution -- while the edge is fixed"""
+    layer_name, limits = REGRESSION_PLACES[place]
+    gen = torch.Generator().manual_seed(37)
+    graphs, per, H = 4, 12, 16
+    ptr = torch.arange(graphs + 1) * per
+    ei = torch.cat([torch.randint(0, per, (2, 30), generator=gen) + int(ptr[k]) for k in range(graphs)], dim=1)
+    x = torch.randint(0, 21, (graphs * per, 1), generator=gen)
+    ea = torch.randint(0, 4, (ei.size(1),), generator=gen)
+    batch = torch.repeat_interleave(torch.arange(graphs), per)
+    data = SimpleNamespace(x=x.to(DEV), edge_index=ei.to(DEV), edge_attr=ea.to(DEV), batch=batch.to(DEV), ptr=ptr.to(DEV), num_graphs=graphs)
+    gout = torch.randn(graphs, 1, generator=gen)
+    torch.manual_seed(38)
+    model = kagnn_amd.KAGINRegression(1, 1, 2, H, 2, 4, 3, 1, 0.0, True)
+    model.atom_encoder = kagnn_amd.graph_models.AtomEncoder(H, [21])
+    model.bond_encoder.bond_embedding_list = torch.nn.ModuleList([torch.nn.Embedding(4, H)])
+    model = model.to(DEV).train()
+    assert isinstance(dict(model.named_modules())[layer_name], kagnn_amd.KANLinear)
+    log = _CallLog(monkeypatch)
+
+    def run():
+        out = model(data)
+        out.backward(gout.to(DEV))
+        return out
+
+    def oracle():
+        frozen = ("grid", "eps", "running_mean", "running_var", "num_batches_tracked")
+        st = {q: (v.detach().cpu().double().requires_grad_(True) if v.is_floating_point() and not q.endswith(frozen)
+                  else v.detach().cpu().double() if v.is_floating_point() else v.detach().cpu()) for q, v in model.state_dict().items()}
+        want = orc.graph_regression_forward(x, ei, ea.view(-1, 1), batch, graphs, st, "kan", 2, 3)
+        want.backward(gout.double())
+        return want.detach(), {q: v.grad for q, v in st.items() if v.is_floating_point() and v.requires_grad}
+
+    run()
+    model.zero_grad(set_to_none=True)
+    first = log.take()
+    assert "kagnn_kagin_model_fwd" in first and "kagnn_kagin_model_bwd" in first, first     # this shape runs the whole-model call
+    _fix_one_edge_and_compare(model, layer_name, run, oracle, log, f"KAGINRegression {place}", limits=limits)
 
 
 def test_auto_symbolic_applies_the_rule_to_the_suggestions():
